@@ -13,7 +13,12 @@ to rank 0 over RCCL (the aggregator's input).  --mode wires-dev times prove()
 alone from wire matrices already resident in HBM (round-1 headline, reported as
 prove_only for comparison).
 
-Also reported (one JSON line, rank 0):
+A plain run sets up, warms up, times the steps and prints the headline line
+(metric, value, ms_per_step, the configuration and prover 0's stage times).
+--dump-outputs DIR also writes the proofs of the last timed step (see
+dump_outputs).  Everything below runs only under --full, after the timed region.
+
+Also reported with --full (one JSON line, rank 0):
   roofline      the wires LDE (NTT) kernel: algorithmic bytes 8*(n+N) per column
                 / its HIP-event-timed duration, vs the 8 TB/s HBM3E peak
   cpu_baseline  the CPU restatement of the same prover (oracle/prover.c, "port";
@@ -165,6 +170,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run and report everything else: the warmup proofs' "
+                         "verification, the kernels alone (roofline), prove-only, one-proof latency, aggregation, "
+                         "configs[3], the zk config, reference parity and bench shapes, the CPU baseline and the "
+                         "profile-derived fields (the options below that switch these off apply under --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the proofs the last timed step returned (rank 0's batch) as "
+                         "DIR/*.npy: one float32 per proof byte, at most 64 MB in all (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=0,
                     help="proofs per GPU per step (default: 256 Wormhole, 1024 voting)")
     ap.add_argument("--provers", type=int, default=0,
@@ -205,7 +218,12 @@ def parse():
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="rehearse the --gpus N path on a one-GPU box: every rank proves on cuda:0, the process "
                          "group is gloo over host tensors (not RCCL); the line says rehearsal (not a measurement)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (ms_per_step and --dump-outputs need a timed step)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def launch_ranks(n, argv):
@@ -737,6 +755,35 @@ def configs3(args, circuit, prover, provers, cin, cin_inputs, per, NP, B, dist, 
                     "timed region"}
 
 
+DUMP_BYTES = 60 * 1000 * 1000  # under 64 MB whichever way a megabyte is counted
+
+
+def dump_outputs(out_dir, proofs):
+    """--dump-outputs: what the last timed step returned to its caller, the
+    serialized proofs of this rank's batch in input order (inputs are seeded, the
+    non-zk prover draws no randomness and the PoW witness is the smallest one,
+    so two runs with the same arguments give the same bytes).
+      proofs.npy         float32 [k][max proof bytes]: one value per byte (exact
+                         in float32), rows zero-padded to the longest proof
+      proof_index.npy    float64 [k]: the rows' positions in the batch; all of it
+                         when that fits in the budget, else a fixed sample
+                         (numpy default_rng(0), sorted)
+      proof_lengths.npy  float64 [batch]: every proof's length in bytes"""
+    os.makedirs(out_dir, exist_ok=True)
+    lengths = np.array([len(p) for p in proofs], np.float64)
+    width = int(lengths.max())
+    k = min(len(proofs), max(1, (DUMP_BYTES - 2 * 8 * len(proofs) - 3 * 128) // (4 * width)))
+    index = np.arange(len(proofs))
+    if k < len(proofs):
+        index = np.sort(np.random.default_rng(0).choice(len(proofs), k, replace=False))
+    rows = np.zeros((k, width), np.float32)
+    for r, i in enumerate(index):
+        rows[r, :len(proofs[i])] = np.frombuffer(proofs[i], np.uint8)
+    np.save(os.path.join(out_dir, "proofs.npy"), rows)
+    np.save(os.path.join(out_dir, "proof_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(out_dir, "proof_lengths.npy"), lengths)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -781,7 +828,7 @@ def main():
     cin = [prover.inputs_array(inputs[first[i]:first[i] + per[i]]) for i in range(NP)]
     # prove-only comparison path: wire matrices resident in HBM (host-generated)
     wires = pis = d_wires = None
-    if args.mode == "wires-dev" or rank == 0:
+    if args.mode == "wires-dev" or (args.full and rank == 0):
         wires, pis = make_witnesses(circuit, inputs[:max(per[0], 2)] if args.mode == "e2e" else inputs)
         d_wires = torch.from_numpy(wires.view(np.int64)).to(f"cuda:{local}")
     wstride = wires[0].nbytes if wires is not None else 0
@@ -808,7 +855,7 @@ def main():
     proofs = steps(args.warmup, False) if args.warmup else None
     # proofs of the warmup verify (rank 0 checks the first and last with the oracle verifier)
     verified = None
-    if rank == 0 and args.warmup:
+    if args.full and rank == 0 and args.warmup:
         from oracle_lib import lib as olib
         vd = prover.verifier_data()
         verified = all(olib().ora_verify(vd, len(vd), p, len(p)) == 0 for p in (proofs[0], proofs[-1]))
@@ -822,7 +869,7 @@ def main():
     trace_marker(torch)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    steps(args.steps, args.pipeline)
+    last = steps(args.steps, args.pipeline)
     torch.cuda.synchronize()
     trace_marker(torch)
     if dist is not None:
@@ -832,6 +879,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     # kernel statistics summed over the provers (HIP events on each prover's stream)
     ks = provers[0].kernel_stats()
     for p in provers[1:]:
@@ -841,20 +890,20 @@ def main():
     stages = prover.stage_times()
     # the same kernels alone on the GPU (one prover, one step, after the timed region)
     iso = None
-    if rank == 0 and NP > 1:
+    if args.full and rank == 0 and NP > 1:
         prover.kernel_stats(reset=True)
         prover.prove_inputs_array(cin[0], per[0])
         iso = prover.kernel_stats()
     # prove() alone from HBM-resident wires (round-1 headline definition), one prover
     prove_only = None
-    if rank == 0 and args.mode == "e2e":
+    if args.full and rank == 0 and args.mode == "e2e":
         prover.set_timing(False)
         t1 = time.perf_counter()
         prover.prove_wires_dev(d_wires.data_ptr(), pis[:per[0]], per[0])
         prove_only = per[0] / (time.perf_counter() - t1)
     # single-proof latency (BASELINE configs[1]): one proof through the same prover
     lat = None
-    if rank == 0:
+    if args.full and rank == 0:
         prover.set_timing(False)
         ts = []
         one = prover.inputs_array(inputs[:1])
@@ -868,7 +917,7 @@ def main():
     # `agg_leaves` leaves (agg_leaves/2 aggregation proofs, degree 2^13, batched) and a
     # default tree (8 leaves, branching 2, depth 3) end to end; after the timed region
     agg = None
-    if rank == 0 and not voting and args.agg_leaves and proofs is not None:
+    if args.full and rank == 0 and not voting and args.agg_leaves and proofs is not None:
         from qp_wormhole.aggregator import TreeAggregationConfig, aggregate_level, aggregate_to_tree
         from qp_wormhole.prover import _common_degree_bits
         from oracle_lib import lib as olib
@@ -905,13 +954,13 @@ def main():
     # BASELINE configs[3] as one measured pipeline (every rank, after the headline):
     # leaves -> per-GPU subtree root -> RCCL gather of the roots -> tree root on rank 0
     c3 = None
-    if not voting and args.configs3 and args.mode == "e2e":
+    if args.full and not voting and args.configs3 and args.mode == "e2e":
         c3 = configs3(args, circuit, prover, provers, cin, [inputs[first[i]:first[i] + per[i]] for i in range(NP)],
                       per, NP, B, dist, world, rank, local, torch, cdev)
     # standard_recursion_zk_config (the reference's cargo-bench and aggregator config):
     # under no_random it proves the same circuit without salts, one prover, one batch
     zk = None
-    if rank == 0 and not voting and args.mode == "e2e":
+    if args.full and rank == 0 and not voting and args.mode == "e2e":
         zc = qp_wormhole.Circuit.wormhole(zero_knowledge=True)
         zp = qp_wormhole.Prover(qp_wormhole.Context(local), zc, max_batch=per[0])
         zin = zp.inputs_array(inputs[:per[0]])
@@ -928,10 +977,10 @@ def main():
               "note": "standard_recursion_zk_config, e2e, one prover (the headline runs --provers, default 3)"}
         zp.free()
     ref_parity = None
-    if rank == 0 and not voting and args.mode == "e2e":
+    if args.full and rank == 0 and not voting and args.mode == "e2e":
         ref_parity = reference_parity(qp_wormhole, local)
     shapes = None
-    if rank == 0 and not voting and args.mode == "e2e" and args.ref_shapes:
+    if args.full and rank == 0 and not voting and args.mode == "e2e" and args.ref_shapes:
         tr = time.perf_counter()
         shapes = {"prover_create_proof": cargo_bench_shape(qp_wormhole, local)}
         tc = time.perf_counter()
@@ -942,9 +991,6 @@ def main():
                             "voting": time.perf_counter() - ta}
     if rank == 0:
         total = world * B * args.steps
-        lde = ks["lde_wires"]
-        achieved = lde["units"] / (lde["ms"] * 1e-3) / 1e9 if lde["ms"] else None
-        leaf = ks["leaf_hash_wires"]
         rec = {
             "metric": "Voting proofs/sec (whole node)" if voting else "Wormhole proofs/sec (whole node)",
             "value": total / dt,
@@ -971,100 +1017,110 @@ def main():
                        "batch_per_gpu": B, "provers_per_gpu": NP, "host_threads_per_prover": host_threads,
                        "step_schedule": "pipelined" if (args.pipeline and NP > 1) else "joined per step",
                        "parallelism": f"proofs sharded x{world}, RCCL gather of leaf proofs"},
-            "roofline": {"kernel": f"k_lde (wires LDE, 135 cols x 2^{circuit.degree_bits} -> "
-                                   f"2^{circuit.degree_bits + 3})", "bound": "hbm",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS if achieved else None,
-                         "traffic": pmc_traffic("qpk::k_lde_cosets<9>", circuit.num_wires, circuit.degree_bits,
-                                                per[0]) if circuit.degree_bits == 13 else None,
-                         "traffic_unit": "bytes per launch",
-                         "algorithmic_bytes_per_launch": lde["units"] / max(lde["launches"], 1),
-                         "traffic_source": f"{os.path.relpath(PMC_FILE, ROOT)} (rocprofv3 --pmc FETCH_SIZE, WRITE_SIZE "
-                                           "passes of this bench at batch 128), per proof x proofs per launch",
-                         "avg_launch_ms": lde["ms"] / max(lde["launches"], 1),
-                         "note": "HIP events on the prover stream around each launch of the kernel"},
-            "valu_kernels": {"leaf_hash_wires_perms_per_s": leaf["units"] / (leaf["ms"] * 1e-3) if leaf["ms"] else None,
-                             "avg_launch_ms": leaf["ms"] / max(leaf["launches"], 1),
-                             "quotient_avg_launch_ms": ks["quotient"]["ms"] / max(ks["quotient"]["launches"], 1),
-                             # k_quotient_1r: one lane per LDE point; algorithmic = 8 (241 reads + 2 writes) per point
-                             "quotient_hbm_bytes_per_launch": pmc_traffic(
-                                 "qpk::k_quotient_1r", 0, 0, per[0], lanes_per_proof=8 << circuit.degree_bits)
-                             if circuit.degree_bits == 13 else None,
-                             "quotient_algorithmic_bytes_per_launch": per[0] * 8 * 243 * (8 << circuit.degree_bits)},
             "stage_ms_per_step": {k: v / args.steps for k, v in stages.items()},
             "proof_bytes": prover.proof_size,
-            "latency_1proof_ms": lat,
-            "zk_config": zk,
-            "aggregation": agg,
-            "configs3": c3,
-            "prove_only_1prover_proofs_per_s": prove_only,
-            "warmup_proof_verified": verified,
-            "reference_proof_bytes_equal": ref_parity,
-            "reference_bench_shapes": shapes,
         }
-        if iso is not None and iso["lde_wires"]["ms"]:
-            # with concurrent provers a launch's event-to-event time includes the
-            # other prover's kernels; the kernel's own rate is the isolated pass
-            il = iso["lde_wires"]
-            ia = il["units"] / (il["ms"] * 1e-3) / 1e9
-            rl = rec["roofline"]
-            rl.update({"timed_region_achieved": rl["achieved"], "timed_region_avg_launch_ms": rl["avg_launch_ms"],
-                       "achieved": ia, "frac": ia / HBM_PEAK_GBS,
-                       "avg_launch_ms": il["ms"] / max(il["launches"], 1),
-                       "algorithmic_bytes_per_launch": il["units"] / max(il["launches"], 1),
-                       "note": f"achieved: the kernel alone (one prover, {per[0]} proofs per launch, HIP events on "
-                               f"its stream, right after the timed region); timed_region_*: the same events during "
-                               f"the timed region, where {NP} provers' kernels share the GPU"})
-            lh, qk = iso["leaf_hash_wires"], iso["quotient"]
-            if lh["ms"] and qk["ms"]:
-                rec["valu_kernels"].update({"leaf_hash_wires_perms_per_s": lh["units"] / (lh["ms"] * 1e-3),
-                                            "avg_launch_ms": lh["ms"] / max(lh["launches"], 1),
-                                            "quotient_avg_launch_ms": qk["ms"] / max(qk["launches"], 1),
-                                            "proofs_per_launch": per[0],
-                                            "note": "isolated pass, as roofline.achieved; HBM bytes: PMC file"})
-        vk = rec["valu_kernels"]
-        ipp = perm_valu_instr()
-        ksum, ksum1, ceil = load_json(KSUM_FILE), load_json(KSUM1_FILE), load_json(CEIL_FILE)
-        if vk.get("leaf_hash_wires_perms_per_s") and ipp:
-            ach = vk["leaf_hash_wires_perms_per_s"] / 64 * ipp
-            rr = register_replay()
-            rec["dominant_kernel"] = {
-                "kernel": "k_leaf_hash (Poseidon Merkle leaves)", "bound": "valu",
-                # one prover: kernels do not overlap, so shares are shares of GPU time
-                "share_of_kernel_time": ksum1["leaf_hash_share"] if ksum1 else None,
-                "achieved": ach, "peak": VALU_PEAK_WAVE_INSTR_S, "unit": "wave-instructions/s",
-                "frac": ach / VALU_PEAK_WAVE_INSTR_S, "instr_per_perm": ipp,
-                "mix_ceiling": mix_ceiling(ceil),
-                "mix_ceiling_priced_at": "the calibration streams' clock" if ceil else None,
-                "frac_of_mix_ceiling": ach / mix_ceiling(ceil) if ceil else None,
-                # clock-consistent: the kernel's VALU rate and its ceiling re-priced
-                # at its own clock, both from the same counter-pass dispatches
-                "frac_of_mix_ceiling_at_own_clock": ceil.get("frac_of_ceiling_in_counter_pass") if ceil else None,
-                "own_clock_ghz_in_counter_pass": ceil.get("leaf_hash_clock_ghz") if ceil else None,
-                # the additive class model underprices this mix (frac > 1 above):
-                # the loop replayed from registers is the ceiling that holds
-                "frac_of_register_replay": rr["frac"] if rr else None,
-                "register_replay": rr,
-                "frac_of_ceiling": rr["frac"] if rr else None,
-                "ceiling_kind": "the kernel's own instruction stream replayed from registers (tools/leaf_ubench L3 "
-                                "vs L0, same run); mix_ceiling* = an additive per-class estimate",
-                "sources": {"instr_per_perm": os.path.relpath(PMC_SQ_FILE, ROOT),
-                            "mix_ceiling": os.path.relpath(CEIL_FILE, ROOT) if ceil else None,
-                            "share": os.path.relpath(KSUM1_FILE, ROOT) if ksum1 else None,
-                            "perms_per_s": "this run (HIP events, isolated pass)"},
-                "note": "issue-bound 64-bit integer work (no MFMA path); peak = the guide's wave64 issue "
-                        "(1 VALU instruction / 2 cycles / SIMD), which v_mad_u64_u32 (59% of the kernel's "
-                        "VALU) does not reach: mix_ceiling = the kernel's instruction mix at the measured "
-                        "saturated rate of each instruction class"}
-        if ksum:
-            rec["gpu_busy_frac"] = {"value": ksum["gpu_busy_frac"], "source": os.path.relpath(KSUM_FILE, ROOT),
-                                    "scope": ksum.get("scope"),
-                                    "note": "union of kernel intervals / window, rocprofv3 kernel trace of this bench "
-                                            "(3 provers), cut to the timed steps by the trace markers"}
         rec["stage_ms_per_step"]["note"] = f"prover 0 ({per[0]} proofs), host + device"
-        segregate_profile_fields(rec)
-        if world == 1 and args.cpu_sample > 0:
-            rec["cpu_baseline"] = cpu_baseline(circuit, inputs, args.cpu_sample, args.cpu_seconds)
+        if args.full:
+            lde = ks["lde_wires"]
+            achieved = lde["units"] / (lde["ms"] * 1e-3) / 1e9 if lde["ms"] else None
+            leaf = ks["leaf_hash_wires"]
+            rec.update({
+                "roofline": {"kernel": f"k_lde (wires LDE, 135 cols x 2^{circuit.degree_bits} -> "
+                                       f"2^{circuit.degree_bits + 3})", "bound": "hbm",
+                             "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS if achieved else None,
+                             "traffic": pmc_traffic("qpk::k_lde_cosets<9>", circuit.num_wires, circuit.degree_bits,
+                                                    per[0]) if circuit.degree_bits == 13 else None,
+                             "traffic_unit": "bytes per launch",
+                             "algorithmic_bytes_per_launch": lde["units"] / max(lde["launches"], 1),
+                             "traffic_source": f"{os.path.relpath(PMC_FILE, ROOT)} (rocprofv3 --pmc FETCH_SIZE, "
+                                               "WRITE_SIZE passes of this bench at batch 128), per proof x proofs "
+                                               "per launch",
+                             "avg_launch_ms": lde["ms"] / max(lde["launches"], 1),
+                             "note": "HIP events on the prover stream around each launch of the kernel"},
+                "valu_kernels": {"leaf_hash_wires_perms_per_s": leaf["units"] / (leaf["ms"] * 1e-3)
+                                 if leaf["ms"] else None,
+                                 "avg_launch_ms": leaf["ms"] / max(leaf["launches"], 1),
+                                 "quotient_avg_launch_ms": ks["quotient"]["ms"] / max(ks["quotient"]["launches"], 1),
+                                 # k_quotient_1r: one lane per LDE point; algorithmic = 8 (241 reads + 2 writes)
+                                 # per point
+                                 "quotient_hbm_bytes_per_launch": pmc_traffic(
+                                     "qpk::k_quotient_1r", 0, 0, per[0], lanes_per_proof=8 << circuit.degree_bits)
+                                 if circuit.degree_bits == 13 else None,
+                                 "quotient_algorithmic_bytes_per_launch":
+                                     per[0] * 8 * 243 * (8 << circuit.degree_bits)},
+                "latency_1proof_ms": lat,
+                "zk_config": zk,
+                "aggregation": agg,
+                "configs3": c3,
+                "prove_only_1prover_proofs_per_s": prove_only,
+                "warmup_proof_verified": verified,
+                "reference_proof_bytes_equal": ref_parity,
+                "reference_bench_shapes": shapes,
+            })
+            if iso is not None and iso["lde_wires"]["ms"]:
+                # with concurrent provers a launch's event-to-event time includes the
+                # other prover's kernels; the kernel's own rate is the isolated pass
+                il = iso["lde_wires"]
+                ia = il["units"] / (il["ms"] * 1e-3) / 1e9
+                rl = rec["roofline"]
+                rl.update({"timed_region_achieved": rl["achieved"], "timed_region_avg_launch_ms": rl["avg_launch_ms"],
+                           "achieved": ia, "frac": ia / HBM_PEAK_GBS,
+                           "avg_launch_ms": il["ms"] / max(il["launches"], 1),
+                           "algorithmic_bytes_per_launch": il["units"] / max(il["launches"], 1),
+                           "note": f"achieved: the kernel alone (one prover, {per[0]} proofs per launch, HIP events on "
+                                   f"its stream, right after the timed region); timed_region_*: the same events during "
+                                   f"the timed region, where {NP} provers' kernels share the GPU"})
+                lh, qk = iso["leaf_hash_wires"], iso["quotient"]
+                if lh["ms"] and qk["ms"]:
+                    rec["valu_kernels"].update({"leaf_hash_wires_perms_per_s": lh["units"] / (lh["ms"] * 1e-3),
+                                                "avg_launch_ms": lh["ms"] / max(lh["launches"], 1),
+                                                "quotient_avg_launch_ms": qk["ms"] / max(qk["launches"], 1),
+                                                "proofs_per_launch": per[0],
+                                                "note": "isolated pass, as roofline.achieved; HBM bytes: PMC file"})
+            vk = rec["valu_kernels"]
+            ipp = perm_valu_instr()
+            ksum, ksum1, ceil = load_json(KSUM_FILE), load_json(KSUM1_FILE), load_json(CEIL_FILE)
+            if vk.get("leaf_hash_wires_perms_per_s") and ipp:
+                ach = vk["leaf_hash_wires_perms_per_s"] / 64 * ipp
+                rr = register_replay()
+                rec["dominant_kernel"] = {
+                    "kernel": "k_leaf_hash (Poseidon Merkle leaves)", "bound": "valu",
+                    # one prover: kernels do not overlap, so shares are shares of GPU time
+                    "share_of_kernel_time": ksum1["leaf_hash_share"] if ksum1 else None,
+                    "achieved": ach, "peak": VALU_PEAK_WAVE_INSTR_S, "unit": "wave-instructions/s",
+                    "frac": ach / VALU_PEAK_WAVE_INSTR_S, "instr_per_perm": ipp,
+                    "mix_ceiling": mix_ceiling(ceil),
+                    "mix_ceiling_priced_at": "the calibration streams' clock" if ceil else None,
+                    "frac_of_mix_ceiling": ach / mix_ceiling(ceil) if ceil else None,
+                    # clock-consistent: the kernel's VALU rate and its ceiling re-priced
+                    # at its own clock, both from the same counter-pass dispatches
+                    "frac_of_mix_ceiling_at_own_clock": ceil.get("frac_of_ceiling_in_counter_pass") if ceil else None,
+                    "own_clock_ghz_in_counter_pass": ceil.get("leaf_hash_clock_ghz") if ceil else None,
+                    # the additive class model underprices this mix (frac > 1 above):
+                    # the loop replayed from registers is the ceiling that holds
+                    "frac_of_register_replay": rr["frac"] if rr else None,
+                    "register_replay": rr,
+                    "frac_of_ceiling": rr["frac"] if rr else None,
+                    "ceiling_kind": "the kernel's own instruction stream replayed from registers (tools/leaf_ubench L3 "
+                                    "vs L0, same run); mix_ceiling* = an additive per-class estimate",
+                    "sources": {"instr_per_perm": os.path.relpath(PMC_SQ_FILE, ROOT),
+                                "mix_ceiling": os.path.relpath(CEIL_FILE, ROOT) if ceil else None,
+                                "share": os.path.relpath(KSUM1_FILE, ROOT) if ksum1 else None,
+                                "perms_per_s": "this run (HIP events, isolated pass)"},
+                    "note": "issue-bound 64-bit integer work (no MFMA path); peak = CDNA4's wave64 issue "
+                            "(1 VALU instruction / 2 cycles / SIMD), which v_mad_u64_u32 (59% of the kernel's "
+                            "VALU) does not reach: mix_ceiling = the kernel's instruction mix at the measured "
+                            "saturated rate of each instruction class"}
+            if ksum:
+                rec["gpu_busy_frac"] = {"value": ksum["gpu_busy_frac"], "source": os.path.relpath(KSUM_FILE, ROOT),
+                                        "scope": ksum.get("scope"),
+                                        "note": "union of kernel intervals / window, rocprofv3 kernel trace of this "
+                                                "bench (3 provers), cut to the timed steps by the trace markers"}
+            segregate_profile_fields(rec)
+            if world == 1 and args.cpu_sample > 0:
+                rec["cpu_baseline"] = cpu_baseline(circuit, inputs, args.cpu_sample, args.cpu_seconds)
         print(json.dumps(rec), flush=True)
     for p in provers:
         p.free()

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_share_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-shared-gpu",
-                        "--batch", "8", "--provers", "2", "--steps", "1", "--warmup", "1", "--configs3-steps", "1",
+                        "--full", "--batch", "8", "--provers", "2", "--steps", "1", "--warmup", "1", "--configs3-steps", "1",
                         "--cpu-sample", "0", "--ref-shapes", "0"],
                        capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
