@@ -415,6 +415,64 @@ int qp_fri_fold(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs, uint32
 int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint32_t n, uint32_t pow_bits,
                  uint64_t *witness_out);
 
+/* ---- batch proof verifier (plonky2 VerifierCircuitData::verify; the
+ * reference's qp-wormhole-verifier, wormhole/verifier/src/lib.rs) ----------
+ * Per proof the host parses, replays the transcript and checks the vanishing
+ * identity and the PoW; the query rounds of the whole batch (Merkle paths, FRI
+ * folding) run as two gfx950 kernels on the context's stream.              */
+typedef struct qp_verifier qp_verifier;
+
+/* verdict of one proof: plonky2's verify / verify_fri_proof checks in their order */
+typedef enum {
+    QP_VERIFY_OK = 0,
+    QP_VERIFY_PUBLIC_INPUT_COUNT = 1,
+    QP_VERIFY_ZETA_IN_SUBGROUP = 2,
+    QP_VERIFY_VANISHING_IDENTITY = 3,
+    QP_VERIFY_POW = 4,
+    QP_VERIFY_INITIAL_MERKLE_PATH = 5,
+    QP_VERIFY_FRI_CONSISTENCY = 6,
+    QP_VERIFY_FRI_MERKLE_PATH = 7,
+    QP_VERIFY_FINAL_POLY = 8,
+    QP_VERIFY_MALFORMED = 9 /* wrong length, wrong sibling count, field element >= p */
+} qp_verify_status;
+
+/* plonky2 VerifierCircuitData: verifier_only = VerifierOnlyCircuitData bytes (cap height,
+ * constants||sigmas cap, circuit digest), common = CommonCircuitData bytes.
+ * ctx == NULL: everything runs on the host (no device needed).
+ * Supported circuits: the gate set of this library's circuits (the six leaf
+ * gates and the seven recursive-verifier gates), two challenges, no lookup
+ * tables, salted (hiding) or not; anything else returns QP_ERR_FORMAT (with
+ * *out set to a handle that only carries the reason for
+ * qp_verifier_last_error; free it as usual).                               */
+int qp_verifier_new(qp_ctx *ctx, const uint8_t *verifier_only, size_t vlen,
+                    const uint8_t *common, size_t clen, uint32_t max_batch, qp_verifier **out);
+void qp_verifier_free(qp_verifier *v);
+const char *qp_verifier_last_error(const qp_verifier *v);
+/* VerifierCircuitData::verify for n serialized ProofWithPublicInputs; status_out[i] is a
+ * qp_verify_status. Returns QP_OK whenever the call itself completed, whatever the verdicts.
+ * Where several checks fail the verdict is the first in plonky2's sequential
+ * order (checks 1-4, then the lowest failing query; within it the four initial
+ * trees, per layer consistency before the layer's path, the final polynomial).
+ * n > max_batch is processed in chunks; a verdict never depends on the
+ * neighbouring proofs.  Not thread-safe per handle.                         */
+int qp_verifier_verify(qp_verifier *v, const uint8_t *const *proofs, const size_t *lens,
+                       uint32_t n, uint32_t *status_out);
+/* host threads of the per-proof work, the calling thread included (default:
+ * the machine's, at most 16)                                               */
+int qp_verifier_set_host_threads(qp_verifier *v, uint32_t nthreads);
+/* verify_merkle_proof_to_cap for n independent (leaf, index, siblings) triples against one cap:
+ * leaves [n][width], idx [n], siblings [n][nsib][4], cap [2^cap_height][4]; ok_out[i] = 0/1.
+ * Routine-level seam; also the small-shape test surface of the path kernel.
+ * An index past the tree (idx >> nsib >= 2^cap_height) gives 0.  Shapes:
+ * width >= 1, nsib <= 32, cap_height <= 20, nsib + cap_height <= 32.  Unlike
+ * the handle-based seams above it keeps nothing between calls: every call
+ * allocates and frees its device buffers and copies from the caller's
+ * (pageable) memory, so it is for checks and tests, not for a hot loop;
+ * qp_verifier_verify keeps its buffers.                                     */
+int qp_merkle_verify(qp_ctx *ctx, const uint64_t *leaves, uint32_t width, const uint32_t *idx,
+                     const uint64_t *siblings, uint32_t nsib, const uint64_t *cap,
+                     uint32_t cap_height, uint32_t n, uint8_t *ok_out);
+
 #ifdef __cplusplus
 }
 #endif

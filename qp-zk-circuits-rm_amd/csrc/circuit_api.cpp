@@ -194,6 +194,7 @@ int qp_aggregation_circuit_new(const uint8_t *inner_common, size_t len, uint32_t
   try {
     qr::InnerCommon ic;
     if (!qr::parse_common(inner_common, len, ic).empty()) return QP_ERR_ARG;
+    if (ic.hiding) return QP_ERR_ARG;  // salted leaves: the recursive verifier does not open them
     qc::CircuitConfig cfg = ic.zero_knowledge ? qc::CircuitConfig::standard_recursion_zk_config()
                                               : qc::CircuitConfig::standard_recursion_config();
     if (ic.num_wires != cfg.num_wires || ic.num_routed_wires != cfg.num_routed_wires ||

@@ -12,6 +12,7 @@
 #include <stdexcept>
 #include <string.h>
 #include "field.h"
+#include "gate_constraints.h"
 #include "poseidon.h"
 
 namespace qr {
@@ -150,7 +151,7 @@ std::string parse_common(const uint8_t *b, size_t n, InnerCommon &c) {
     c.gates.push_back(g);
   }
   if (r.err || r.pos != n) return "malformed CommonCircuitData bytes";
-  if (c.num_challenges != 2 || c.hiding) return "unsupported inner config";
+  if (c.num_challenges != 2) return "unsupported inner config";
   if (c.selector_indices.size() != c.gates.size() || c.k_is.size() != c.num_routed_wires)
     return "inconsistent CommonCircuitData";
   for (auto &g : c.gates) {
@@ -184,7 +185,10 @@ size_t proof_bytes(const InnerCommon &c, uint32_t npis) {
 
 namespace {
 
-struct G {
+// circuit targets as gate_constraints.h's arithmetic (ExtensionAlgebraTarget<2>
+// pairs: a + b Y, Y^2 = 7)
+struct G : AlgOps<G, ExtT> {
+  using E = ExtT;
   CircuitBuilder &b;
   explicit G(CircuitBuilder &bb) : b(bb) {}
 
@@ -227,29 +231,14 @@ struct G {
     for (uint32_t i = 0; i < k; i++) x = b.mul(x, x);
     return x;
   }
-  // ExtensionAlgebraTarget<2> (the recursion gates' values at zeta: pairs of
-  // extension targets a + b Y, Y^2 = 7; gadgets/arithmetic_extension.rs)
-  struct Alg {
-    ExtT a, b;
-  };
-  Alg alg(const std::vector<ExtT> &w, uint32_t i) { return {w[i], w[i + 1]}; }
-  Alg alg_zero() { return {ext_zero(), ext_zero()}; }
-  Alg alg_sub(Alg x, Alg y) { return {sub(x.a, y.a), sub(x.b, y.b)}; }
-  // mul_add_ext_algebra: the W-weighted inner product first, then the plain one
-  Alg alg_mul_add(Alg x, Alg y, Alg z) {
-    ExtT r0 = b.arithmetic_extension(gl::EXT_W, 1, x.b, y.b, z.a);
-    r0 = b.mul_add_ext(x.a, y.a, r0);
-    ExtT r1 = b.mul_add_ext(x.a, y.b, z.b);
-    r1 = b.mul_add_ext(x.b, y.a, r1);
-    return {r0, r1};
+  // the operations gate_constraints.h needs beyond the ones above
+  ExtT arithmetic_extension(F c0, F c1, ExtT m0, ExtT m1, ExtT addend) {
+    return b.arithmetic_extension(c0, c1, m0, m1, addend);
   }
-  Alg alg_mul(Alg x, Alg y) { return alg_mul_add(x, y, alg_zero()); }
-  Alg alg_scalar_mul_add(ExtT c, Alg x, Alg z) { return {mul_add(c, x.a, z.a), mul_add(c, x.b, z.b)}; }
-  Alg alg_scalar_mul(ExtT c, Alg x) { return alg_scalar_mul_add(c, x, alg_zero()); }
-  void push(std::vector<ExtT> &out, Alg x) {
-    out.push_back(x.a);
-    out.push_back(x.b);
-  }
+  ExtT reduce(ExtT base, const std::vector<ExtT> &t) { return b.reduce_ext(base, t); }
+  ExtT mul_const_add(F c, ExtT x, ExtT y) { return b.mul_const_add_ext(c, x, y); }
+  std::vector<ExtT> poseidon_mds(const std::vector<ExtT> &s) { return b.poseidon_mds(s); }
+  ExtT exp_u64(ExtT x, uint64_t e) { return b.exp_u64_ext(x, e); }
 };
 
 // RecursiveChallenger (iop/challenger.rs)
@@ -293,184 +282,6 @@ struct Chal {
     return {a, c};
   }
 };
-
-// MDS layer on ext states: one PoseidonMdsGate row (mds_layer_circuit with
-// num_routed_wires >= 48)
-void mds_ext(G &g, ExtT s[12]) {
-  std::vector<ExtT> v(s, s + 12);
-  v = g.b.poseidon_mds(v);
-  for (int r = 0; r < 12; r++) s[r] = v[r];
-}
-
-// sbox_monomial_circuit: exp_u64_extension(x, 7)
-ExtT sbox_ext(G &g, ExtT x) { return g.b.exp_u64_ext(x, 7); }
-
-// gates/*::eval_unfiltered_circuit (values at zeta), in upstream plonky2's
-// operation forms (values pinned by SURVEY.md A.5 for the leaf gates; the
-// recursion gates' formulas restate upstream, parity unpinned)
-std::vector<ExtT> gate_constraints(G &g, const InnerCommon::Gate &gate, const std::vector<ExtT> &w,
-                                   const ExtT *gc, const std::vector<Target> &pi_hash) {
-  std::vector<ExtT> out;
-  CircuitBuilder &b = g.b;
-  switch (gate.id) {
-    case 9:  // Noop
-      break;
-    case 3:  // Constant
-      for (uint32_t i = 0; i < gate.p[0]; i++) out.push_back(g.sub(gc[i], w[i]));
-      break;
-    case 12:  // PublicInput
-      for (uint32_t i = 0; i < 4; i++) out.push_back(g.sub(w[i], g.ext(pi_hash[i])));
-      break;
-    case 2: {  // BaseSum<2>: the recomposed sum, then limb (limb - 1) per limb
-      const uint32_t L = (uint32_t)gate.p[0];
-      std::vector<ExtT> limbs(w.begin() + 1, w.begin() + 1 + L);
-      out.push_back(g.sub(b.reduce_ext(g.ext_const(2), limbs), w[0]));
-      for (ExtT l : limbs) out.push_back(g.mul_sub(l, l, l));
-      break;
-    }
-    case 0: {  // Arithmetic: out - (c0 m0 m1 + c1 addend)
-      for (uint32_t i = 0; i < gate.p[0]; i++) {
-        ExtT scaled = g.mul_many({gc[0], w[4 * i], w[4 * i + 1]});
-        ExtT comp = g.mul_add(gc[1], w[4 * i + 2], scaled);
-        out.push_back(g.sub(w[4 * i + 3], comp));
-      }
-      break;
-    }
-    case 1:    // ArithmeticExtension{num_ops}: out - (c0 m0 m1 + c1 addend), algebra
-    case 8: {  // MulExtension{num_ops}: out - c0 m0 m1
-      const bool ae = gate.id == 1;
-      for (uint32_t i = 0; i < gate.p[0]; i++) {
-        const uint32_t o = ae ? 8 * i : 6 * i;
-        G::Alg scaled = g.alg_scalar_mul(gc[0], g.alg_mul(g.alg(w, o), g.alg(w, o + 2)));
-        if (ae) scaled = g.alg_scalar_mul_add(gc[1], g.alg(w, o + 4), scaled);
-        g.push(out, g.alg_sub(g.alg(w, ae ? o + 6 : o + 4), scaled));
-      }
-      break;
-    }
-    case 15:    // Reducing{num_coeffs}: acc_i - (acc_{i-1} alpha + coeff_i), base coefficients
-    case 14: {  // ReducingExtension{num_coeffs}: ext coefficients
-      const uint32_t nc = (uint32_t)gate.p[0], cw = gate.id == 15 ? 1 : 2;
-      const G::Alg alpha = g.alg(w, 2);
-      G::Alg acc = g.alg(w, 4);
-      for (uint32_t i = 0; i < nc; i++) {
-        const G::Alg coeff = cw == 1 ? G::Alg{w[6 + i], g.ext_zero()} : g.alg(w, 6 + 2 * i);
-        const G::Alg next = g.alg(w, i + 1 == nc ? 0 : 6 + cw * nc + 2 * i);
-        g.push(out, g.alg_sub(g.alg_mul_add(acc, alpha, coeff), next));
-        acc = next;
-      }
-      break;
-    }
-    case 10: {  // PoseidonMds: out_r - (sum_i CIRC[i] in_{i+r} + DIAG[r] in_r), algebra
-      for (uint32_t r = 0; r < 12; r++) {
-        G::Alg res = g.alg_zero();
-        for (uint32_t i = 0; i < 12; i++)
-          res = g.alg_scalar_mul_add(g.ext_const(ps::mds_circ(i)), g.alg(w, 2 * ((i + r) % 12)), res);
-        res = g.alg_scalar_mul_add(g.ext_const(r == 0 ? 8 : 0), g.alg(w, 2 * r), res);
-        g.push(out, g.alg_sub(g.alg(w, 24 + 2 * r), res));
-      }
-      break;
-    }
-    case 4: {  // CosetInterpolation{subgroup_bits, degree}
-      const uint32_t nbits = (uint32_t)gate.p[0], deg = (uint32_t)gate.p[1], np = 1u << nbits;
-      const uint32_t nint = (np - 2) / (deg - 1);
-      const uint32_t sv = 1, sep = sv + 2 * np, sev = sep + 2, si = sev + 2, ssh = si + 4 * nint;
-      const ExtT shift = w[0];
-      const G::Alg ep = g.alg(w, sep), sp = g.alg(w, ssh);
-      g.push(out, g.alg_scalar_mul_add(g.scale(shift, gl::P - 1), sp, ep));
-      const F om = gl::root_of_unity(nbits), ninv = gl::inv(np);
-      G::Alg ev = g.alg_zero(), pr{g.ext_const(1), g.ext_zero()};
-      uint32_t lo = 0, hi = deg;
-      for (uint32_t it = 0;; it++) {
-        for (uint32_t i = lo; i < hi; i++) {
-          const F x = gl::pow(om, i);
-          const G::Alg term{g.sub(sp.a, g.ext_const(x)), sp.b};
-          const G::Alg wv = g.alg_scalar_mul(g.ext_const(gl::mul(x, ninv)), g.alg(w, sv + 2 * i));
-          ev = g.alg_mul_add(wv, pr, g.alg_mul(ev, term));
-          pr = g.alg_mul(pr, term);
-        }
-        if (it == nint) break;
-        const G::Alg ie = g.alg(w, si + 2 * it), ip = g.alg(w, si + 2 * (nint + it));
-        g.push(out, g.alg_sub(ie, ev));
-        g.push(out, g.alg_sub(ip, pr));
-        ev = ie;
-        pr = ip;
-        lo = 1 + (deg - 1) * (it + 1);
-        hi = std::min(lo + deg - 1, np);
-      }
-      g.push(out, g.alg_sub(g.alg(w, sev), ev));
-      break;
-    }
-    case 13: {  // RandomAccess{bits, copies, extra}
-      const uint32_t bits = (uint32_t)gate.p[0], copies = (uint32_t)gate.p[1], extra = (uint32_t)gate.p[2];
-      const uint32_t vec = 1u << bits, routed = (2 + vec) * copies + extra;
-      for (uint32_t cp = 0; cp < copies; cp++) {
-        const uint32_t base = (2 + vec) * cp;
-        std::vector<ExtT> bw(bits);
-        for (uint32_t i = 0; i < bits; i++) bw[i] = w[routed + cp * bits + i];
-        for (uint32_t i = 0; i < bits; i++) out.push_back(g.mul_sub(bw[i], bw[i], bw[i]));
-        ExtT idx = g.ext_zero();
-        for (uint32_t i = bits; i-- > 0;) idx = b.mul_const_add_ext(2, idx, bw[i]);
-        out.push_back(g.sub(idx, w[base]));
-        std::vector<ExtT> list(w.begin() + base + 2, w.begin() + base + 2 + vec);
-        for (uint32_t i = 0; i < bits; i++) {
-          std::vector<ExtT> nx(list.size() / 2);
-          // select_ext_generalized(b, y, x) = b y - (b x - x)
-          for (size_t j = 0; j < nx.size(); j++)
-            nx[j] = g.mul_sub(bw[i], list[2 * j + 1], g.mul_sub(bw[i], list[2 * j], list[2 * j]));
-          list = nx;
-        }
-        out.push_back(g.sub(list[0], w[base + 1]));
-      }
-      for (uint32_t i = 0; i < extra; i++) out.push_back(g.sub(gc[i], w[(2 + vec) * copies + i]));
-      break;
-    }
-    case 11: {  // Poseidon: constant layers, x^7 S-boxes, PoseidonMdsGate layers, wire checks
-      ExtT swap = w[24];
-      out.push_back(g.mul_sub(swap, swap, swap));
-      for (int i = 0; i < 4; i++) out.push_back(g.mul_sub(swap, g.sub(w[i + 4], w[i]), w[25 + i]));
-      ExtT s[12];
-      for (int i = 0; i < 4; i++) {
-        ExtT delta = w[25 + i];
-        s[i] = g.add(w[i], delta);
-        s[i + 4] = g.sub(w[i + 4], delta);
-      }
-      for (int i = 8; i < 12; i++) s[i] = w[i];
-      int rc = 0;
-      for (int r = 0; r < 4; r++, rc++) {
-        for (int i = 0; i < 12; i++) s[i] = g.add_const(s[i], ps::RC_HOST[rc * 12 + i]);
-        if (r)
-          for (int i = 0; i < 12; i++) {
-            ExtT wi = w[29 + (r - 1) * 12 + i];
-            out.push_back(g.sub(s[i], wi));
-            s[i] = wi;
-          }
-        for (int i = 0; i < 12; i++) s[i] = sbox_ext(g, s[i]);
-        mds_ext(g, s);
-      }
-      for (int r = 0; r < 22; r++, rc++) {
-        for (int i = 0; i < 12; i++) s[i] = g.add_const(s[i], ps::RC_HOST[rc * 12 + i]);
-        ExtT wi = w[65 + r];
-        out.push_back(g.sub(s[0], wi));
-        s[0] = sbox_ext(g, wi);
-        mds_ext(g, s);
-      }
-      for (int r = 0; r < 4; r++, rc++) {
-        for (int i = 0; i < 12; i++) s[i] = g.add_const(s[i], ps::RC_HOST[rc * 12 + i]);
-        for (int i = 0; i < 12; i++) {
-          ExtT wi = w[87 + r * 12 + i];
-          out.push_back(g.sub(s[i], wi));
-          s[i] = sbox_ext(g, wi);
-        }
-        mds_ext(g, s);
-      }
-      for (int i = 0; i < 12; i++) out.push_back(g.sub(s[i], w[12 + i]));
-      break;
-    }
-    default:
-      throw std::runtime_error("unsupported inner gate");
-  }
-  return out;
-}
 
 std::vector<Target> virt(CircuitBuilder &b, size_t n) {
   auto v = b.add_virtual_targets(n);

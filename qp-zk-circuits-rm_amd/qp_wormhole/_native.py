@@ -15,6 +15,7 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "qpgpu.
 
 U64P = np.ctypeslib.ndpointer(np.uint64, flags="C_CONTIGUOUS")
 U32P = np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS")
+U8P = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 VP = ctypes.c_void_p
 PP = ctypes.POINTER(ctypes.c_void_p)
 
@@ -159,6 +160,15 @@ def lib():
         "qp_fri_layer_free": (None, [VP]),
         "qp_fri_fold": (ctypes.c_int, [VP, U64P, ctypes.c_uint32, ctypes.c_uint32, U64P, U64P]),
         "qp_pow_grind": (ctypes.c_int, [VP, U64P, U32P, ctypes.c_uint32, ctypes.c_uint32, U64P]),
+        "qp_verifier_new": (ctypes.c_int, [VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                           ctypes.c_uint32, PP]),
+        "qp_verifier_free": (None, [VP]),
+        "qp_verifier_last_error": (ctypes.c_char_p, [VP]),
+        "qp_verifier_verify": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t),
+                                              ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+        "qp_verifier_set_host_threads": (ctypes.c_int, [VP, ctypes.c_uint32]),
+        "qp_merkle_verify": (ctypes.c_int, [VP, U64P, ctypes.c_uint32, U32P, U64P, ctypes.c_uint32, U64P,
+                                            ctypes.c_uint32, ctypes.c_uint32, U8P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
