@@ -311,6 +311,47 @@ int qp_prover_debug_force_pow(qp_prover *p, uint64_t witness, int enable);
  * QP_ERR_STATE naming it instead of faulting (every prove entry point checks
  * the tables its kernels read before launching them).                      */
 int qp_prover_debug_drop_table(qp_prover *p, const char *name);
+/* TEST-ONLY: the device field arithmetic, one function at a time
+ * (csrc/field_probe.hip).  Lane i applies `op` to a[i], b[i] and stores the
+ * RAW result (no canonicalisation) to out[i]; the kernel calls the functions
+ * the production kernels call (ntt16.h nt::, field_nc.h gfn::,
+ * poseidon_fast.h pf::, field.h gl::).  The operands must respect the
+ * function's own contract (noted per op); the probe does not check them.
+ * The 4-wide and K-wide forms take a group of consecutive elements per lane
+ * (n a multiple of the group size) and store the group's results in place,
+ * QP_FOP_ACC3 one word per group (out holds n / param words).  b may be NULL
+ * for the unary ops.  Unknown op, unknown param (nonzero where none is taken)
+ * or n not a multiple of the group size: QP_ERR_ARG.                        */
+enum {
+    QP_FOP_NT_ADD = 0,        /* nt::add (add_mad): a + b, any u64                         */
+    QP_FOP_NT_ADD4,           /* nt::add4: groups of 4                                     */
+    QP_FOP_GFN_ADD,           /* gfn::add                                                  */
+    QP_FOP_GFN_ADD_C,         /* gfn::add_c: b < p                                         */
+    QP_FOP_PF_ADD_C,          /* pf::add_c: b < p                                          */
+    QP_FOP_GL_ADD,            /* gl::add: a, b < p; result < p                             */
+    QP_FOP_NT_SUB,            /* nt::sub = gfn::sub: a - b, any u64                        */
+    QP_FOP_NT_SUB4,           /* nt::sub4: groups of 4                                     */
+    QP_FOP_GL_SUB,            /* gl::sub: a, b < p; result < p                             */
+    QP_FOP_NT_REDUCE,         /* nt::reduce(lo = a, hi = b)                                */
+    QP_FOP_GFN_REDUCE,        /* gfn::reduce(lo = a, hi = b)                               */
+    QP_FOP_GL_REDUCE128,      /* gl::reduce128(lo = a, hi = b); result < p                 */
+    QP_FOP_PF_REDUCE_ROW,     /* pf::reduce_row(al = a, ah = b): a, b < 2^42               */
+    QP_FOP_PF_REDUCE_ROW_C,   /* pf::reduce_row_c, same operands                           */
+    QP_FOP_PF_SUB_SMALL,      /* pf::sub_small(r = a, y = b): b < 2^40                     */
+    QP_FOP_PF_MUL,            /* pf::mul                                                   */
+    QP_FOP_PF_MUL_C,          /* pf::mul_c                                                 */
+    QP_FOP_PF_MULK2,          /* pf::mulk<2>: groups of 2                                  */
+    QP_FOP_PF_MULK3,          /* pf::mulk<3>: groups of 3                                  */
+    QP_FOP_GL_MUL,            /* gl::mul (device mul_wide); result < p                     */
+    QP_FOP_PF_SBOX,           /* pf::sbox(a) = a^7                                         */
+    QP_FOP_PF_SBOX_C,         /* pf::sbox_c(a)                                             */
+    QP_FOP_NT_MUL_POW2,       /* nt::mul_pow2<param>(a): param a multiple of 6 below 192   */
+    QP_FOP_ACC3,              /* gfn::Acc3, groups of param (1..256) elements: mac(a[k],
+                               * b[k]) for each, add_shifted(a[0], param % 64), value()   */
+    QP_FOP_COUNT
+};
+int qp_debug_field_op(qp_ctx *ctx, uint32_t op, uint32_t param, const uint64_t *a, const uint64_t *b, uint64_t n,
+                      uint64_t *out);
 /* host threads (the caller included) of the prover's pool for commit() and the
  * per-proof host stages; default min(hardware threads, 16).  Several provers in
  * one process should split the host cores (cores / provers each).           */

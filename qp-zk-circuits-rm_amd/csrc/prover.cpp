@@ -135,11 +135,19 @@ namespace qpk {
 void perm_challenges(uint64_t *ch, const uint64_t *beta, const uint64_t *gamma, uint32_t nc, uint32_t R, uint32_t qdf) {
   const uint32_t last = R % qdf ? R % qdf : qdf;
   for (uint32_t c = 0; c < nc && c < 2; c++) {
+    if (beta[c] == 0) {  // no inverse: w + gamma + 0 s, unscaled (CH_S_MASK)
+      ch[CH_BETA_INV + c] = 1;
+      ch[CH_GAMMA_B + c] = gamma[c];
+      ch[CH_BETA_QDF + c] = ch[CH_BETA_LAST + c] = 1;
+      ch[CH_S_MASK + c] = 0;
+      continue;
+    }
     const uint64_t bi = gl::inv(beta[c]);
     ch[CH_BETA_INV + c] = bi;
     ch[CH_GAMMA_B + c] = gl::mul(gamma[c], bi);
     ch[CH_BETA_QDF + c] = gl::pow(beta[c], qdf);
     ch[CH_BETA_LAST + c] = gl::pow(beta[c], last);
+    ch[CH_S_MASK + c] = ~0ull;
   }
 }
 

@@ -19,8 +19,10 @@ enum : uint32_t {
   CH_ZETA_NEXT_INV = 16, CH_FRI_ALPHA = 18, CH_ALPHA_POW_NC = 20, CH_FRI_BETA = 22,
   // the permutation argument scaled by 1 / beta (k_quotient_1r): (w + gamma +
   // beta s) = beta (w / beta + gamma / beta + s), the beta^len of a chunk's
-  // products applied once per chunk (len = qdf, or the last chunk's R mod qdf)
-  CH_BETA_INV = 32, CH_GAMMA_B = 34, CH_BETA_QDF = 36, CH_BETA_LAST = 38, CHAL_STRIDE = 40
+  // products applied once per chunk (len = qdf, or the last chunk's R mod qdf).
+  // beta = 0 has no inverse: then the words hold 1, gamma, 1, 1 and CH_S_MASK
+  // (all ones otherwise) is 0, which clears the s term: the factor is w + gamma
+  CH_BETA_INV = 32, CH_GAMMA_B = 34, CH_BETA_QDF = 36, CH_BETA_LAST = 38, CH_S_MASK = 40, CHAL_STRIDE = 42
 };
 constexpr uint32_t MAX_FRI_LAYERS = (CH_BETA_INV - CH_FRI_BETA) / 2;
 // the permutation-argument words of the challenge block for challenges beta, gamma

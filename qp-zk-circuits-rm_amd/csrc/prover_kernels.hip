@@ -651,6 +651,7 @@ k_quotient_1r(QuotientArgs a) {
   // and the sigma values need no product (7 products per wire, not 8)
   const uint64_t binv0 = ch[CH_BETA_INV], binv1 = ch[CH_BETA_INV + 1];
   const uint64_t gamb0 = ch[CH_GAMMA_B], gamb1 = ch[CH_GAMMA_B + 1];
+  const uint64_t sm0 = ch[CH_S_MASK], sm1 = ch[CH_S_MASK + 1];  // 0 for a zero beta (no s term), else all ones
   uint64_t kx = x;  // k_j x, k_j = g^j
   uint64_t num0 = 1, den0 = 1, num1 = 1, den1 = 1;
   // per-gate alpha sums (multiplied by the gate's filter at the end)
@@ -696,8 +697,8 @@ k_quotient_1r(QuotientArgs a) {
       uint64_t wb0, wb1;
       mul2(w, binv0, w, binv1, wb0, wb1);
       const uint64_t wg0 = gfn::add_c(wb0, gamb0), wg1 = gfn::add_c(wb1, gamb1);
-      mul2(num0, gfn::add(wg0, kx), den0, gfn::add(wg0, sg), num0, den0);
-      mul2(num1, gfn::add(wg1, kx), den1, gfn::add(wg1, sg), num1, den1);
+      mul2(num0, gfn::add(wg0, kx & sm0), den0, gfn::add(wg0, sg & sm0), num0, den0);
+      mul2(num1, gfn::add(wg1, kx & sm1), den1, gfn::add(wg1, sg & sm1), num1, den1);
       kx = gfn::mul(kx, gl::GEN);
     }
     if ((jj + 1) % qdf == 0 || jj + 1 == R) {
@@ -1033,6 +1034,7 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
   // permutation factors divided by beta_c, as k_quotient_1r (CH_BETA_INV..)
   const uint64_t binv0 = ch[CH_BETA_INV], binv1 = ch[CH_BETA_INV + 1];
   const uint64_t gam0 = ch[CH_GAMMA_B], gam1 = ch[CH_GAMMA_B + 1];
+  const uint64_t sm0 = ch[CH_S_MASK], sm1 = ch[CH_S_MASK + 1];
   uint64_t kx = x;
   uint64_t bs_acc = 0, bs_pw = 1, wire0 = 0, bss0 = 0, bss1 = 0;
   for (uint32_t base = 0; base < R; base += QP_WIN) {
@@ -1061,10 +1063,10 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
         const uint64_t s = cs[(uint64_t)(a.num_constants + base + c + i) * N];
         const uint64_t wg0 = gfn::add_c(gfn::mul(w[c + i], binv0), gam0);
         const uint64_t wg1 = gfn::add_c(gfn::mul(w[c + i], binv1), gam1);
-        num0 = gfn::mul(num0, gfn::add(wg0, kx));
-        num1 = gfn::mul(num1, gfn::add(wg1, kx));
-        den0 = gfn::mul(den0, gfn::add(wg0, s));
-        den1 = gfn::mul(den1, gfn::add(wg1, s));
+        num0 = gfn::mul(num0, gfn::add(wg0, kx & sm0));
+        num1 = gfn::mul(num1, gfn::add(wg1, kx & sm1));
+        den0 = gfn::mul(den0, gfn::add(wg0, s & sm0));
+        den1 = gfn::mul(den1, gfn::add(wg1, s & sm1));
         kx = gfn::mul(kx, gl::GEN);
       }
       const uint32_t bw = k == nchunks - 1 ? CH_BETA_LAST : CH_BETA_QDF;

@@ -148,6 +148,7 @@ def lib():
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),
+        "qp_debug_field_op": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, U64P, VP, ctypes.c_uint64, U64P]),
         "qp_prover_set_host_threads": (ctypes.c_int, [VP, ctypes.c_uint32]),
         "qp_prover_kernel_stats": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_int]),
@@ -299,6 +300,28 @@ def poseidon_permute(ctx, states):
     s = np.ascontiguousarray(states, dtype=np.uint64).copy()
     ctx.check(lib().qp_poseidon_permute(ctx.h, s, s.shape[0]), "qp_poseidon_permute")
     return s
+
+
+# qp_debug_field_op codes (include/qpgpu.h QP_FOP_*)
+(FOP_NT_ADD, FOP_NT_ADD4, FOP_GFN_ADD, FOP_GFN_ADD_C, FOP_PF_ADD_C, FOP_GL_ADD, FOP_NT_SUB, FOP_NT_SUB4, FOP_GL_SUB,
+ FOP_NT_REDUCE, FOP_GFN_REDUCE, FOP_GL_REDUCE128, FOP_PF_REDUCE_ROW, FOP_PF_REDUCE_ROW_C, FOP_PF_SUB_SMALL,
+ FOP_PF_MUL, FOP_PF_MUL_C, FOP_PF_MULK2, FOP_PF_MULK3, FOP_GL_MUL, FOP_PF_SBOX, FOP_PF_SBOX_C, FOP_NT_MUL_POW2,
+ FOP_ACC3, FOP_COUNT) = range(25)
+
+
+def debug_field_op(ctx, op, a, b=None, param=0):
+    """TEST-ONLY (qp_debug_field_op): the device function `op` on a[i], b[i],
+    raw u64 results (one per element; FOP_ACC3: one per group of `param`)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64).ravel()
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.uint64).ravel()
+        if b.size != a.size:
+            raise ValueError("a and b differ in length")
+    nout = a.size // param if op == FOP_ACC3 and param and a.size % param == 0 else a.size
+    out = np.zeros(nout, np.uint64)
+    ctx.check(lib().qp_debug_field_op(ctx.h, int(op), int(param), a, None if b is None else b.ctypes.data, a.size,
+                                      out), "qp_debug_field_op")
+    return out
 
 
 def hash_no_pad(values):

@@ -3,6 +3,7 @@ C ABI) against the CPU oracle, bit-exact.  SURVEY.md section 8 rows a4-a7."""
 import numpy as np
 import pytest
 
+from edge_values import bitrev_perm, constant_columns, edge_cycle
 from oracle_lib import P, commit_values, lib as olib
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +97,148 @@ def test_commit_values_parity(ctx, npolys, log_n, rate_bits, cap_h, nsalt):
     # openings: leaves + Merkle paths against the oracle's tree
     N = 1 << (log_n + rate_bits)
     idx = np.array([0, 1, N - 1, N // 2, 12345 % N], np.uint32)
+    leaves, sibs = b.open(idx)
+    assert (leaves == leaves_o[idx]).all()
+    depth = log_n + rate_bits - cap_h
+    cap2 = np.zeros(((1 << cap_h), 4), np.uint64)
+    sib_o = np.zeros((len(idx), depth, 4), np.uint64)
+    olib().ora_merkle(np.ascontiguousarray(leaves_o), log_n + rate_bits, leaves_o.shape[1], cap_h, cap2,
+                      idx.astype(np.uint64), len(idx), sib_o)
+    assert (cap2 == cap_o).all()
+    assert (sibs == sib_o).all()
+    b.free()
+
+
+def lde_oracle_leaf_order(c, log_n, rate_bits):
+    logN = log_n + rate_bits
+    rev = bitrev_perm(logN)
+    want = np.zeros((len(c), 1 << logN), np.uint64)
+    e = np.zeros(1 << logN, np.uint64)
+    for k in range(len(c)):
+        olib().ora_lde(np.ascontiguousarray(c[k]), log_n, rate_bits, G, e)
+        want[k] = e[rev]
+    return want
+
+
+@pytest.mark.parametrize("log_n,rate_bits", [(ln, r) for ln in range(10, 15) for r in range(1, 5)])
+def test_lde_cosets_kernel(ctx, monkeypatch, log_n, rate_bits):
+    """k_lde_cosets<LOG_T> (one workgroup per column walking its cosets), which
+    the heuristic picks from 256 columns on, at every size and rate it is built
+    for: each LOG_T with its tail_group<G> store loop, each rate's pre-twist
+    (ptw) and merged-twiddle (mtw) tables.  Path hook lde_few=0 forces it for
+    three columns: uniform, all p-1, a cycle through the canonical edge values."""
+    import qp_wormhole
+    assert log_n + rate_bits <= 18
+    n = 1 << log_n
+    rng = np.random.default_rng(1000 * log_n + rate_bits)
+    c = np.stack([rand_felts(rng, n), np.full(n, P - 1, np.uint64), edge_cycle(n)])
+    monkeypatch.delenv("QPGPU_PATHS", raising=False)
+    per_coset = qp_wormhole.lde(ctx, c, rate_bits)  # 3 columns: k_lde
+    monkeypatch.setenv("QPGPU_PATHS", "lde_few=0")
+    fused = qp_wormhole.lde(ctx, c, rate_bits)
+    want = lde_oracle_leaf_order(c, log_n, rate_bits)
+    assert (fused == want).all(), np.argwhere(fused != want)[:4]
+    assert (fused == per_coset).all()
+
+
+def test_lde_cosets_kernel_by_heuristic(ctx, monkeypatch):
+    """256 columns reach the fused kernel through the heuristic itself."""
+    import qp_wormhole
+    log_n, rate_bits = 10, 1
+    rng = np.random.default_rng(256)
+    c = rand_felts(rng, 256, 1 << log_n)
+    c[1] = P - 1
+    c[2] = edge_cycle(1 << log_n)
+    monkeypatch.delenv("QPGPU_PATHS", raising=False)
+    got = qp_wormhole.lde(ctx, c, rate_bits)
+    want = lde_oracle_leaf_order(c, log_n, rate_bits)
+    assert (got == want).all(), np.argwhere(got != want)[:4]
+    monkeypatch.setenv("QPGPU_PATHS", "lde_few=1000000")  # the same columns through k_lde
+    assert (qp_wormhole.lde(ctx, c, rate_bits) == want).all()
+
+
+W_2_32 = 7277203076849721926  # plonky2's generator of the 2^32-th roots of unity (field.h TWO_ADIC_GEN)
+
+
+def structured_columns(n):
+    """Columns that keep the butterflies' inputs on the edges of the field."""
+    i = np.arange(n, dtype=np.uint64)
+    even, top = i % np.uint64(2) == 0, np.uint64(P - 1)
+    cols = [np.full(n, P - 1, np.uint64), np.where(even, top, np.uint64(0)), np.where(even, np.uint64(0), top),
+            np.where(even, top, np.uint64(1))]
+    for at in (0, n // 2, n - 1):
+        col = np.zeros(n, np.uint64)
+        col[at] = P - 1
+        cols.append(col)
+    cols += [np.full(n, 2**32 - 1, np.uint64), np.full(n, P - 2**32, np.uint64), np.uint64(P - 1) - i]
+    return np.stack(cols)
+
+
+def dft_ifft(v, log_n):
+    """c_k = n^-1 sum_j v_j w^(-jk), Python integers."""
+    n = 1 << log_n
+    w_inv = pow(pow(W_2_32, 1 << (32 - log_n), P), P - 2, P)
+    n_inv = pow(n, P - 2, P)
+    pw = [pow(w_inv, e, P) for e in range(n)]
+    return [n_inv * sum(v[j] * pw[j * k % n] for j in range(n)) % P for k in range(n)]
+
+
+def dft_lde(c, log_n, rate_bits):
+    """The coefficients c evaluated on the coset G <w_N>, in bit-reversed (leaf) order."""
+    n, logN = 1 << log_n, log_n + rate_bits
+    N = 1 << logN
+    w = pow(W_2_32, 1 << (32 - logN), P)
+    pw = [pow(w, e, P) for e in range(N)]
+    cg = [c[j] * pow(G, j, P) % P for j in range(n)]
+    ev = [sum(cg[j] * pw[i * j % N] for j in range(n)) % P for i in range(N)]
+    return [ev[r] for r in bitrev_perm(logN)]
+
+
+@pytest.mark.parametrize("log_n,rate_bits", [(1, 3), (2, 3), (3, 3), (4, 3), (5, 3), (6, 3),
+                                             (10, 3), (13, 3), (14, 3), (15, 3), (16, 2)])
+def test_transforms_edge_values(ctx, log_n, rate_bits):
+    """qp_ifft and qp_lde on edge-valued columns.  log_n <= 6: against an O(n^2)
+    DFT in Python integers; each of these sizes ends in a different
+    tail<LOGS> / pass32 combination, and up to n = 16 the first butterfly stage
+    acts on the raw inputs, so add4 / sub4 / mul_pow2 see the edge values
+    themselves.  Larger sizes against the oracle; 15 and 16 run the HBM-level
+    kernels k_dif_level, k_bitrev_scale and k_coset_scale."""
+    import qp_wormhole
+    cols = structured_columns(1 << log_n)
+    got = qp_wormhole.ifft(ctx, cols)
+    if log_n <= 6:
+        ints = [[int(x) for x in col] for col in cols]
+        for k, col in enumerate(ints):
+            assert [int(x) for x in got[k]] == dft_ifft(col, log_n), ("ifft", k)
+        for rb in (1, rate_bits):
+            got = qp_wormhole.lde(ctx, cols, rb)
+            for k, col in enumerate(ints):
+                assert [int(x) for x in got[k]] == dft_lde(col, log_n, rb), ("lde", rb, k)
+        return
+    for k in range(len(cols)):
+        e = cols[k].copy()
+        olib().ora_ifft(e, log_n)
+        assert (got[k] == e).all(), ("ifft", k)
+    got = qp_wormhole.lde(ctx, cols, rate_bits)
+    want = lde_oracle_leaf_order(cols, log_n, rate_bits)
+    assert (got == want).all(), np.argwhere(got != want)[:4]
+
+
+@pytest.mark.parametrize("npolys", [5, 20, 135])
+def test_commit_constant_columns(ctx, npolys):
+    """Every column constant over H at a canonical edge value: its LDE is that
+    constant, so every leaf the leaf-hash kernels (widths 5, 20, 135) absorb is
+    made of edge values."""
+    import qp_wormhole
+    log_n, rate_bits, cap_h = 6, 3, 2
+    vals = constant_columns(npolys, 1 << log_n)
+    coeffs_o, leaves_o, cap_o = commit_values(vals, log_n, rate_bits, cap_h, want_leaves=True)
+    assert (leaves_o == vals[:, 0]).all()  # the leaves are the edge values
+    b = qp_wormhole.PolynomialBatch.from_values(ctx, vals, rate_bits, cap_h)
+    assert (b.coeffs == coeffs_o).all()
+    assert (b.cap == cap_o).all()
+    N = 1 << (log_n + rate_bits)
+    idx = np.array([0, N - 1], np.uint32)
     leaves, sibs = b.open(idx)
     assert (leaves == leaves_o[idx]).all()
     depth = log_n + rate_bits - cap_h

@@ -8,6 +8,7 @@ FRI arities [4, 4], cap height 4) plus smaller and zero-tailed variants."""
 import numpy as np
 import pytest
 
+from edge_values import CANON_EDGES, constant_columns, edge_cycle
 from oracle_lib import P, lib as olib
 
 G = 0xC65C18B67785D900
@@ -126,6 +127,43 @@ def test_quotient_recursion_gate_set_matches_oracle(ctx, log_n):
     assert (got == want).all(), np.argwhere(got != want)[:4]
 
 
+EDGE_CHALLENGES = [(P - 1, P - 1), (0, 1), (2**32 - 1, P - 2**32)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_n", [6, 8])
+@pytest.mark.parametrize("gate_set", ["leaf", "recursion"])
+def test_quotient_edge_values(ctx, circuit, gate_set, log_n):
+    """Both quotient kernels (the leaf gate set: single-read; RECURSION_GATES:
+    generic) on constant columns of canonical edge values.  The kernels read
+    LDE values and only a constant column keeps them on the edge, so every
+    constraint sum drives Acc3 with maximal products, which random cells
+    cannot do; the challenges cycle through edge pairs as well."""
+    import ctypes
+
+    import qp_wormhole
+    if gate_set == "leaf":
+        g = qp_wormhole.gate_desc(circuit)
+    else:
+        g = qp_wormhole.GateDesc.build(RECURSION_GATES, [(0, 5), (5, 10), (10, 14)], num_gate_constraints=123)
+    n = 1 << log_n
+    nzs = g.num_challenges * ((g.num_routed_wires + g.quotient_degree_factor - 1) // g.quotient_degree_factor)
+    cs = constant_columns(g.num_constants + g.num_routed_wires, n)
+    wires = constant_columns(g.num_wires, n, start=3)
+    zs = constant_columns(nzs, n, start=7)
+    B = [qp_wormhole.PolynomialBatch.from_values(ctx, v, 3, 4) for v in (cs, wires, zs)]
+    for k in range(3):
+        ch = [np.array(EDGE_CHALLENGES[(k + i) % 3], np.uint64) for i in range(4)]
+        betas, gammas, alphas, pih = ch[0], ch[1], ch[2], np.concatenate([ch[3], ch[1]])
+        got = qp_wormhole.quotient(ctx, B[0], B[1], B[2], g, betas, gammas, alphas, pih)
+        want = np.zeros_like(got)
+        assert olib().ora_quotient_desc(ctypes.addressof(g), log_n, 3, cs, wires, zs, betas, gammas, alphas, pih,
+                                        want) == 0
+        assert (got == want).all(), (k, np.argwhere(got != want)[:4])
+    for b in B:
+        b.free()
+
+
 @pytest.mark.gpu
 def test_quotient_rejects_bad_gate_parameters(ctx):
     import qp_wormhole
@@ -223,6 +261,36 @@ def test_fri_fold_matches_oracle(ctx, log_len, ab):
     want = np.zeros_like(got)
     olib().ora_fri_fold(c, log_len, ab, beta, want)
     assert (got == want).all()
+
+
+def ext_fold(c0, c1, ab, beta):
+    """The arity-2^ab coefficient fold in F[X]/(X^2 - 7), Python integers."""
+    ar, out0, out1 = 1 << ab, [], []
+    for j in range(len(c0) >> ab):
+        a0 = a1 = 0
+        for k in reversed(range(ar)):
+            a0, a1 = (a0 * beta[0] + 7 * a1 * beta[1]) % P, (a0 * beta[1] + a1 * beta[0]) % P
+            a0, a1 = (a0 + c0[j * ar + k]) % P, (a1 + c1[j * ar + k]) % P
+        out0.append(a0)
+        out1.append(a1)
+    return [out0, out1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_len,ab", [(5, 1), (3, 3), (13, 4)])
+def test_fri_fold_edge_values(ctx, log_len, ab):
+    """Coefficients and beta from the canonical edge list."""
+    import qp_wormhole
+    c = np.stack([edge_cycle(1 << log_len), edge_cycle(1 << log_len, start=5)])
+    for i in range(len(CANON_EDGES)):
+        beta = np.array([CANON_EDGES[i], CANON_EDGES[-1 - i]], np.uint64)
+        got = qp_wormhole.fri_fold(ctx, c, ab, beta)
+        want = np.zeros_like(got)
+        olib().ora_fri_fold(c, log_len, ab, beta, want)
+        assert (got == want).all(), i
+        if (log_len, ab) == (5, 1):
+            assert [[int(x) for x in row] for row in got] == \
+                ext_fold([int(x) for x in c[0]], [int(x) for x in c[1]], ab, [int(x) for x in beta]), i
 
 
 @pytest.mark.gpu
