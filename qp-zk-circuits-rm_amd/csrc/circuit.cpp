@@ -24,28 +24,9 @@ namespace qc {
 static const F NEG_ONE = gl::P - 1;
 static const uint64_t UNUSED_SELECTOR = 0xFFFFFFFFull;
 
-static inline int gate_degree(GateKind k) {
-  switch (k) {
-    case G_NOOP: return 0;
-    case G_CONSTANT: return 1;
-    case G_PUBLIC_INPUT: return 1;
-    case G_BASE_SUM: return 2;
-    case G_ARITHMETIC: return 3;
-    case G_POSEIDON: return 7;
-    case G_RANDOM_ACCESS: return RA_BITS + 1;
-    case G_ARITH_EXT: return 3;
-    case G_MUL_EXT: return 3;
-    case G_REDUCING: return 2;
-    case G_REDUCING_EXT: return 2;
-    case G_POSEIDON_MDS: return 1;
-    case G_COSET_INTERP: return CI_DEGREE;
-    default: return 0;
-  }
-}
-
 CircuitBuilder::CircuitBuilder(const CircuitConfig &cfg) : cfg_(cfg) {
-  arith_ops_ = cfg.num_routed_wires / 4;
-  base_sum_limbs_ = std::min<uint32_t>(63, cfg.num_routed_wires - 1);
+  arith_ops_ = builder_params(G_ARITHMETIC, cfg).p0;
+  base_sum_limbs_ = builder_params(G_BASE_SUM, cfg).p0;
 }
 
 Target CircuitBuilder::add_virtual_target() { return Target::virt(nvirt_++); }
@@ -425,27 +406,28 @@ CircuitData CircuitBuilder::build() {
   for (GateKind k : order)
     if (present[k]) {
       cd.gate_kinds.push_back(k);
-      cd.gate_params.push_back(k == G_CONSTANT ? ncg : k == G_BASE_SUM ? base_sum_limbs_ : k == G_ARITHMETIC ? arith_ops_
-                               : k == G_RANDOM_ACCESS ? RA_BITS : k == G_ARITH_EXT ? AE_OPS : k == G_MUL_EXT ? ME_OPS
-                               : k == G_REDUCING ? RED_COEFFS : k == G_REDUCING_EXT ? REDE_COEFFS
-                               : k == G_COSET_INTERP ? CI_BITS : 0);
-      cd.gate_params2.push_back(k == G_RANDOM_ACCESS ? RA_COPIES : k == G_COSET_INTERP ? CI_DEGREE : 0);
-      cd.gate_params3.push_back(k == G_RANDOM_ACCESS ? RA_EXTRA : 0);
+      const GateParams p = builder_params(k, cfg_);
+      cd.gate_params.push_back(p.p0);
+      cd.gate_params2.push_back(p.p1);
+      cd.gate_params3.push_back(p.p2);
     }
   const uint32_t num_gates = (uint32_t)cd.gate_kinds.size();
+  std::vector<GateShape> shapes;
+  for (uint32_t i = 0; i < num_gates; i++)
+    shapes.push_back(gate_shape(cd.gate_kinds[i], cd.gate_params[i], cd.gate_params2[i], cd.gate_params3[i]));
   uint32_t gate_index[G_NKINDS];
   for (uint32_t i = 0; i < num_gates; i++) gate_index[cd.gate_kinds[i]] = i;
   // selector_polynomials
   const uint32_t max_degree = cd.quotient_degree_factor + 1;
-  const int max_gate_degree = gate_degree(cd.gate_kinds.back());
-  if ((uint32_t)max_gate_degree + num_gates - 1 <= max_degree) {
+  const uint32_t max_gate_degree = shapes.back().degree;
+  if (max_gate_degree + num_gates - 1 <= max_degree) {
     cd.groups.push_back({0, num_gates});
     cd.selector_indices.assign(num_gates, 0);
   } else {
     uint32_t start = 0;
     while (start < num_gates) {
       uint32_t size = 0;
-      while (start + size < num_gates && size + gate_degree(cd.gate_kinds[start + size]) < max_degree) size++;
+      while (start + size < num_gates && size + shapes[start + size].degree < max_degree) size++;
       if (!size) throw std::runtime_error("gate degree too high for the quotient degree factor");
       cd.groups.push_back({start, start + size});
       start += size;
@@ -455,24 +437,14 @@ CircuitData CircuitBuilder::build() {
         if (i >= cd.groups[g].first && i < cd.groups[g].second) cd.selector_indices.push_back(g);
   }
   const uint32_t nsel = (uint32_t)cd.groups.size();
+  // gate constants and constraint count: the maximum over the gates
   uint32_t max_gate_consts = 0;
-  for (GateKind k : cd.gate_kinds)
-    max_gate_consts = std::max<uint32_t>(max_gate_consts, k == G_CONSTANT ? ncg : k == G_ARITHMETIC ? 2
-                                                          : k == G_RANDOM_ACCESS ? RA_EXTRA : k == G_ARITH_EXT ? 2
-                                                          : k == G_MUL_EXT ? 1 : 0);
-  cd.num_constants = nsel + max_gate_consts;
-  // constraint count = max over gates
   cd.num_gate_constraints = 0;
-  for (uint32_t i = 0; i < num_gates; i++) {
-    GateKind k = cd.gate_kinds[i];
-    uint32_t c = k == G_CONSTANT ? ncg : k == G_PUBLIC_INPUT ? 4 : k == G_BASE_SUM ? base_sum_limbs_ + 1
-               : k == G_ARITHMETIC ? arith_ops_ : k == G_POSEIDON ? 123
-               : k == G_RANDOM_ACCESS ? RA_COPIES * (RA_BITS + 2) + RA_EXTRA
-               : k == G_ARITH_EXT ? 2 * AE_OPS : k == G_MUL_EXT ? 2 * ME_OPS : k == G_REDUCING ? 2 * RED_COEFFS
-               : k == G_REDUCING_EXT ? 2 * REDE_COEFFS : k == G_POSEIDON_MDS ? 24
-               : k == G_COSET_INTERP ? 4 + 4 * CI_NINT : 0;
-    cd.num_gate_constraints = std::max(cd.num_gate_constraints, c);
+  for (const GateShape &sh : shapes) {
+    max_gate_consts = std::max(max_gate_consts, (uint32_t)sh.consts);
+    cd.num_gate_constraints = std::max(cd.num_gate_constraints, (uint32_t)sh.constraints);
   }
+  cd.num_constants = nsel + max_gate_consts;
   // num_partial_products: routed wires in chunks of qdf, minus one
   cd.num_partial_products = (cfg_.num_routed_wires + cd.quotient_degree_factor - 1) / cd.quotient_degree_factor - 1;
   cd.k_is.resize(cfg_.num_routed_wires);
@@ -1006,23 +978,15 @@ std::vector<uint8_t> CircuitData::common_bytes() const {
   w.u64(0);  // luts
   w.u64(gate_kinds.size());
   for (size_t i = 0; i < gate_kinds.size(); i++) {
-    w.u32(gate_serial_id(gate_kinds[i]));
-    GateKind k = gate_kinds[i];
-    if (k == G_CONSTANT || k == G_BASE_SUM || k == G_ARITHMETIC || k == G_ARITH_EXT || k == G_MUL_EXT ||
-        k == G_REDUCING || k == G_REDUCING_EXT)
-      w.u64(gate_params[i]);
+    const GateKind k = gate_kinds[i];
+    const uint32_t prm[3] = {gate_params[i], gate_params2[i], gate_params3[i]};
+    w.u32(serial_id(k));
+    for (uint32_t j = 0; j < serial_params(k); j++) w.u64(prm[j]);
     if (k == G_COSET_INTERP) {  // CosetInterpolationGate { subgroup_bits, degree, barycentric_weights }
-      w.u64(gate_params[i]);
-      w.u64(gate_params2[i]);
       const uint32_t np = 1u << gate_params[i];
       const F om = gl::root_of_unity(gate_params[i]), ninv = gl::inv(np);
       w.u64(np);
-      for (uint32_t j = 0, x = 0; j < np; j++, (void)x) w.u64(gl::mul(gl::pow(om, j), ninv));  // 1 / prod_{l != j}(w^j - w^l) = w^j / n
-    }
-    if (k == G_RANDOM_ACCESS) {  // RandomAccessGate { bits, num_copies, num_extra_constants }
-      w.u64(gate_params[i]);
-      w.u64(gate_params2[i]);
-      w.u64(gate_params3[i]);
+      for (uint32_t j = 0; j < np; j++) w.u64(gl::mul(gl::pow(om, j), ninv));  // 1 / prod_{l != j}(w^j - w^l) = w^j / n
     }
   }
   return w.b;

@@ -14,11 +14,13 @@
 // 256 proofs per batch on the host threads.
 #pragma once
 #include <stdint.h>
+#include <algorithm>
 #include <map>
 #include <string>
 #include <tuple>
 #include <unordered_map>
 #include <vector>
+#include "gates.h"
 
 namespace qc {
 
@@ -37,18 +39,8 @@ struct Target {
   bool operator<(const Target &o) const { return v < o.v; }
 };
 
-enum GateKind : uint8_t {
-  G_NOOP = 0, G_CONSTANT, G_PUBLIC_INPUT, G_BASE_SUM, G_ARITHMETIC, G_POSEIDON,
-  // the recursive verifier's gates (plonky2 verify_proof; aggregation circuits)
-  G_RANDOM_ACCESS,   // RandomAccessGate{bits 4, copies 4, extra constants 2}
-  G_ARITH_EXT,       // ArithmeticExtensionGate{num_ops 10}: out = c0 m0 m1 + c1 addend (ext)
-  G_MUL_EXT,         // MulExtensionGate{num_ops 13}: out = c0 m0 m1 (ext)
-  G_REDUCING,        // ReducingGate{num_coeffs 43}: Horner of base coefficients by an ext alpha
-  G_REDUCING_EXT,    // ReducingExtensionGate{num_coeffs 32}: the same over ext coefficients
-  G_POSEIDON_MDS,    // PoseidonMdsGate: the 12x12 MDS layer on ext values
-  G_COSET_INTERP,    // CosetInterpolationGate{subgroup_bits 4, degree 6}
-  G_NKINDS
-};
+// gate kinds: the library's one table (gates.h)
+using namespace qg;
 
 // extension-field target (a, b) = a + b X, X^2 = 7 (plonky2 ExtensionTarget<2>)
 struct ExtT {
@@ -77,26 +69,6 @@ constexpr uint32_t ra_wire_claimed(uint32_t c) { return (2 + RA_VEC) * c + 1; }
 constexpr uint32_t ra_wire_item(uint32_t i, uint32_t c) { return (2 + RA_VEC) * c + 2 + i; }
 constexpr uint32_t ra_wire_bit(uint32_t i, uint32_t c) { return (2 + RA_VEC) * RA_COPIES + RA_EXTRA + RA_BITS * c + i; }
 
-// plonky2 DefaultGateSerializer ids
-inline uint32_t gate_serial_id(GateKind k) {
-  switch (k) {
-    case G_NOOP: return 9;
-    case G_CONSTANT: return 3;
-    case G_PUBLIC_INPUT: return 12;
-    case G_BASE_SUM: return 2;
-    case G_ARITHMETIC: return 0;
-    case G_POSEIDON: return 11;
-    case G_RANDOM_ACCESS: return 13;
-    case G_ARITH_EXT: return 1;
-    case G_MUL_EXT: return 8;
-    case G_REDUCING: return 15;
-    case G_REDUCING_EXT: return 14;
-    case G_POSEIDON_MDS: return 10;
-    case G_COSET_INTERP: return 4;
-    default: return 0xFFFFFFFF;
-  }
-}
-
 struct CircuitConfig {
   uint32_t num_wires = 135, num_routed_wires = 80, num_constants = 2;
   bool use_base_arithmetic_gate = true;
@@ -112,6 +84,26 @@ struct CircuitConfig {
     return c;
   }
 };
+
+// the parameters (p0, p1, p2 of gates.h) of the builder's gate of a kind: the
+// new_from_config shapes above
+struct GateParams {
+  uint32_t p0 = 0, p1 = 0, p2 = 0;
+};
+inline GateParams builder_params(GateKind k, const CircuitConfig &cfg) {
+  switch (k) {
+    case G_CONSTANT: return {cfg.num_constants};
+    case G_BASE_SUM: return {std::min<uint32_t>(63, cfg.num_routed_wires - 1)};
+    case G_ARITHMETIC: return {cfg.num_routed_wires / 4};
+    case G_RANDOM_ACCESS: return {RA_BITS, RA_COPIES, RA_EXTRA};
+    case G_ARITH_EXT: return {AE_OPS};
+    case G_MUL_EXT: return {ME_OPS};
+    case G_REDUCING: return {RED_COEFFS};
+    case G_REDUCING_EXT: return {REDE_COEFFS};
+    case G_COSET_INTERP: return {CI_BITS, CI_DEGREE};
+    default: return {};
+  }
+}
 
 struct GateInst {
   GateKind kind;

@@ -244,10 +244,16 @@ int qp_circuit_census(const qp_circuit *c, uint32_t *gens, uint32_t *rows, uint3
     }
   }
   memset(gens, 0, 14 * sizeof(uint32_t));
-  memset(rows, 0, qc::G_NKINDS * sizeof(uint32_t));
   for (const auto &g : c->cd.schedule)
     if (g.kind < 14) gens[g.kind]++;
-  for (const auto &r : c->cd.rows) rows[r.kind]++;
+  // rows[]: the ABI's order (qpgpu.h), not the kind enum's
+  static const qc::GateKind order[13] = {qc::G_NOOP,         qc::G_CONSTANT,      qc::G_PUBLIC_INPUT, qc::G_BASE_SUM,
+                                         qc::G_ARITHMETIC,   qc::G_POSEIDON,      qc::G_RANDOM_ACCESS, qc::G_ARITH_EXT,
+                                         qc::G_MUL_EXT,      qc::G_REDUCING,      qc::G_REDUCING_EXT,
+                                         qc::G_POSEIDON_MDS, qc::G_COSET_INTERP};
+  uint32_t by_kind[qc::G_NKINDS] = {0};
+  for (const auto &r : c->cd.rows) by_kind[r.kind]++;
+  for (int i = 0; i < 13; i++) rows[i] = by_kind[order[i]];
   return QP_OK;
 }
 

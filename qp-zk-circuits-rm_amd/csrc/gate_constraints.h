@@ -65,23 +65,23 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
   using ExtT = typename GG::E;
   using Alg = typename GG::Alg;
   std::vector<ExtT> out;
-  switch (gate.id) {
-    case 9:  // Noop
+  switch (gate.kind) {
+    case qc::G_NOOP:
       break;
-    case 3:  // Constant
+    case qc::G_CONSTANT:
       for (uint32_t i = 0; i < gate.p[0]; i++) out.push_back(g.sub(gc[i], w[i]));
       break;
-    case 12:  // PublicInput
+    case qc::G_PUBLIC_INPUT:
       for (uint32_t i = 0; i < 4; i++) out.push_back(g.sub(w[i], g.ext(pi_hash[i])));
       break;
-    case 2: {  // BaseSum<2>: the recomposed sum, then limb (limb - 1) per limb
+    case qc::G_BASE_SUM: {  // BaseSum<2>: the recomposed sum, then limb (limb - 1) per limb
       const uint32_t L = (uint32_t)gate.p[0];
       std::vector<ExtT> limbs(w.begin() + 1, w.begin() + 1 + L);
       out.push_back(g.sub(g.reduce(g.ext_const(2), limbs), w[0]));
       for (ExtT l : limbs) out.push_back(g.mul_sub(l, l, l));
       break;
     }
-    case 0: {  // Arithmetic: out - (c0 m0 m1 + c1 addend)
+    case qc::G_ARITHMETIC: {  // out - (c0 m0 m1 + c1 addend)
       for (uint32_t i = 0; i < gate.p[0]; i++) {
         ExtT scaled = g.mul_many({gc[0], w[4 * i], w[4 * i + 1]});
         ExtT comp = g.mul_add(gc[1], w[4 * i + 2], scaled);
@@ -89,9 +89,9 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       }
       break;
     }
-    case 1:    // ArithmeticExtension{num_ops}: out - (c0 m0 m1 + c1 addend), algebra
-    case 8: {  // MulExtension{num_ops}: out - c0 m0 m1
-      const bool ae = gate.id == 1;
+    case qc::G_ARITH_EXT:  // ArithmeticExtension{num_ops}: out - (c0 m0 m1 + c1 addend), algebra
+    case qc::G_MUL_EXT: {  // MulExtension{num_ops}: out - c0 m0 m1
+      const bool ae = gate.kind == qc::G_ARITH_EXT;
       for (uint32_t i = 0; i < gate.p[0]; i++) {
         const uint32_t o = ae ? 8 * i : 6 * i;
         Alg scaled = g.alg_scalar_mul(gc[0], g.alg_mul(g.alg(w, o), g.alg(w, o + 2)));
@@ -100,9 +100,9 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       }
       break;
     }
-    case 15:    // Reducing{num_coeffs}: acc_i - (acc_{i-1} alpha + coeff_i), base coefficients
-    case 14: {  // ReducingExtension{num_coeffs}: ext coefficients
-      const uint32_t nc = (uint32_t)gate.p[0], cw = gate.id == 15 ? 1 : 2;
+    case qc::G_REDUCING:  // Reducing{num_coeffs}: acc_i - (acc_{i-1} alpha + coeff_i), base coefficients
+    case qc::G_REDUCING_EXT: {  // ReducingExtension{num_coeffs}: ext coefficients
+      const uint32_t nc = (uint32_t)gate.p[0], cw = gate.kind == qc::G_REDUCING ? 1 : 2;
       const Alg alpha = g.alg(w, 2);
       Alg acc = g.alg(w, 4);
       for (uint32_t i = 0; i < nc; i++) {
@@ -113,7 +113,7 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       }
       break;
     }
-    case 10: {  // PoseidonMds: out_r - (sum_i CIRC[i] in_{i+r} + DIAG[r] in_r), algebra
+    case qc::G_POSEIDON_MDS: {  // out_r - (sum_i CIRC[i] in_{i+r} + DIAG[r] in_r), algebra
       for (uint32_t r = 0; r < 12; r++) {
         Alg res = g.alg_zero();
         for (uint32_t i = 0; i < 12; i++)
@@ -123,7 +123,7 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       }
       break;
     }
-    case 4: {  // CosetInterpolation{subgroup_bits, degree}
+    case qc::G_COSET_INTERP: {  // CosetInterpolation{subgroup_bits, degree}
       const uint32_t nbits = (uint32_t)gate.p[0], deg = (uint32_t)gate.p[1], np = 1u << nbits;
       const uint32_t nint = (np - 2) / (deg - 1);
       const uint32_t sv = 1, sep = sv + 2 * np, sev = sep + 2, si = sev + 2, ssh = si + 4 * nint;
@@ -153,7 +153,7 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       g.push(out, g.alg_sub(g.alg(w, sev), ev));
       break;
     }
-    case 13: {  // RandomAccess{bits, copies, extra}
+    case qc::G_RANDOM_ACCESS: {  // RandomAccess{bits, copies, extra}
       const uint32_t bits = (uint32_t)gate.p[0], copies = (uint32_t)gate.p[1], extra = (uint32_t)gate.p[2];
       const uint32_t vec = 1u << bits, routed = (2 + vec) * copies + extra;
       for (uint32_t cp = 0; cp < copies; cp++) {
@@ -177,7 +177,7 @@ std::vector<typename GG::E> gate_constraints(GG &g, const InnerCommon::Gate &gat
       for (uint32_t i = 0; i < extra; i++) out.push_back(g.sub(gc[i], w[(2 + vec) * copies + i]));
       break;
     }
-    case 11: {  // Poseidon: constant layers, x^7 S-boxes, PoseidonMdsGate layers, wire checks
+    case qc::G_POSEIDON: {  // constant layers, x^7 S-boxes, PoseidonMdsGate layers, wire checks
       ExtT swap = w[24];
       out.push_back(g.mul_sub(swap, swap, swap));
       for (int i = 0; i < 4; i++) out.push_back(g.mul_sub(swap, g.sub(w[i + 4], w[i]), w[25 + i]));

@@ -118,9 +118,6 @@ struct qp_prover {
   // device witness generation (witness.hip): schedule + per-proof slot values
   DevBuf wg_gens, wg_lvl, wg_lpos, wg_wslot, wg_wslot_cm, wg_in_slots, wg_pi_slots, wg_vals, wg_in, wg_err, wg_pis;
   uint32_t wg_nslots = 0, wg_nin = 0, wg_nlev = 0;
-  bool has_poseidon_gate = false;
-  bool has_random_access = false;
-  bool generic_quotient = false;  // a gate outside k_quotient_1r's set (the recursive verifier's RandomAccess)
   uint64_t *h_in = nullptr;  // pinned [max_batch][wg_nin] commit() values
   std::vector<std::vector<uint64_t>> wscratch;  // per-proof slot values when host chains run split
   std::vector<uint32_t> h_werr;
@@ -270,46 +267,12 @@ int setup(qp_prover *P) {
     c->err = "unsupported circuit shape for the GPU prover (need 2 challenges, qdf = blowup, 2^6 <= n <= 2^15)";
     return QP_ERR_ARG;
   }
-  qpk::GateDesc &g = P->gdesc;
-  g.ngates = (uint32_t)cd.gate_kinds.size();
-  g.nsel = (uint32_t)cd.groups.size();
-  for (uint32_t i = 0; i < g.ngates; i++) {
-    switch (cd.gate_kinds[i]) {
-      case qc::G_NOOP: g.kind[i] = qpk::GK_NOOP; break;
-      case qc::G_CONSTANT: g.kind[i] = qpk::GK_CONSTANT; break;
-      case qc::G_PUBLIC_INPUT: g.kind[i] = qpk::GK_PUBLIC_INPUT; break;
-      case qc::G_BASE_SUM: g.kind[i] = qpk::GK_BASE_SUM; break;
-      case qc::G_ARITHMETIC: g.kind[i] = qpk::GK_ARITHMETIC; break;
-      case qc::G_POSEIDON:
-        g.kind[i] = qpk::GK_POSEIDON;
-        P->has_poseidon_gate = true;
-        break;
-      case qc::G_RANDOM_ACCESS:
-        g.kind[i] = qpk::GK_RANDOM_ACCESS;
-        P->has_random_access = true;
-        // k_quotient_1r evaluates the RandomAccessGate of the recursive verifier's width
-        if (cd.gate_params[i] != qpk::RA_QBITS) P->generic_quotient = true;
-        break;
-      // the other recursive-verifier gates: the generic (any gate list) kernel
-      case qc::G_ARITH_EXT: g.kind[i] = qpk::GK_ARITH_EXT; P->generic_quotient = true; break;
-      case qc::G_MUL_EXT: g.kind[i] = qpk::GK_MUL_EXT; P->generic_quotient = true; break;
-      case qc::G_REDUCING: g.kind[i] = qpk::GK_REDUCING; P->generic_quotient = true; break;
-      case qc::G_REDUCING_EXT: g.kind[i] = qpk::GK_REDUCING_EXT; P->generic_quotient = true; break;
-      case qc::G_POSEIDON_MDS: g.kind[i] = qpk::GK_POSEIDON_MDS; P->generic_quotient = true; break;
-      case qc::G_COSET_INTERP: g.kind[i] = qpk::GK_COSET_INTERP; P->generic_quotient = true; break;
-      default:
-        c->err = "unsupported gate kind for the GPU prover";
-        return QP_ERR_ARG;
-    }
-    g.param[i] = cd.gate_params[i];
-    g.param2[i] = i < cd.gate_params2.size() ? cd.gate_params2[i] : 0;
-    g.param3[i] = i < cd.gate_params3.size() ? cd.gate_params3[i] : 0;
-    g.sel_index[i] = cd.selector_indices[i];
+  qp_gate_desc gd;
+  if (qp_circuit_gate_desc(P->circuit, &gd) != QP_OK) {
+    c->err = "more gates or selector groups than a gate description holds";
+    return QP_ERR_ARG;
   }
-  for (uint32_t s = 0; s < g.nsel; s++) {
-    g.grp_lo[s] = cd.groups[s].first;
-    g.grp_hi[s] = cd.groups[s].second;
-  }
+  P->gdesc = qpk::gate_desc_dev(gd);
   const uint64_t n = 1ull << P->log_n;
   const uint64_t N = n << P->rate_bits;
   TRY(hipSetDevice(c->device));
@@ -658,13 +621,7 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     a.apow = P->apow.p;
     a.xtab = P->qtab.p;
     a.l0tab = P->qtab.p + N;
-    const uint32_t B = 1u << P->rate_bits;
-    const uint64_t wN = gl::root_of_unity(logN);
-    for (uint32_t k = 0; k < B; k++) {
-      uint64_t xn = gl::pow(gl::mul(gl::GEN, gl::pow(wN, k)), n);
-      a.zh[k] = gl::sub(xn, 1);
-      a.zh_inv[k] = gl::inv(a.zh[k]);
-    }
+    qpk::quotient_zh(a, P->log_n, P->rate_bits);
     a.q_out = P->qvals.p;
     a.q_bstride = (uint64_t)nc * N;
     a.log_n = P->log_n;
@@ -676,9 +633,7 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     kt_begin(P, 3);
     // the leaf gate set: one single-read pass; any other gate list (and the
     // path hook quotient_parts=1): the per-gate launches
-    const qpk::QuotientKernel qk =
-        P->generic_quotient || qpk::path_opt("quotient_parts", 0) ? qpk::QK_PARTS : qpk::QK_1R;
-    qpk::quotient_values(a, qk, nb, s);
+    qpk::quotient_values(a, qpk::quotient_kernel(a.g, a.R), nb, s);
     kt_end(P, 3, (double)nb * N);
     qpk::quotient_coeffs(c->tw, P->qvals.p, P->cbuf.p, P->quot.coeffs.p, P->log_n, P->rate_bits, nc, nb,
                          (uint64_t)nc * N, (uint64_t)nc * N, P->quot.cbs(), s);
@@ -771,12 +726,10 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     uint64_t shift = gl::GEN;
     for (size_t l = 0; l < P->arity.size(); l++) {
       const uint32_t ab = P->arity[l];
-      // values of this layer: coset_fft(coef, shift) of size 2^lg, leaf order
-      qpk::lde(c->tw, coef, coef_cs, P->fvals[l].p, 1ull << lg, 2, coef_log, lg - coef_log, shift, nb, coef_bs,
-               2ull << lg, s);
+      // values of this layer: coset_fft(coef, shift) of size 2^lg, leaf order, and their tree
+      qpk::fri_layer_tree(c->tw, coef, coef_cs, coef_bs, coef_log, P->fvals[l].p, P->fdig[l].p, lg, ab, P->cap_h, shift,
+                          nb, s);
       const uint64_t dbs = qpk::tree_digest_count(lg - ab, P->cap_h) * 4;
-      qpk::fri_leaf(P->fvals[l].p, P->fdig[l].p, lg, ab, 2ull << lg, dbs, nb, s);
-      qpk::merkle_tree(P->fdig[l].p, lg - ab, P->cap_h, nb, dbs, s);
       TRY(hipGetLastError());
       if ((rc = fetch_caps(P, P->fdig[l].p, dbs, lg - ab, nb))) return rc;
       P->pool->parallel_for(nb, [&](size_t b) {
@@ -828,7 +781,6 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
   });
   TRY(hipMemcpyAsync(P->pow_state.p, P->h_powst.data(), (size_t)nb * 192, hipMemcpyHostToDevice, s));
   TRY(hipMemcpyAsync(P->pow_pos.p, P->h_pos.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
-  TRY(hipMemsetAsync(P->pow_found.p, 0xFF, (size_t)nb * 8, s));
   if (P->pow_forced) {
     // test-only: the given witness for every proof (reproducing a reference
     // proof, whose find_any witness is nondeterministic); the transcript and
@@ -836,17 +788,9 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     TRY(hipStreamSynchronize(s));
     for (uint32_t b = 0; b < nb; b++) P->h_found[b] = P->pow_forced_witness;
   } else {
-    // Minimal witness per proof in one launch (k_pow_scan): 2048 workgroups
-    // claim 256-candidate blocks from per-proof counters, moving on to the
-    // next proof once theirs has a hit below the claimed block
-    const uint64_t limit = 1ull << std::min<uint32_t>(P->pow_bits + 20, 62);
-    TRY(hipMemsetAsync(P->pow_next.p, 0, (size_t)nb * 8, s));
-    // (per-wave claims and 2-4 candidates per thread measured no better:
-    // profiles/r05_ab_pow_wave.log, r05_ab_pow_cpt.log; a windowed loop with a
-    // host check per window was the round-1 form)
-    qpk::k_pow_scan<<<2048, 256, 0, s>>>(P->pow_state.p, (const uint32_t *)P->pow_pos.p, P->pow_found.p,
-                                         P->pow_next.p, nb, P->pow_bits, limit);
-    TRY(hipGetLastError());
+    // minimal witness per proof in one launch
+    TRY(qpk::pow_search(P->pow_state.p, (const uint32_t *)P->pow_pos.p, P->pow_found.p, P->pow_next.p, nb, P->pow_bits,
+                        s));
     TRY(hipMemcpyAsync(P->h_found.data(), P->pow_found.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
     TRY(hipStreamSynchronize(s));
     for (uint32_t b = 0; b < nb; b++)

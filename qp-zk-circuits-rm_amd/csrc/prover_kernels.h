@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gates.h"
 #include "kernels.h"
 #include "ntt_device.h"
 
@@ -30,12 +31,7 @@ void perm_challenges(uint64_t *ch, const uint64_t *beta, const uint64_t *gamma, 
 constexpr uint32_t OPEN_STRIDE = 520;  // 257 ext openings per proof (+pad)
 constexpr uint32_t APOW_STRIDE = 256;  // alpha_c^i, i < #vanishing terms (per challenge)
 
-// = QP_GATE_* (include/qpgpu.h)
-enum GateKindDev : uint32_t {
-  GK_NOOP = 0, GK_CONSTANT, GK_PUBLIC_INPUT, GK_BASE_SUM, GK_ARITHMETIC, GK_POSEIDON,
-  GK_ARITH_EXT, GK_MUL_EXT, GK_RANDOM_ACCESS, GK_EXPONENTIATION, GK_REDUCING, GK_REDUCING_EXT, GK_POSEIDON_MDS,
-  GK_COSET_INTERP, GK_COUNT
-};
+using namespace qg;  // gate kinds (gates.h)
 // RandomAccessGate width k_quotient_1r evaluates (the recursive verifier's
 // RandomAccessGate::new_from_config shape); other widths take the per-gate
 // launches (k_quotient_part)
@@ -49,6 +45,26 @@ struct GateDesc {
            grp_hi[MAX_GATES_DEV] = {0};
 };
 
+static_assert(MAX_GATES_DEV == QP_MAX_GATES, "GateDesc holds an ABI gate description");
+// the kernels' form of a gate description
+inline GateDesc gate_desc_dev(const qp_gate_desc &g) {
+  GateDesc d;
+  d.ngates = g.num_gates;
+  d.nsel = g.num_selectors;
+  for (uint32_t i = 0; i < g.num_gates; i++) {
+    d.kind[i] = g.kind[i];
+    d.param[i] = g.param[i];
+    d.param2[i] = g.param2[i];
+    d.param3[i] = g.param3[i];
+    d.sel_index[i] = g.selector_index[i];
+  }
+  for (uint32_t i = 0; i < g.num_selectors; i++) {
+    d.grp_lo[i] = g.group_lo[i];
+    d.grp_hi[i] = g.group_hi[i];
+  }
+  return d;
+}
+
 struct QuotientArgs {
   const uint64_t *cs_lde, *w_lde, *z_lde;
   uint64_t w_bstride, z_bstride;
@@ -60,6 +76,8 @@ struct QuotientArgs {
   uint32_t log_n, rate_bits, R, qdf, num_constants;
   GateDesc g;
 };
+// zh[k] = Z_H on coset k of the LDE domain (x^n - 1 at x = g w_N^k) and its inverse
+void quotient_zh(QuotientArgs &a, uint32_t log_n, uint32_t rate_bits);
 
 struct FriComposeArgs {
   const uint64_t *coeffs[4];
@@ -100,6 +118,12 @@ enum QuotientKernel : uint32_t {
   QK_1R,    // k_quotient_1r: the leaf gate set, every column read once
   QK_PARTS  // k_quotient_part: permutation terms, then one launch per gate (any gate list)
 };
+// the kernel a gate list takes.  k_quotient_1r's precondition: kinds among
+// Noop, Constant, PublicInput, BaseSum, Arithmetic, Poseidon and RandomAccess
+// of RA_QBITS bits, each at most once, the Constant, PublicInput, BaseSum and
+// Arithmetic reads inside the R routed wires it sweeps; anything else, and the
+// path hook quotient_parts=1, takes the per-gate launches
+QuotientKernel quotient_kernel(const GateDesc &g, uint32_t R);
 void quotient_values(const QuotientArgs &a, QuotientKernel k, uint32_t nb, hipStream_t s);
 // ... and their coset iNTT into nc * qdf * n coefficients per proof (qvals
 // [nb][nc][N] leaf order -> coeffs [nb][nc][qdf * n]; cbuf: scratch of the
@@ -139,10 +163,22 @@ __global__ void k_fri_leaf_row(const uint64_t *vals, uint64_t *dig, uint32_t log
 // the leaf digests of a FRI layer for nb proofs (row or one-lane form by size)
 void fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
               uint64_t d_bstride, uint32_t nb, hipStream_t s);
+// one FRI reduction layer's commitment for nb proofs: values = coset_fft(coef,
+// shift) of size 2^log_len in leaf order (coef: [2][coef_cstride] per proof,
+// 2^coef_log of them possibly nonzero), the leaf digests of 2^ab values each
+// and the tree over them (dig: tree_digest_count(log_len - ab, cap_h) * 4 words per proof)
+void fri_layer_tree(const Twiddles &tw, const uint64_t *coef, uint64_t coef_cstride, uint64_t coef_bstride,
+                    uint32_t coef_log, uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint32_t cap_h,
+                    uint64_t shift, uint32_t nb, hipStream_t s);
 __global__ void k_fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer,
                        const uint64_t *chal, uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz);
 __global__ void k_pow_scan(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
                            uint32_t bits, uint64_t limit);
+// fri_proof_of_work's minimal witness per proof in one launch: found[b] = the
+// least witness below 2^min(bits + 20, 62), all ones if none (found and the
+// claim counters next are reset here)
+hipError_t pow_search(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
+                      uint32_t bits, hipStream_t s);
 __global__ void k_gather_rows_b(const uint64_t *cols, uint64_t stride, uint64_t bstride, uint32_t ncols,
                                 const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
 __global__ void k_gather_paths_b(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, uint32_t cap_h,

@@ -384,7 +384,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
                                                     const uint64_t *__restrict__ wl,
                                                     const uint64_t *__restrict__ gc, uint64_t N, TermAcc &A) {
   switch (kind) {
-    case GK_ARITH_EXT:  // per op: multiplicand_0, multiplicand_1, addend, output
+    case G_ARITH_EXT:  // per op: multiplicand_0, multiplicand_1, addend, output
       for (uint32_t i = 0; i < q0; i++) {
         const uint32_t o = 8 * i;
         uint64_t p0, p1;
@@ -394,7 +394,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
         A.emit(gfn::sub(WV(o + 7), gfn::add(gfn::mul(p1, c0), gfn::mul(WV(o + 5), c1))));
       }
       break;
-    case GK_MUL_EXT:  // per op: multiplicand_0, multiplicand_1, output
+    case G_MUL_EXT:  // per op: multiplicand_0, multiplicand_1, output
       for (uint32_t i = 0; i < q0; i++) {
         const uint32_t o = 6 * i;
         uint64_t p0, p1;
@@ -403,12 +403,12 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
         A.emit(gfn::sub(WV(o + 5), gfn::mul(p1, gc[0])));
       }
       break;
-    case GK_REDUCING:
-    case GK_REDUCING_EXT: {
+    case G_REDUCING:
+    case G_REDUCING_EXT: {
       // output 0..2, alpha 2..4, old_acc 4..6, coeffs from 6, then accumulators;
       // a chunk's coefficients and accumulators are loaded before its Horner
       // steps (eight steps' reads in flight instead of one)
-      const uint32_t cw = kind == GK_REDUCING ? 1 : 2, start_accs = 6 + cw * q0;
+      const uint32_t cw = kind == G_REDUCING ? 1 : 2, start_accs = 6 + cw * q0;
       uint64_t a0 = WV(4), a1 = WV(5);
       const uint64_t al0 = WV(2), al1 = WV(3);
       constexpr uint32_t CH = 8;
@@ -439,7 +439,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
       }
       break;
     }
-    case GK_EXPONENTIATION: {  // base 0, power bits 1.. (LE), output 1+nb, intermediates 2+nb..
+    case G_EXPONENTIATION: {  // base 0, power bits 1.. (LE), output 1+nb, intermediates 2+nb..
       const uint64_t base = WV(0);
       uint64_t prev = 1;
       for (uint32_t i = 0; i < q0; i++) {
@@ -452,7 +452,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
       A.emit(gfn::sub(WV(1 + q0), WV(2 + q0 + q0 - 1)));
       break;
     }
-    case GK_POSEIDON_MDS: {  // inputs 0..24, outputs 24..48 (ext pairs)
+    case G_POSEIDON_MDS: {  // inputs 0..24, outputs 24..48 (ext pairs)
       // the permutation's MDS layer (circulant + diagonal) on each coordinate
       // of the 12 extension inputs, each input read once
       uint64_t a[12], b[12];
@@ -470,7 +470,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
       }
       break;
     }
-    case GK_RANDOM_ACCESS: {  // q0 bits, q1 copies, q2 extra constants
+    case G_RANDOM_ACCESS: {  // q0 bits, q1 copies, q2 extra constants
       const uint32_t vec = 1u << q0, routed = (2 + vec) * q1 + q2;
       for (uint32_t cp = 0; cp < q1; cp++) {
         const uint32_t base = (2 + vec) * cp, bw = routed + cp * q0;
@@ -512,7 +512,7 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
       for (uint32_t i = 0; i < q2; i++) A.emit(gfn::sub(gc[(uint64_t)i * N], WV((2 + vec) * q1 + i)));
       break;
     }
-    case GK_COSET_INTERP: {  // q0 subgroup bits, q1 degree
+    case G_COSET_INTERP: {  // q0 subgroup bits, q1 degree
       const uint32_t np = 1u << q0, deg = q1, nint = (np - 2) / (deg - 1);
       const uint32_t sv = 1, sep = sv + 2 * np, sev = sep + 2, si = sev + 2, ssh = si + 4 * nint;
       // w_16 = 2^12 (the subgroup of the FRI arity-16 cosets), 1 / 2^k = p - (p - 1) / 2^k
@@ -561,6 +561,34 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
   }
 }
 
+
+// selector filter of gate gi at the point cs addresses (constants columns,
+// stride N): prod over the gate's group of (j - s), j != gi, times (UNUSED - s)
+// when there are several groups
+__device__ __forceinline__ uint64_t selector_filter(const GateDesc &g, const uint64_t *cs, uint64_t N, uint32_t gi) {
+  const uint32_t si = g.sel_index[gi];
+  const uint64_t sv = cs[(uint64_t)si * N];
+  uint64_t f = 1;
+  for (uint32_t jg = g.grp_lo[si]; jg < g.grp_hi[si]; jg++)
+    if (jg != gi) f = gfn::mul(f, gfn::sub(jg, sv));
+  if (g.nsel > 1) f = gfn::mul(f, gfn::sub(0xFFFFFFFFull, sv));
+  return f;
+}
+
+// a quotient launch's store of point t (rev = its natural index): the last
+// launch divides by Z_H (zh_inv of rev's coset) and canonicalises, the others
+// leave the raw accumulators for the next
+__device__ __forceinline__ void quotient_store(const QuotientArgs &a, uint64_t *q, uint64_t N, uint32_t t, uint32_t rev,
+                                               uint64_t acc0, uint64_t acc1, bool last) {
+  if (last) {
+    const uint64_t zh_inv = a.zh_inv[rev & ((1u << a.rate_bits) - 1)];
+    q[t] = gfn::canon(gfn::mul(acc0, zh_inv));
+    q[N + t] = gfn::canon(gfn::mul(acc1, zh_inv));
+  } else {
+    q[t] = acc0;
+    q[N + t] = acc1;
+  }
+}
 
 // Single-read form (the default): every LDE column is read once per point,
 // wires 0..23 a second time by the Poseidon gate (its inputs and outputs).
@@ -621,12 +649,12 @@ k_quotient_1r(QuotientArgs a) {
   int g_const = -1, g_pi = -1, g_bs = -1, g_ar = -1, g_pos = -1, g_ra = -1;
   for (uint32_t gi = 0; gi < a.g.ngates; gi++) {
     switch (a.g.kind[gi]) {
-      case GK_CONSTANT: g_const = (int)gi; break;
-      case GK_PUBLIC_INPUT: g_pi = (int)gi; break;
-      case GK_BASE_SUM: g_bs = (int)gi; break;
-      case GK_ARITHMETIC: g_ar = (int)gi; break;
-      case GK_POSEIDON: g_pos = (int)gi; break;
-      case GK_RANDOM_ACCESS: g_ra = (int)gi; break;
+      case G_CONSTANT: g_const = (int)gi; break;
+      case G_PUBLIC_INPUT: g_pi = (int)gi; break;
+      case G_BASE_SUM: g_bs = (int)gi; break;
+      case G_ARITHMETIC: g_ar = (int)gi; break;
+      case G_POSEIDON: g_pos = (int)gi; break;
+      case G_RANDOM_ACCESS: g_ra = (int)gi; break;
       default: break;
     }
   }
@@ -745,16 +773,7 @@ k_quotient_1r(QuotientArgs a) {
     }
   }
   uint64_t acc0 = pz0.value(), acc1 = pz1.value();
-  // selector filters: prod_{j in group, j != gate}(j - s) * (UNUSED - s)
-  auto filter = [&](int gi) -> uint64_t {
-    const uint32_t si = a.g.sel_index[gi];
-    const uint64_t sv = cs[(uint64_t)si * N];
-    uint64_t f = 1;
-    for (uint32_t jg = a.g.grp_lo[si]; jg < a.g.grp_hi[si]; jg++)
-      if (jg != (uint32_t)gi) f = gfn::mul(f, gfn::sub(jg, sv));
-    if (nsel > 1) f = gfn::mul(f, gfn::sub(0xFFFFFFFFull, sv));
-    return f;
-  };
+  auto filter = [&](int gi) { return selector_filter(a.g, cs, N, (uint32_t)gi); };
   if (g_const >= 0) {
     const uint64_t f = filter(g_const);
     acc0 = gfn::add(acc0, gfn::mul(f, sc0));
@@ -827,9 +846,7 @@ k_quotient_1r(QuotientArgs a) {
     acc0 = gfn::add(acc0, gfn::mul(f, A.sum0()));
     acc1 = gfn::add(acc1, gfn::mul(f, A.sum1()));
   }
-  const uint64_t zh_inv = a.zh_inv[j & ((1u << a.rate_bits) - 1)];
-  q[t] = gfn::canon(gfn::mul(acc0, zh_inv));
-  q[N + t] = gfn::canon(gfn::mul(acc1, zh_inv));
+  quotient_store(a, q, N, t, j, acc0, acc1, true);
 }
 
 // ---- per-gate form of the generic quotient (the default for gate lists
@@ -890,25 +907,20 @@ __global__ void __launch_bounds__(256) k_quotient_part(QuotientArgs a, uint32_t 
     acc1 = A.sum1();
   } else {
     const uint32_t kind = a.g.kind[gi];
-    const uint32_t si = a.g.sel_index[gi], nsel = a.g.nsel;
-    const uint64_t sv = cs[(uint64_t)si * N];
-    uint64_t f = 1;
-    for (uint32_t jj = a.g.grp_lo[si]; jj < a.g.grp_hi[si]; jj++)
-      if (jj != gi) f = gfn::mul(f, gfn::sub(jj, sv));
-    if (nsel > 1) f = gfn::mul(f, gfn::sub(0xFFFFFFFFull, sv));
+    const uint64_t f = selector_filter(a.g, cs, N, gi);
     A.i = 2 * (1 + nchunks);
-    const uint64_t *gc = cs + (uint64_t)nsel * N;
+    const uint64_t *gc = cs + (uint64_t)a.g.nsel * N;
     if constexpr (PART == 2) {
       poseidon_gate(wl, N, A);
     } else {
       switch (kind) {
-        case GK_CONSTANT:
+        case G_CONSTANT:
           for (uint32_t i = 0; i < a.g.param[gi]; i++) A.emit(gfn::sub(gc[(uint64_t)i * N], WV(i)));
           break;
-        case GK_PUBLIC_INPUT:
+        case G_PUBLIC_INPUT:
           for (uint32_t i = 0; i < 4; i++) A.emit(gfn::sub(WV(i), ch[CH_PIH + i]));
           break;
-        case GK_BASE_SUM: {
+        case G_BASE_SUM: {
           // each limb read once, high limb first in chunks: the sum by Horner
           // and the limb's boolean check at its own alpha index (i0 + 1 + i)
           const uint32_t L = a.g.param[gi], i0 = A.i;
@@ -934,7 +946,7 @@ __global__ void __launch_bounds__(256) k_quotient_part(QuotientArgs a, uint32_t 
           A.i = i0 + 1 + L;
           break;
         }
-        case GK_ARITHMETIC:
+        case G_ARITHMETIC:
           for (uint32_t i = 0; i < a.g.param[gi]; i++) {
             const uint64_t comp = gfn::add(gfn::mul(gfn::mul(WV(4 * i), WV(4 * i + 1)), gc[0]),
                                            gfn::mul(WV(4 * i + 2), gc[N]));
@@ -949,15 +961,7 @@ __global__ void __launch_bounds__(256) k_quotient_part(QuotientArgs a, uint32_t 
     acc0 = gfn::add(q[t], gfn::mul(f, A.sum0()));
     acc1 = gfn::add(q[N + t], gfn::mul(f, A.sum1()));
   }
-  if (last) {
-    const uint32_t j = gl::rev_bits(t, logN);
-    const uint64_t zh_inv = a.zh_inv[j & ((1u << a.rate_bits) - 1)];
-    q[t] = gfn::canon(gfn::mul(acc0, zh_inv));
-    q[N + t] = gfn::canon(gfn::mul(acc1, zh_inv));
-  } else {
-    q[t] = acc0;
-    q[N + t] = acc1;
-  }
+  quotient_store(a, q, N, t, gl::rev_bits(t, logN), acc0, acc1, last);
 }
 // ---- k_quotient_prefix: the permutation terms and every gate of gmask that
 // reads routed wires only (Constant, PublicInput, BaseSum, Arithmetic,
@@ -991,12 +995,12 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
   int gi_c = -1, gi_pi = -1, gi_bs = -1, gi_ar = -1, gi_ae = -1, gi_me = -1;
   for (uint32_t gi = 0; gi < a.g.ngates; gi++)
     if ((gmask >> gi) & 1) switch (a.g.kind[gi]) {
-        case GK_CONSTANT: gi_c = (int)gi; break;
-        case GK_PUBLIC_INPUT: gi_pi = (int)gi; break;
-        case GK_BASE_SUM: gi_bs = (int)gi; break;
-        case GK_ARITHMETIC: gi_ar = (int)gi; break;
-        case GK_ARITH_EXT: gi_ae = (int)gi; break;
-        case GK_MUL_EXT: gi_me = (int)gi; break;
+        case G_CONSTANT: gi_c = (int)gi; break;
+        case G_PUBLIC_INPUT: gi_pi = (int)gi; break;
+        case G_BASE_SUM: gi_bs = (int)gi; break;
+        case G_ARITHMETIC: gi_ar = (int)gi; break;
+        case G_ARITH_EXT: gi_ae = (int)gi; break;
+        case G_MUL_EXT: gi_me = (int)gi; break;
         default: break;
       }
   const uint32_t n_c = gi_c >= 0 ? a.g.param[gi_c] : 0, n_bs = gi_bs >= 0 ? a.g.param[gi_bs] : 0;
@@ -1010,16 +1014,7 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
     lz0.mac(term, p0[i]);
     lz1.mac(term, p1[i]);
   };
-  auto filter = [&](int gi) -> uint64_t {
-    if (gi < 0) return 0;
-    const uint32_t si = a.g.sel_index[gi];
-    const uint64_t sv = cs[(uint64_t)si * N];
-    uint64_t f = 1;
-    for (uint32_t jj = a.g.grp_lo[si]; jj < a.g.grp_hi[si]; jj++)
-      if (jj != (uint32_t)gi) f = gfn::mul(f, gfn::sub(jj, sv));
-    if (a.g.nsel > 1) f = gfn::mul(f, gfn::sub(0xFFFFFFFFull, sv));
-    return f;
-  };
+  auto filter = [&](int gi) -> uint64_t { return gi < 0 ? 0 : selector_filter(a.g, cs, N, (uint32_t)gi); };
   const uint64_t f_c = filter(gi_c), f_pi = filter(gi_pi), f_bs = filter(gi_bs), f_ar = filter(gi_ar),
                  f_ae = filter(gi_ae), f_me = filter(gi_me);
   const uint32_t jn = gl::rev_bits(t, logN);
@@ -1135,14 +1130,7 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
     acc0 = gfn::add(acc0, gfn::mul(f_bs, gfn::add(bss0, m0)));
     acc1 = gfn::add(acc1, gfn::mul(f_bs, gfn::add(bss1, m1)));
   }
-  if (last) {
-    const uint64_t zh_inv = a.zh_inv[jn & ((1u << a.rate_bits) - 1)];
-    q[t] = gfn::canon(gfn::mul(acc0, zh_inv));
-    q[N + t] = gfn::canon(gfn::mul(acc1, zh_inv));
-  } else {
-    q[t] = acc0;
-    q[N + t] = acc1;
-  }
+  quotient_store(a, q, N, t, jn, acc0, acc1, last);
 }
 template __global__ void k_quotient_prefix<8>(QuotientArgs, uint32_t, uint32_t);
 
@@ -1223,6 +1211,29 @@ __global__ void __launch_bounds__(256) k_qintt_radix(const uint64_t *__restrict_
   }
 }
 
+void quotient_zh(QuotientArgs &a, uint32_t log_n, uint32_t rate_bits) {
+  const uint64_t wN = gl::root_of_unity(log_n + rate_bits);
+  for (uint32_t k = 0; k < (1u << rate_bits); k++) {
+    const uint64_t xn = gl::pow(gl::mul(gl::GEN, gl::pow(wN, k)), 1ull << log_n);
+    a.zh[k] = gl::sub(xn, 1);
+    a.zh_inv[k] = gl::inv(a.zh[k]);
+  }
+}
+
+QuotientKernel quotient_kernel(const GateDesc &g, uint32_t R) {
+  if (path_opt("quotient_parts", 0)) return QK_PARTS;
+  uint32_t seen = 0;
+  for (uint32_t i = 0; i < g.ngates; i++) {
+    const uint32_t k = g.kind[i];
+    const bool swept = k == G_CONSTANT || k == G_PUBLIC_INPUT || k == G_BASE_SUM || k == G_ARITHMETIC;
+    if (!(k == G_NOOP || swept || k == G_POSEIDON || (k == G_RANDOM_ACCESS && g.param[i] == RA_QBITS)) ||
+        (seen >> k) & 1 || (swept && gate_shape(k, g.param[i]).wires > R))
+      return QK_PARTS;
+    seen |= 1u << k;
+  }
+  return QK_1R;
+}
+
 // ---- compute_quotient_polys as launches, shared by the prover's stage 3 and
 // the qp_quotient seam (any 2^6 <= n <= 2^15: the coset iNTT takes its LDS or
 // its large-n form by size)
@@ -1238,28 +1249,20 @@ void quotient_values(const QuotientArgs &a, QuotientKernel k, uint32_t nb, hipSt
       uint32_t gmask = 0;
       if (a.qdf == 8 && path_opt("qprefix", 1))
         for (uint32_t gi = 0; gi < a.g.ngates; gi++) {
-          const uint32_t p = a.g.param[gi];
-          uint64_t wires = ~0ull;
-          switch (a.g.kind[gi]) {
-            case GK_CONSTANT: wires = p <= 2 ? p : ~0ull; break;
-            case GK_PUBLIC_INPUT: wires = 4; break;
-            case GK_BASE_SUM: wires = 1ull + p; break;
-            case GK_ARITHMETIC: wires = 4ull * p; break;
-            case GK_ARITH_EXT: wires = 8ull * p; break;
-            case GK_MUL_EXT: wires = 6ull * p; break;
-            default: break;
-          }
-          if (wires <= a.R) gmask |= 1u << gi;
+          const uint32_t kind = a.g.kind[gi], p = a.g.param[gi];
+          const bool routed_only = (kind == G_CONSTANT && p <= 2) || kind == G_PUBLIC_INPUT || kind == G_BASE_SUM ||
+                                   kind == G_ARITHMETIC || kind == G_ARITH_EXT || kind == G_MUL_EXT;
+          if (routed_only && gate_shape(kind, p).wires <= a.R) gmask |= 1u << gi;
         }
       int lastg = -1;
       for (uint32_t gi = 0; gi < a.g.ngates; gi++)
-        if (a.g.kind[gi] != GK_NOOP && !((gmask >> gi) & 1)) lastg = (int)gi;
+        if (a.g.kind[gi] != G_NOOP && !((gmask >> gi) & 1)) lastg = (int)gi;
       if (gmask) k_quotient_prefix<8><<<qg, 256, 0, s>>>(a, gmask, lastg < 0);
       else k_quotient_part<0><<<qg, 256, 0, s>>>(a, 0, lastg < 0);
       for (uint32_t gi = 0; gi < a.g.ngates; gi++) {
-        if (a.g.kind[gi] == GK_NOOP || ((gmask >> gi) & 1)) continue;
+        if (a.g.kind[gi] == G_NOOP || ((gmask >> gi) & 1)) continue;
         const uint32_t l = (int)gi == lastg;
-        if (a.g.kind[gi] == GK_POSEIDON) k_quotient_part<2><<<qg, 256, 0, s>>>(a, gi, l);
+        if (a.g.kind[gi] == G_POSEIDON) k_quotient_part<2><<<qg, 256, 0, s>>>(a, gi, l);
         else k_quotient_part<1><<<qg, 256, 0, s>>>(a, gi, l);
       }
       break;
@@ -1576,6 +1579,16 @@ void fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab
     k_fri_leaf<<<dim3((unsigned)((nl + 255) / 256), nb), 256, 0, s>>>(vals, dig, log_len, ab, v_bstride, d_bstride);
 }
 
+void fri_layer_tree(const Twiddles &tw, const uint64_t *coef, uint64_t coef_cstride, uint64_t coef_bstride,
+                    uint32_t coef_log, uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint32_t cap_h,
+                    uint64_t shift, uint32_t nb, hipStream_t s) {
+  const uint64_t dbs = tree_digest_count(log_len - ab, cap_h) * 4;
+  lde(tw, coef, coef_cstride, vals, 1ull << log_len, 2, coef_log, log_len - coef_log, shift, nb, coef_bstride,
+      2ull << log_len, s);
+  fri_leaf(vals, dig, log_len, ab, 2ull << log_len, dbs, nb, s);
+  merkle_tree(dig, log_len - ab, cap_h, nb, dbs, s);
+}
+
 // fold: out[k] = sum_{i<2^ab} beta^i c[2^ab k + i]  (coefficients, ext as 2 columns).
 // Only the first 2^log_nz input coefficients can be nonzero (the layer-0
 // polynomial has degree < n in a length-N buffer): outputs past them are
@@ -1658,6 +1671,22 @@ __global__ void __launch_bounds__(256) k_pow_scan(const uint64_t *__restrict__ s
     }
   }
 }
+
+// 2048 workgroups claim 256-candidate blocks from per-proof counters, moving
+// on to the next proof once theirs has a hit below the claimed block (per-wave
+// claims and 2-4 candidates per thread measured no better:
+// profiles/r05_ab_pow_wave.log, r05_ab_pow_cpt.log; a windowed loop with a
+// host check per window was the round-1 form)
+hipError_t pow_search(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
+                      uint32_t bits, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(found, 0xFF, (size_t)nb * 8, s);
+  if (!e) e = hipMemsetAsync(next, 0, (size_t)nb * 8, s);
+  if (e) return e;
+  const uint64_t limit = 1ull << std::min<uint32_t>(bits + 20, 62);
+  k_pow_scan<<<2048, 256, 0, s>>>(states, pos, found, next, nb, bits, limit);
+  return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- gathers
 
 // out[b][q][c] = cols[b*bstride + c*stride + idx[b][q] >> shift]

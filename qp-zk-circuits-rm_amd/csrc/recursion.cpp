@@ -131,22 +131,14 @@ std::string parse_common(const uint8_t *b, size_t n, InnerCommon &c) {
   for (uint64_t i = 0; i < ngates; i++) {
     InnerCommon::Gate g{};
     g.id = r.u32();
-    switch (g.id) {
-      case 9: case 12: case 11: case 10: break;         // Noop, PublicInput, Poseidon, PoseidonMds
-      case 3: case 2: case 0:                           // Constant, BaseSum<2>, Arithmetic,
-      case 1: case 8: case 15: case 14:                 // ArithmeticExtension, MulExtension, Reducing(Extension)
-        g.p[0] = r.u64();
-        break;
-      case 13: g.p[0] = r.u64(); g.p[1] = r.u64(); g.p[2] = r.u64(); break;  // RandomAccess
-      case 4: {  // CosetInterpolation: subgroup_bits, degree, barycentric_weights
-        g.p[0] = r.u64();
-        g.p[1] = r.u64();
-        const uint64_t nw = r.u64();
-        if (g.p[0] > 6 || nw != (1ull << g.p[0]) || g.p[1] < 2) return "bad CosetInterpolationGate";
-        for (uint64_t i = 0; i < nw; i++) r.u64();
-        break;
-      }
-      default: return "unsupported gate (DefaultGateSerializer id " + std::to_string(g.id) + ") in the inner circuit";
+    g.kind = qc::kind_from_serial(g.id);
+    if (g.kind == qc::G_NKINDS || g.kind == qc::G_EXPONENTIATION)
+      return "unsupported gate (DefaultGateSerializer id " + std::to_string(g.id) + ") in the inner circuit";
+    for (uint32_t j = 0; j < qc::serial_params(g.kind); j++) g.p[j] = r.u64();
+    if (g.kind == qc::G_COSET_INTERP) {  // subgroup_bits, degree, then barycentric_weights
+      const uint64_t nw = r.u64();
+      if (g.p[0] > 6 || nw != (1ull << g.p[0]) || g.p[1] < 2) return "bad CosetInterpolationGate";
+      for (uint64_t i = 0; i < nw; i++) r.u64();
     }
     c.gates.push_back(g);
   }
@@ -155,9 +147,9 @@ std::string parse_common(const uint8_t *b, size_t n, InnerCommon &c) {
   if (c.selector_indices.size() != c.gates.size() || c.k_is.size() != c.num_routed_wires)
     return "inconsistent CommonCircuitData";
   for (auto &g : c.gates) {
-    if (g.id == 13 && (g.p[0] != qc::RA_BITS || g.p[1] != qc::RA_COPIES || g.p[2] != qc::RA_EXTRA))
+    if (g.kind == qc::G_RANDOM_ACCESS && (g.p[0] != qc::RA_BITS || g.p[1] != qc::RA_COPIES || g.p[2] != qc::RA_EXTRA))
       return "unsupported RandomAccessGate shape";
-    if (g.id == 4 && (g.p[0] != qc::CI_BITS || g.p[1] != qc::CI_DEGREE)) return "unsupported CosetInterpolationGate shape";
+    if (g.kind == qc::G_COSET_INTERP && (g.p[0] != qc::CI_BITS || g.p[1] != qc::CI_DEGREE)) return "unsupported CosetInterpolationGate shape";
   }
   return "";
 }

@@ -46,7 +46,8 @@ struct InnerCommon {
   std::vector<F> k_is;
   uint32_t num_partial_products = 0;
   struct Gate {
-    uint32_t id;    // DefaultGateSerializer tag
+    qc::GateKind kind;
+    uint32_t id;    // DefaultGateSerializer tag (error messages)
     uint64_t p[3];  // parameters in serialization order
   };
   std::vector<Gate> gates;

@@ -57,22 +57,7 @@ int qp_circuit_gate_desc(const qp_circuit *c, qp_gate_desc *g) {
   if (cd.gate_kinds.size() > QP_MAX_GATES || cd.groups.size() > QP_MAX_GATES) return QP_ERR_ARG;
   g->num_gates = (uint32_t)cd.gate_kinds.size();
   for (uint32_t i = 0; i < g->num_gates; i++) {
-    switch (cd.gate_kinds[i]) {
-      case qc::G_NOOP: g->kind[i] = QP_GATE_NOOP; break;
-      case qc::G_CONSTANT: g->kind[i] = QP_GATE_CONSTANT; break;
-      case qc::G_PUBLIC_INPUT: g->kind[i] = QP_GATE_PUBLIC_INPUT; break;
-      case qc::G_BASE_SUM: g->kind[i] = QP_GATE_BASE_SUM; break;
-      case qc::G_ARITHMETIC: g->kind[i] = QP_GATE_ARITHMETIC; break;
-      case qc::G_POSEIDON: g->kind[i] = QP_GATE_POSEIDON; break;
-      case qc::G_RANDOM_ACCESS: g->kind[i] = QP_GATE_RANDOM_ACCESS; break;
-      case qc::G_ARITH_EXT: g->kind[i] = QP_GATE_ARITHMETIC_EXTENSION; break;
-      case qc::G_MUL_EXT: g->kind[i] = QP_GATE_MUL_EXTENSION; break;
-      case qc::G_REDUCING: g->kind[i] = QP_GATE_REDUCING; break;
-      case qc::G_REDUCING_EXT: g->kind[i] = QP_GATE_REDUCING_EXTENSION; break;
-      case qc::G_POSEIDON_MDS: g->kind[i] = QP_GATE_POSEIDON_MDS; break;
-      case qc::G_COSET_INTERP: g->kind[i] = QP_GATE_COSET_INTERPOLATION; break;
-      default: return QP_ERR_ARG;
-    }
+    g->kind[i] = cd.gate_kinds[i];
     g->param[i] = cd.gate_params[i];
     g->param2[i] = i < cd.gate_params2.size() ? cd.gate_params2[i] : 0;
     g->param3[i] = i < cd.gate_params3.size() ? cd.gate_params3[i] : 0;
@@ -121,54 +106,19 @@ int qp_quotient(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp
       ctx->err = "qp_quotient: selector group " + std::to_string(s) + " out of range";
       return QP_ERR_ARG;
     }
-  bool fast = g->num_gates <= 8 && !qpk::path_opt("quotient_parts", 0);
-  uint32_t seen = 0;
   for (uint32_t i = 0; i < g->num_gates; i++) {
-    const uint32_t k = g->kind[i], p = g->param[i], p2 = g->param2[i], p3 = g->param3[i];
-    uint64_t wires_used = 0, consts_used = 0, ncons = 0;
+    const uint32_t k = g->kind[i];
+    const qg::GateShape sh = qg::gate_shape(k, g->param[i], g->param2[i], g->param3[i]);
     // plonky2 places each gate in the selector group it belongs to
-    bool ok = g->selector_index[i] < g->num_selectors && g->group_lo[g->selector_index[i]] <= i &&
-              i < g->group_hi[g->selector_index[i]];
-    switch (k) {
-      case QP_GATE_NOOP: break;
-      case QP_GATE_CONSTANT: wires_used = p; consts_used = p; ncons = p; break;
-      case QP_GATE_PUBLIC_INPUT: wires_used = 4; ncons = 4; break;
-      case QP_GATE_BASE_SUM: wires_used = 1ull + p; ncons = 1ull + p; break;
-      case QP_GATE_ARITHMETIC: wires_used = 4ull * p; consts_used = 2; ncons = p; break;
-      case QP_GATE_POSEIDON: wires_used = 135; ncons = 123; break;
-      case QP_GATE_ARITHMETIC_EXTENSION: wires_used = 8ull * p; consts_used = 2; ncons = 2ull * p; break;
-      case QP_GATE_MUL_EXTENSION: wires_used = 6ull * p; consts_used = 1; ncons = 2ull * p; break;
-      case QP_GATE_RANDOM_ACCESS:
-        ok = ok && p >= 1 && p <= 6;
-        wires_used = (2ull + (1ull << (p & 63))) * p2 + p3 + (uint64_t)p2 * p;
-        consts_used = p3;
-        ncons = (p + 2ull) * p2 + p3;
-        break;
-      case QP_GATE_EXPONENTIATION: ok = ok && p >= 1; wires_used = 2ull + 2ull * p; ncons = p + 1ull; break;
-      case QP_GATE_REDUCING: ok = ok && p >= 1; wires_used = 6ull + p + 2ull * (p - 1); ncons = 2ull * p; break;
-      case QP_GATE_REDUCING_EXTENSION:
-        ok = ok && p >= 1;
-        wires_used = 6ull + 2ull * p + 2ull * (p - 1);
-        ncons = 2ull * p;
-        break;
-      case QP_GATE_POSEIDON_MDS: wires_used = 48; ncons = 24; break;
-      case QP_GATE_COSET_INTERPOLATION: {
-        ok = ok && p >= 2 && p <= 6 && p2 >= 2 && p2 <= (1u << p);
-        const uint64_t np = 1ull << (p & 63), nint = ok ? (np - 2) / (p2 - 1) : 0;
-        wires_used = 1 + 2 * np + 4 + 4 * nint + 2;
-        ncons = 4 + 4 * nint;
-        break;
-      }
-      default: ok = false; break;
-    }
-    if (!ok || wires_used > W || consts_used > n_gc || ncons > g->num_gate_constraints) {
+    const bool placed = g->selector_index[i] < g->num_selectors && g->group_lo[g->selector_index[i]] <= i &&
+                        i < g->group_hi[g->selector_index[i]];
+    // the kernels' Reducing gates take the last accumulator from wires 0..1: at least one coefficient
+    const bool no_coeffs = (k == qg::G_REDUCING || k == qg::G_REDUCING_EXT) && g->param[i] < 1;
+    if (!placed || !sh.ok || no_coeffs || sh.wires > W || sh.consts > n_gc ||
+        sh.constraints > g->num_gate_constraints) {
       ctx->err = "qp_quotient: gate " + std::to_string(i) + ": unknown gate kind, selector or parameters";
       return QP_ERR_ARG;
     }
-    // the single-read kernel: the six leaf-circuit kinds, each at most once, the
-    // non-Poseidon ones inside the routed wires it sweeps
-    if (k > QP_GATE_POSEIDON || (seen >> k) & 1 || (k != QP_GATE_POSEIDON && wires_used > R)) fast = false;
-    seen |= 1u << k;
   }
   const uint64_t n = 1ull << log_n, N = 1ull << logN;
   QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -207,13 +157,7 @@ int qp_quotient(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp
     a.apow = d_apow.p;
     a.xtab = d_tab.p;
     a.l0tab = d_tab.p + N;
-    const uint32_t B = 1u << rb;
-    const uint64_t wN = gl::root_of_unity(logN);
-    for (uint32_t k = 0; k < B; k++) {
-      const uint64_t xn = gl::pow(gl::mul(gl::GEN, gl::pow(wN, k)), n);
-      a.zh[k] = gl::sub(xn, 1);
-      a.zh_inv[k] = gl::inv(a.zh[k]);
-    }
+    qpk::quotient_zh(a, log_n, rb);
     a.q_out = d_q.p;
     a.q_bstride = 2 * N;
     a.log_n = log_n;
@@ -221,23 +165,10 @@ int qp_quotient(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp
     a.R = R;
     a.qdf = qdf;
     a.num_constants = g->num_constants;
-    a.g.ngates = g->num_gates;
-    a.g.nsel = g->num_selectors;
-    for (uint32_t i = 0; i < g->num_gates; i++) {
-      a.g.kind[i] = g->kind[i];
-      a.g.param[i] = g->param[i];
-      a.g.param2[i] = g->param2[i];
-      a.g.param3[i] = g->param3[i];
-      a.g.sel_index[i] = g->selector_index[i];
-    }
-    for (uint32_t i = 0; i < g->num_selectors; i++) {
-      a.g.grp_lo[i] = g->group_lo[i];
-      a.g.grp_hi[i] = g->group_hi[i];
-    }
+    a.g = qpk::gate_desc_dev(*g);
     // the prover's kernels: the single-read one for the leaf gate set, else
     // the permutation terms and one launch per gate
-    const qpk::QuotientKernel qk = fast ? qpk::QK_1R : qpk::QK_PARTS;
-    qpk::quotient_values(a, qk, 1, s);
+    qpk::quotient_values(a, qpk::quotient_kernel(a.g, R), 1, s);
     qpk::quotient_coeffs(ctx->tw, d_q.p, d_cbuf.p, d_out.p, log_n, rb, nc, 1, 2 * N, 2 * N, (uint64_t)nc * qdf * n, s);
     QP_HIP_TRY(ctx, hipGetLastError());
     QP_HIP_TRY(ctx, hipMemcpyAsync(quotient_coeffs_out, d_out.p, (uint64_t)nc * qdf * n * 8, hipMemcpyDeviceToHost, s));
@@ -296,10 +227,9 @@ int qp_fri_layer_commit(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs
   }
   e = hipMemcpy2DAsync(d_c.p, Lc * 8, coeffs, Lin * 8, Lc * 8, 2, hipMemcpyHostToDevice, s);
   if (!e) {
-    // values = coset_fft(coeffs, shift), leaf (bit-reversed) order
-    qpk::lde(ctx->tw, d_c.p, Lc, L->d_vals, Lv, 2, lc, log_values - lc, shift, 1, 2 * Lc, 2 * Lv, s);
-    qpk::fri_leaf(L->d_vals, L->d_dig, log_values, arity_bits, 2 * Lv, dbs, 1, s);
-    qpk::merkle_tree(L->d_dig, log_leaves, cap_height, 1, dbs, s);
+    // values = coset_fft(coeffs, shift), leaf (bit-reversed) order, and their tree
+    qpk::fri_layer_tree(ctx->tw, d_c.p, Lc, 2 * Lc, lc, L->d_vals, L->d_dig, log_values, arity_bits, cap_height, shift,
+                        1, s);
     e = hipGetLastError();
   }
   if (!e)
@@ -398,12 +328,8 @@ int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint3
     QP_HIP_TRY(ctx, d_found.alloc(n));
     QP_HIP_TRY(ctx, hipMemcpyAsync(d_pre.p, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, s));
     QP_HIP_TRY(ctx, hipMemcpyAsync(d_pos.p, pos, n * 4ull, hipMemcpyHostToDevice, s));
-    QP_HIP_TRY(ctx, hipMemsetAsync(d_found.p, 0xFF, n * 8ull, s));
-    QP_HIP_TRY(ctx, hipMemsetAsync(d_next.p, 0, n * 8ull, s));
     // the prover's single-launch minimal-witness search (prover.cpp stage 6)
-    const uint64_t limit = 1ull << std::min<uint32_t>(pow_bits + 20, 62);
-    qpk::k_pow_scan<<<2048, 256, 0, s>>>(d_pre.p, (const uint32_t *)d_pos.p, d_found.p, d_next.p, n, pow_bits, limit);
-    QP_HIP_TRY(ctx, hipGetLastError());
+    QP_HIP_TRY(ctx, qpk::pow_search(d_pre.p, (const uint32_t *)d_pos.p, d_found.p, d_next.p, n, pow_bits, s));
     QP_HIP_TRY(ctx, hipMemcpyAsync(found.data(), d_found.p, n * 8ull, hipMemcpyDeviceToHost, s));
     QP_HIP_TRY(ctx, hipStreamSynchronize(s));
     for (uint32_t b = 0; b < n; b++)

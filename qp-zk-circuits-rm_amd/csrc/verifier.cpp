@@ -73,40 +73,6 @@ struct VG : qr::AlgOps<VG, gl::ext> {
   E exp_u64(E x, uint64_t e) { return gl::ext_pow(x, e); }
 };
 
-// wires, gate constants and constraints a gate reads / produces (bounds for
-// the evaluator's indexing, checked once in qp_verifier_new)
-void gate_needs(const InnerCommon::Gate &g, uint64_t &wires, uint64_t &consts, uint64_t &cons) {
-  const uint64_t n = g.p[0];
-  wires = consts = cons = 0;
-  switch (g.id) {
-    case 9: break;
-    case 3: wires = consts = cons = n; break;
-    case 12: wires = cons = 4; break;
-    case 2: wires = cons = 1 + n; break;
-    case 0: wires = 4 * n; consts = 2; cons = n; break;
-    case 1: wires = 8 * n; consts = 2; cons = 2 * n; break;
-    case 8: wires = 6 * n; consts = 1; cons = 2 * n; break;
-    case 15: wires = 6 + n + 2 * (n ? n - 1 : 0); cons = 2 * n; break;
-    case 14: wires = 6 + 2 * n + 2 * (n ? n - 1 : 0); cons = 2 * n; break;
-    case 10: wires = 48; cons = 24; break;
-    case 4: {
-      const uint64_t np = 1ull << g.p[0], nint = (np - 2) / (g.p[1] - 1);
-      wires = 1 + 2 * np + 4 + 4 * nint + 2;
-      cons = 4 + 4 * nint;
-      break;
-    }
-    case 13: {
-      const uint64_t vec = 1ull << g.p[0];
-      wires = (2 + vec) * g.p[1] + g.p[2] + g.p[1] * g.p[0];
-      consts = g.p[2];
-      cons = g.p[1] * (g.p[0] + 2) + g.p[2];
-      break;
-    }
-    case 11: wires = 135; cons = 123; break;
-    default: wires = ~0ull; break;
-  }
-}
-
 struct Dims {
   uint32_t log_n, log_N, cap_h, capw, nq, nc, salt, nlayers, final_len, ncls, init_sibs;
   uint32_t width[4], unsalted[4];
@@ -235,13 +201,14 @@ std::string check_supported(const InnerCommon &c, Dims &d) {
   // the gates' reads stay inside the openings
   const uint32_t nsel = (uint32_t)c.groups.size();
   for (size_t gi = 0; gi < c.gates.size(); gi++) {
-    uint64_t w, k, n;
-    // a parameter is a raw u64 of the common data: bound it before gate_needs multiplies it
+    // a parameter is a raw u64 of the common data: bound it before gate_shape multiplies it
     for (uint64_t prm : c.gates[gi].p)
       if (prm > c.num_wires)
         return "gate " + std::to_string(gi) + " (id " + std::to_string(c.gates[gi].id) + "): parameter exceeds the wire count";
-    gate_needs(c.gates[gi], w, k, n);
-    if (w > c.num_wires || k > c.num_constants - nsel || n > c.num_gate_constraints)
+    // (zero Reducing coefficients pass here, as upstream's from_bytes takes them)
+    const qg::GateShape sh = qg::gate_shape(c.gates[gi].kind, c.gates[gi].p[0], c.gates[gi].p[1], c.gates[gi].p[2]);
+    if (!sh.ok || sh.wires > c.num_wires || sh.consts > c.num_constants - nsel ||
+        sh.constraints > c.num_gate_constraints)
       return "gate " + std::to_string(gi) + " (id " + std::to_string(c.gates[gi].id) + ") exceeds the circuit's wires, constants or constraints";
     if (c.selector_indices[gi] >= nsel) return "selector index out of range";
   }

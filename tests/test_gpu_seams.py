@@ -40,6 +40,20 @@ def test_gate_desc_matches_common_data(circuit):
     assert g.num_constants == circuit.num_constants
     assert g.num_gate_constraints == circuit.num_gate_constraints
     assert g.quotient_degree_factor == 8 and g.num_challenges == 2
+    # a level-1 aggregation circuit: every kind the builder emits, in CommonCircuitData.gates order
+    from test_oracle_golden import current_common_bytes
+    agg = qp_wormhole.Circuit.aggregation(current_common_bytes(), 2)
+    g = qp_wormhole.gate_desc(agg)
+    kinds = ["noop", "constant", "poseidon_mds", "public_input", "base_sum", "reducing_extension", "reducing",
+             "arithmetic_extension", "arithmetic", "mul_extension", "random_access", "coset_interpolation", "poseidon"]
+    params = [(0, 0, 0), (2, 0, 0), (0, 0, 0), (0, 0, 0), (63, 0, 0), (32, 0, 0), (43, 0, 0), (10, 0, 0), (20, 0, 0),
+              (13, 0, 0), (4, 4, 2), (4, 6, 0), (0, 0, 0)]
+    assert g.num_gates == 13 and [qp_wormhole._native.GATE_KINDS[k] for k in list(g.kind)[:13]] == kinds
+    assert list(zip(g.param, g.param2, g.param3))[:13] == params
+    assert list(g.selector_index)[:13] == [0] * 7 + [1] * 4 + [2] * 2 and g.num_selectors == 3
+    assert [(g.group_lo[i], g.group_hi[i]) for i in range(3)] == [(0, 7), (7, 11), (11, 13)]
+    assert (g.num_wires, g.num_routed_wires, g.num_constants, g.num_gate_constraints) == (135, 80, 5, 123)
+    assert g.quotient_degree_factor == 8 and g.num_challenges == 2
 
 
 @pytest.fixture(scope="module")
@@ -125,6 +139,38 @@ def test_quotient_recursion_gate_set_matches_oracle(ctx, log_n):
     assert olib().ora_quotient_desc(ctypes.addressof(g), log_n, 3, cs, wires, zs, betas, gammas, alphas, pih,
                                     want) == 0
     assert (got == want).all(), np.argwhere(got != want)[:4]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("log_n", [6, 8])
+def test_quotient_random_access_single_read_matches_oracle(ctx, log_n, monkeypatch):
+    """The leaf gates with a RandomAccess gate of the width the single-read
+    kernel evaluates and no extension gate: qp_quotient takes that kernel, as the
+    prover does for such a circuit.  Against the descriptor-driven oracle, and
+    word for word against the per-gate launches (quotient_parts=1)."""
+    import ctypes
+
+    import qp_wormhole
+    gates = [("noop", (), 0), ("constant", (2,), 0), ("public_input", (), 0), ("base_sum", (63,), 0),
+             ("arithmetic", (20,), 0), ("random_access", (4, 4, 2), 1), ("poseidon", (), 1)]
+    g = qp_wormhole.GateDesc.build(gates, [(0, 5), (5, 7)], num_gate_constraints=123)
+    rng = np.random.default_rng(100 + log_n)
+    n = 1 << log_n
+    cs = rand_felts(rng, g.num_constants + 80, n)
+    wires = rand_felts(rng, 135, n)
+    zs = rand_felts(rng, 20, n)
+    betas, gammas, alphas, pih = rand_felts(rng, 2), rand_felts(rng, 2), rand_felts(rng, 2), rand_felts(rng, 4)
+    B = [qp_wormhole.PolynomialBatch.from_values(ctx, v, 3, 4) for v in (cs, wires, zs)]
+    got = qp_wormhole.quotient(ctx, B[0], B[1], B[2], g, betas, gammas, alphas, pih)
+    want = np.zeros_like(got)
+    assert olib().ora_quotient_desc(ctypes.addressof(g), log_n, 3, cs, wires, zs, betas, gammas, alphas, pih,
+                                    want) == 0
+    assert (got == want).all(), np.argwhere(got != want)[:4]
+    monkeypatch.setenv("QPGPU_PATHS", "quotient_parts=1")
+    parts = qp_wormhole.quotient(ctx, B[0], B[1], B[2], g, betas, gammas, alphas, pih)
+    assert (got == parts).all(), np.argwhere(got != parts)[:4]
+    for b in B:
+        b.free()
 
 
 EDGE_CHALLENGES = [(P - 1, P - 1), (0, 1), (2**32 - 1, P - 2**32)]
