@@ -456,6 +456,58 @@ int qp_fri_fold(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs, uint32
 int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint32_t n, uint32_t pow_bits,
                  uint64_t *witness_out);
 
+/* The three polynomial stages between the commitments (the whole-circuit
+ * prover's stages 2, 4 and 5 for one proof of any circuit).  Limits of the
+ * circuit-level calls (qp_partial_products_and_zs, qp_opening_set,
+ * qp_fri_initial_poly): 2^6 <= degree <= 2^15 (qp_quotient's), 1 or 2
+ * challenges, batches of one context and one log_n, unsalted, of one proof. */
+
+/* permutation data of a circuit, uploaded once (the sigmas and k_is of
+ * ProverOnlyCircuitData / CommonCircuitData):
+ * sigmas: values over H, column-major [num_routed][2^log_n] (the sigma columns of
+ * constants||sigmas); k_is [num_routed].  1 <= num_routed <= 256.  A qp_perm
+ * uses its context: free it before qp_ctx_destroy.                          */
+typedef struct qp_perm qp_perm;
+int qp_perm_new(qp_ctx *ctx, const uint64_t *sigmas, const uint64_t *k_is, uint32_t num_routed,
+                uint32_t log_n, qp_perm **out);
+void qp_perm_free(qp_perm *p);
+
+/* wires_permutation_partial_products_and_zs (plonk/prover.rs), reached from
+ * CircuitData::prove (tree.rs:136, lib.rs:233-237) after the wires commitment.
+ * wires: values over H, column-major, column stride 2^log_n; the first num_routed columns are read.
+ * zs_pp_out [num_challenges * nchunks][2^log_n], nchunks = ceil(num_routed / quotient_degree_factor)
+ * <= 16, in the order prove() commits them (all Zs, then the partial products per challenge): what
+ * qp_commit_values takes next and what qp_quotient expects as zs_pp.  beta = 0 is legal.  A zero
+ * denominator w + beta sigma + gamma (plonky2 panics in its batch inversion; probability about
+ * num_routed * n / p per challenge for transcript-drawn challenges) is not detected, as in the
+ * whole-circuit prover: its row quotient comes out as 0.                                         */
+int qp_partial_products_and_zs(qp_perm *p, const uint64_t *wires, uint32_t quotient_degree_factor,
+                               const uint64_t *betas, const uint64_t *gammas, uint32_t num_challenges,
+                               uint64_t *zs_pp_out);
+
+/* OpeningSet::new (plonk/proof.rs), reached from CircuitData::prove after zeta is drawn:
+ * every polynomial of the four committed batches at zeta, in oracle order (constants||sigmas, wires,
+ * Zs||partial products, quotient chunks), then the first num_challenges polynomials of zs_pp (the Zs)
+ * at g*zeta: out [(sum of npolys) + num_challenges][2], at most 260 extension values (a
+ * standard-config circuit has 257).  One launch (+ the slice reduction), one copy back.
+ * zeta != 0 and zeta^n != 1 (plonky2's prover refuses the latter too).                           */
+int qp_opening_set(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp_batch *zs_pp,
+                   const qp_batch *quotient, uint32_t num_challenges, const uint64_t zeta[2], uint64_t *out);
+/* the general form: polynomials [first, first + npolys) of one batch (of one proof, any log_n
+ * qp_commit_values accepts) at npts extension points, out [npts][npolys][2], npts * npolys <= 2^20.
+ * For other opening schedules and as the small-shape test surface.                               */
+int qp_batch_eval_ext(const qp_batch *b, uint32_t first, uint32_t npolys, const uint64_t *points,
+                      uint32_t npts, uint64_t *out);
+
+/* the initial polynomial of PolynomialBatch::prove_openings (fri/oracle.rs), reached from
+ * CircuitData::prove after the openings are observed and the FRI alpha is drawn:
+ * alpha-reduce the zeta batch and the g*zeta batch, divide each by (X - point), combine as plonky2 does
+ * (what stage 5 of the whole-circuit prover computes): coeffs_out [2][2^log_n] (c0 row, c1 row), the
+ * layout qp_fri_layer_commit takes with log_coeffs = log_n.  zeta != 0 and zeta^n != 1.           */
+int qp_fri_initial_poly(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp_batch *zs_pp,
+                        const qp_batch *quotient, uint32_t num_challenges, const uint64_t alpha[2],
+                        const uint64_t zeta[2], uint64_t *coeffs_out);
+
 /* ---- batch proof verifier (plonky2 VerifierCircuitData::verify; the
  * reference's qp-wormhole-verifier, wormhole/verifier/src/lib.rs) ----------
  * Per proof the host parses, replays the transcript and checks the vanishing

@@ -7,6 +7,9 @@
 //   qp_fri_layer_commit  fri/prover.rs fri_committed_trees, one reduction layer
 //   qp_fri_fold          the same loop's coefficient fold with beta
 //   qp_pow_grind         fri/prover.rs fri_proof_of_work (minimal witness)
+//   qp_partial_products_and_zs  plonk/prover.rs wires_permutation_partial_products_and_zs
+//   qp_opening_set / qp_batch_eval_ext  plonk/proof.rs OpeningSet::new
+//   qp_fri_initial_poly  fri/oracle.rs PolynomialBatch::prove_openings, the polynomial FRI starts from
 // The transcript stays with the caller: each seam consumes the challenges the
 // caller's Challenger drew and returns what it must observe next.
 #include <stdlib.h>
@@ -35,7 +38,66 @@ struct DMem {  // device allocation owned by one call
 
 inline unsigned cdiv(uint64_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }
 
+// degrees of the circuit-level seams (qp_quotient's): k_fri_divide runs n / 8
+// threads and holds at most 64 values per thread, k_z_scan has its two forms
+constexpr uint32_t SEAM_LOG_MIN = 6, SEAM_LOG_MAX = qpk::BIG_LOG_MAX - 1;
+constexpr uint32_t PP_MAX_CHUNKS = 16;  // k_pp_rows' per-row chunk arrays
+
+// zeta, g*zeta and their inverses: the opening words of a one-proof challenge block
+struct OpenPoint {
+  gl::ext z, zn, zi, zni;
+  void fill(uint64_t *ch) const {
+    ch[qpk::CH_ZETA] = z.c0; ch[qpk::CH_ZETA + 1] = z.c1;
+    ch[qpk::CH_ZETA_NEXT] = zn.c0; ch[qpk::CH_ZETA_NEXT + 1] = zn.c1;
+    ch[qpk::CH_ZETA_INV] = zi.c0; ch[qpk::CH_ZETA_INV + 1] = zi.c1;
+    ch[qpk::CH_ZETA_NEXT_INV] = zni.c0; ch[qpk::CH_ZETA_NEXT_INV + 1] = zni.c1;
+  }
+};
+
+// the shared preconditions of qp_opening_set and qp_fri_initial_poly: four
+// batches (constants||sigmas, wires, Zs||partial products, quotient) of ctx,
+// of one proof, unsalted, holding coefficients of one degree 2^6..2^15; 1 or 2
+// challenges with their Zs present; zeta invertible and outside H
+int check_circuit_batches(qp_ctx *ctx, const char *fn, const qp_batch *const bt[4], uint32_t nc,
+                          const uint64_t *zeta, const void *out, OpenPoint *pt) {
+  auto fail = [&](const char *why) {
+    ctx->err = std::string(fn) + ": " + why;
+    return (int)QP_ERR_ARG;
+  };
+  if (!bt[0] || !bt[1] || !bt[2] || !bt[3] || !zeta || !out) return fail("null argument");
+  const uint32_t log_n = bt[0]->log_n;
+  for (int i = 0; i < 4; i++) {
+    if (bt[i]->ctx != ctx) return fail("a batch belongs to another context");
+    if (bt[i]->log_n != log_n) return fail("the batches differ in log_n");
+    if (bt[i]->nbat != 1 || bt[i]->nsalt) return fail("needs unsalted batches of one proof");
+    if (!bt[i]->d_coeffs || !bt[i]->npolys) return fail("a batch holds no coefficients");
+  }
+  if (log_n < SEAM_LOG_MIN || log_n > SEAM_LOG_MAX) return fail("unsupported degree (2^6 <= n <= 2^15)");
+  if (nc < 1 || nc > 2) return fail("num_challenges must be 1 or 2");
+  if (bt[2]->npolys < nc) return fail("zs_pp holds fewer polynomials than challenges");
+  const gl::ext z{gl::canon(zeta[0]), gl::canon(zeta[1])};
+  if (!(z.c0 | z.c1)) return fail("zeta = 0");
+  const gl::ext zn_pow = gl::ext_pow(z, 1ull << log_n);
+  if (zn_pow.c0 == 1 && zn_pow.c1 == 0) return fail("zeta^n = 1 (an opening point inside the subgroup)");
+  pt->z = z;
+  pt->zn = gl::ext_scale(z, gl::root_of_unity(log_n));
+  pt->zi = gl::ext_inv(z);
+  pt->zni = gl::ext_inv(pt->zn);
+  return QP_OK;
+}
+
 }  // namespace
+
+struct qp_perm {
+  qp_ctx *ctx = nullptr;
+  uint32_t R = 0, log_n = 0;
+  uint64_t *d_sigmas = nullptr;  // [R][n] values over H
+  uint64_t *d_kis = nullptr;     // [R]
+  ~qp_perm() {
+    if (d_sigmas) (void)hipFree(d_sigmas);
+    if (d_kis) (void)hipFree(d_kis);
+  }
+};
 
 struct qp_fri_layer {
   qp_ctx *ctx = nullptr;
@@ -341,6 +403,256 @@ int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint3
   } catch (const std::bad_alloc &) {
     return QP_ERR_OOM;
   }
+  return QP_OK;
+}
+
+// ---- partial products / Z, the opening set, the initial FRI polynomial ------
+// The whole-circuit prover's stages 2, 4 and 5 (prover.cpp) for one proof of
+// any circuit: the same kernels, reading a one-proof challenge block
+// (CHAL_STRIDE words, proof index 0) that the seam fills from its arguments.
+// Every precondition the kernels assume is checked here before a launch.
+
+int qp_perm_new(qp_ctx *ctx, const uint64_t *sigmas, const uint64_t *k_is, uint32_t num_routed, uint32_t log_n,
+                qp_perm **out) {
+  if (!ctx || !out) return QP_ERR_ARG;
+  *out = nullptr;
+  if (!sigmas || !k_is) {
+    ctx->err = "qp_perm_new: null argument";
+    return QP_ERR_ARG;
+  }
+  if (log_n < SEAM_LOG_MIN || log_n > SEAM_LOG_MAX || num_routed < 1 || num_routed > 16 * PP_MAX_CHUNKS) {
+    ctx->err = "qp_perm_new: unsupported shape (2^6 <= n <= 2^15, 1 <= num_routed <= 256)";
+    return QP_ERR_ARG;
+  }
+  QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  qp_perm *p = new (std::nothrow) qp_perm();
+  if (!p) return QP_ERR_OOM;
+  p->ctx = ctx;
+  p->R = num_routed;
+  p->log_n = log_n;
+  const uint64_t n = 1ull << log_n;
+  std::vector<uint64_t> k(num_routed);
+  for (uint32_t j = 0; j < num_routed; j++) k[j] = gl::canon(k_is[j]);
+  hipError_t e = hipMalloc(&p->d_sigmas, (size_t)num_routed * n * 8);
+  if (!e) e = hipMalloc(&p->d_kis, (size_t)num_routed * 8);
+  if (!e) e = hipMemcpyAsync(p->d_sigmas, sigmas, (size_t)num_routed * n * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (!e) e = hipMemcpyAsync(p->d_kis, k.data(), (size_t)num_routed * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (!e) e = hipStreamSynchronize(ctx->stream);
+  if (e) {
+    delete p;
+    ctx->err = std::string("qp_perm_new: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? QP_ERR_OOM : QP_ERR_HIP;
+  }
+  *out = p;
+  return QP_OK;
+}
+
+void qp_perm_free(qp_perm *p) { delete p; }
+
+int qp_partial_products_and_zs(qp_perm *p, const uint64_t *wires, uint32_t qdf, const uint64_t *betas,
+                               const uint64_t *gammas, uint32_t nc, uint64_t *zs_pp_out) {
+  if (!p) return QP_ERR_ARG;
+  qp_ctx *ctx = p->ctx;
+  if (!wires || !betas || !gammas || !zs_pp_out) {
+    ctx->err = "qp_partial_products_and_zs: null argument";
+    return QP_ERR_ARG;
+  }
+  const uint32_t R = p->R, log_n = p->log_n;
+  const uint32_t nchunks = qdf ? (R + qdf - 1) / qdf : 0;
+  // k_pp_rows keeps PP_MAX_CHUNKS chunk products per row; the challenge block holds two challenges
+  if (nc < 1 || nc > 2 || qdf < 1 || nchunks > PP_MAX_CHUNKS) {
+    ctx->err = "qp_partial_products_and_zs: unsupported shape (1 or 2 challenges, at most 16 chunks of quotient_degree_factor)";
+    return QP_ERR_ARG;
+  }
+  const uint64_t n = 1ull << log_n, pbs = (uint64_t)nc * nchunks * n;
+  QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
+  for (uint32_t c = 0; c < nc; c++) {
+    chal[qpk::CH_BETA + c] = gl::canon(betas[c]);
+    chal[qpk::CH_GAMMA + c] = gl::canon(gammas[c]);
+  }
+  qpk::perm_challenges(chal.data(), chal.data() + qpk::CH_BETA, chal.data() + qpk::CH_GAMMA, nc, R, qdf);
+  DMem d_w, d_prods, d_zs, d_chal;
+  QP_HIP_TRY(ctx, d_w.alloc((uint64_t)R * n));
+  QP_HIP_TRY(ctx, d_prods.alloc(pbs));
+  QP_HIP_TRY(ctx, d_zs.alloc(pbs));
+  QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
+  QP_HIP_TRY(ctx, hipMemcpyAsync(d_w.p, wires, (uint64_t)R * n * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(ctx, hipMemcpyAsync(d_chal.p, chal.data(), chal.size() * 8, hipMemcpyHostToDevice, s));
+  // prover.cpp stage 2: the leaf circuits' shape takes the compile-time kernel
+  if (R == 80 && qdf == 8 && nc == 2)
+    qpk::k_pp_rows_t<80, 8><<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(d_w.p, p->d_sigmas, p->d_kis, d_chal.p, d_prods.p,
+                                                                   log_n, 0, 0, ctx->tw.fwd);
+  else
+    qpk::k_pp_rows<<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(d_w.p, p->d_sigmas, p->d_kis, d_chal.p, d_prods.p, log_n, R,
+                                                          qdf, nc, 0, 0, ctx->tw.fwd);
+  if (log_n <= qpk::LDS_LOG_MAX)
+    qpk::k_z_scan<true><<<dim3(nc, 1), 1024, 8u * (qpk::ntt_lds_words(n) + 1024), s>>>(d_prods.p, d_zs.p, log_n, nc,
+                                                                                         nchunks, 0, 0);
+  else
+    qpk::k_z_scan<false><<<dim3(nc, 1), 1024, 8u * 1024, s>>>(d_prods.p, d_zs.p, log_n, nc, nchunks, 0, 0);
+  QP_HIP_TRY(ctx, hipGetLastError());
+  QP_HIP_TRY(ctx, hipMemcpyAsync(zs_pp_out, d_zs.p, pbs * 8, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(ctx, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_opening_set(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp_batch *zs_pp,
+                   const qp_batch *quotient, uint32_t nc, const uint64_t zeta[2], uint64_t *out) {
+  if (!ctx) return QP_ERR_ARG;
+  const qp_batch *bt[4] = {cs, wires, zs_pp, quotient};
+  OpenPoint pt;
+  int rc = check_circuit_batches(ctx, "qp_opening_set", bt, nc, zeta, out, &pt);
+  if (rc) return rc;
+  const uint32_t log_n = cs->log_n;
+  const uint64_t total = (uint64_t)cs->npolys + wires->npolys + zs_pp->npolys + quotient->npolys + nc;
+  if (2 * total > qpk::OPEN_STRIDE) {
+    ctx->err = "qp_opening_set: more than 260 openings (use qp_batch_eval_ext per batch)";
+    return QP_ERR_ARG;
+  }
+  QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
+  pt.fill(chal.data());
+  DMem d_chal, d_out, d_part;
+  QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
+  QP_HIP_TRY(ctx, d_out.alloc(qpk::OPEN_STRIDE));
+  QP_HIP_TRY(ctx, d_part.alloc((uint64_t)qpk::OPEN_MAX_SLICES * qpk::OPEN_STRIDE));
+  QP_HIP_TRY(ctx, hipMemcpyAsync(d_chal.p, chal.data(), chal.size() * 8, hipMemcpyHostToDevice, s));
+  // prover.cpp stage 4: the zeta batch in oracle order, then the Zs at g*zeta
+  qpk::OpeningsArgs oa;
+  uint32_t off = 0;
+  for (int i = 0; i < 4; i++) {
+    oa.seg[oa.nseg++] = qpk::OpenSeg{bt[i]->d_coeffs, 0, bt[i]->npolys, qpk::CH_ZETA, off, 0};
+    off += bt[i]->npolys;
+  }
+  oa.seg[oa.nseg++] = qpk::OpenSeg{zs_pp->d_coeffs, 0, nc, qpk::CH_ZETA_NEXT, off, 0};
+  oa.log_n = log_n;
+  oa.pts = d_chal.p;
+  oa.out = d_out.p;
+  oa.part = d_part.p;
+  qpk::openings(oa, 1, s);
+  QP_HIP_TRY(ctx, hipGetLastError());
+  QP_HIP_TRY(ctx, hipMemcpyAsync(out, d_out.p, total * 16, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(ctx, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_batch_eval_ext(const qp_batch *b, uint32_t first, uint32_t npolys, const uint64_t *points, uint32_t npts,
+                      uint64_t *out) {
+  if (!b || !b->ctx) return QP_ERR_ARG;
+  qp_ctx *ctx = b->ctx;
+  if (!points || !out) {
+    ctx->err = "qp_batch_eval_ext: null argument";
+    return QP_ERR_ARG;
+  }
+  if (b->nbat != 1 || !b->d_coeffs || npolys < 1 || npts < 1 || first > b->npolys || npolys > b->npolys - first ||
+      (uint64_t)npts * npolys > (1u << 20) || b->log_n > qpk::BIG_LOG_MAX) {
+    ctx->err = "qp_batch_eval_ext: unsupported shape (a batch of one proof holding its coefficients, a window "
+               "inside it, at most 2^20 values)";
+    return QP_ERR_ARG;
+  }
+  // one segment per (point, window of at most ROW polynomials), packed into launches of at most
+  // OPEN_MAX_SEG segments and one OPEN_STRIDE row of results each
+  constexpr uint32_t ROW = qpk::OPEN_STRIDE / 2;
+  struct Piece { uint32_t launch, row_off, pt, p0, np; };
+  std::vector<Piece> pieces;
+  std::vector<qpk::OpeningsArgs> launches;
+  try {
+    uint32_t used = ROW;  // forces the first launch
+    for (uint32_t q = 0; q < npts; q++)
+      for (uint32_t p0 = 0; p0 < npolys; p0 += ROW) {
+        const uint32_t np = std::min(ROW, npolys - p0);
+        if (launches.empty() || used + np > ROW || launches.back().nseg == qpk::OPEN_MAX_SEG) {
+          launches.emplace_back();
+          used = 0;
+        }
+        qpk::OpeningsArgs &oa = launches.back();
+        oa.seg[oa.nseg++] = qpk::OpenSeg{b->d_coeffs + (uint64_t)(first + p0) * b->n(), 0, np, 2 * q, used, 0};
+        pieces.push_back(Piece{(uint32_t)launches.size() - 1, used, q, p0, np});
+        used += np;
+      }
+    std::vector<uint64_t> pts(2 * (size_t)npts), res(launches.size() * (size_t)qpk::OPEN_STRIDE);
+    for (size_t i = 0; i < pts.size(); i++) pts[i] = gl::canon(points[i]);
+    QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DMem d_pts, d_out, d_part;
+    QP_HIP_TRY(ctx, d_pts.alloc(pts.size()));
+    QP_HIP_TRY(ctx, d_out.alloc(res.size()));
+    QP_HIP_TRY(ctx, d_part.alloc((uint64_t)qpk::OPEN_MAX_SLICES * qpk::OPEN_STRIDE));
+    QP_HIP_TRY(ctx, hipMemcpyAsync(d_pts.p, pts.data(), pts.size() * 8, hipMemcpyHostToDevice, s));
+    for (size_t l = 0; l < launches.size(); l++) {
+      qpk::OpeningsArgs &oa = launches[l];
+      oa.log_n = b->log_n;
+      oa.pts = d_pts.p;  // proof index 0: the point of a segment is pts[pt_off], pts[pt_off + 1]
+      oa.out = d_out.p + l * (size_t)qpk::OPEN_STRIDE;
+      oa.part = d_part.p;  // launches are ordered on the stream: the scratch is free again
+      qpk::openings(oa, 1, s);
+    }
+    QP_HIP_TRY(ctx, hipGetLastError());
+    QP_HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_out.p, res.size() * 8, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(ctx, hipStreamSynchronize(s));
+    for (const Piece &pc : pieces)
+      memcpy(out + 2 * ((size_t)pc.pt * npolys + pc.p0),
+             res.data() + pc.launch * (size_t)qpk::OPEN_STRIDE + 2 * (size_t)pc.row_off, (size_t)pc.np * 16);
+  } catch (const std::bad_alloc &) {
+    return QP_ERR_OOM;
+  }
+  return QP_OK;
+}
+
+int qp_fri_initial_poly(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp_batch *zs_pp,
+                        const qp_batch *quotient, uint32_t nc, const uint64_t alpha[2], const uint64_t zeta[2],
+                        uint64_t *coeffs_out) {
+  if (!ctx) return QP_ERR_ARG;
+  const qp_batch *bt[4] = {cs, wires, zs_pp, quotient};
+  OpenPoint pt;
+  int rc = check_circuit_batches(ctx, "qp_fri_initial_poly", bt, nc, zeta, coeffs_out, &pt);
+  if (rc) return rc;
+  if (!alpha) {
+    ctx->err = "qp_fri_initial_poly: null argument";
+    return QP_ERR_ARG;
+  }
+  const uint32_t log_n = cs->log_n;
+  const uint64_t n = 1ull << log_n;
+  QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
+  pt.fill(chal.data());
+  const gl::ext al{gl::canon(alpha[0]), gl::canon(alpha[1])}, ap = gl::ext_pow(al, nc);
+  chal[qpk::CH_FRI_ALPHA] = al.c0;
+  chal[qpk::CH_FRI_ALPHA + 1] = al.c1;
+  chal[qpk::CH_ALPHA_POW_NC] = ap.c0;
+  chal[qpk::CH_ALPHA_POW_NC + 1] = ap.c1;
+  DMem d_chal, d_comp, d_fin;
+  QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
+  QP_HIP_TRY(ctx, d_comp.alloc(4 * n));
+  QP_HIP_TRY(ctx, d_fin.alloc(2 * n));
+  QP_HIP_TRY(ctx, hipMemcpyAsync(d_chal.p, chal.data(), chal.size() * 8, hipMemcpyHostToDevice, s));
+  // prover.cpp stage 5
+  qpk::FriComposeArgs fa;
+  for (int i = 0; i < 4; i++) {
+    fa.coeffs[i] = bt[i]->d_coeffs;
+    fa.bstride[i] = 0;
+    fa.npolys[i] = bt[i]->npolys;
+  }
+  fa.noracles = 4;
+  fa.nnext = nc;
+  fa.log_n = log_n;
+  fa.chal = d_chal.p;
+  fa.comp = d_comp.p;
+  qpk::k_fri_compose<<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(fa);
+  // k_fri_divide: n / 8 threads up to 1024, n / threads values each (n >= 2^6: at least 8 threads;
+  // <16> holds 16 per thread, n <= 2^14; <64> holds 64, n <= 2^16)
+  const unsigned T = (unsigned)std::min<uint64_t>(1024, n / 8);
+  if (n / T <= 16)
+    qpk::k_fri_divide<16><<<1, T, 0, s>>>(d_comp.p, d_fin.p, log_n, d_chal.p, 0, n);
+  else
+    qpk::k_fri_divide<64><<<1, 1024, 0, s>>>(d_comp.p, d_fin.p, log_n, d_chal.p, 0, n);
+  QP_HIP_TRY(ctx, hipGetLastError());
+  QP_HIP_TRY(ctx, hipMemcpyAsync(coeffs_out, d_fin.p, 2 * n * 8, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(ctx, hipStreamSynchronize(s));
   return QP_OK;
 }
 

@@ -5,8 +5,9 @@ Mirrors qp-wormhole-prover's WormholeProver (wormhole/prover/src/lib.rs:74-237)
 and plonky2's PolynomialBatch for the parity tests.  The HIP library is the
 only backend: importing the native pieces raises if it is not built.
 """
-from ._native import (GATE_KINDS, Context, FriLayer, GateDesc, PolynomialBatch, QpError, debug_field_op,  # noqa: F401
-                      fri_fold, gate_desc, header_symbols, ifft, lde, lib, poseidon_permute, pow_grind, quotient)
+from ._native import (GATE_KINDS, Context, FriLayer, GateDesc, PermutationData, PolynomialBatch, QpError,  # noqa: F401
+                      debug_field_op, fri_fold, fri_initial_poly, gate_desc, header_symbols, ifft, lde, lib,
+                      opening_set, poseidon_permute, pow_grind, quotient)
 
 from .circuits import (Circuit, CircuitInputs, PrivateCircuitInputs, ProcessedStorageProof,  # noqa: F401,E402
                        PublicCircuitInputs, VoteCircuitData, VotePrivateInputs, VotePublicInputs, Witness)
@@ -20,4 +21,5 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "Witness", "VoteCircuitData", "VotePrivateInputs", "VotePublicInputs", "Prover", "ProofWithPublicInputs", "WormholeProver", "Context", "PolynomialBatch", "QpError", "ifft", "lde", "poseidon_permute", "lib", "header_symbols",
            "generate_circuit_binaries", "prover_only_bytes", "AggregatedProof", "CircuitData", "TreeAggregationConfig",
            "WormholeProofAggregator", "aggregate_chunk", "aggregate_level", "aggregate_to_tree", "GateDesc", "gate_desc", "quotient", "FriLayer", "fri_fold", "pow_grind",
+           "PermutationData", "opening_set", "fri_initial_poly",
            "WormholeVerifier", "merkle_verify"]

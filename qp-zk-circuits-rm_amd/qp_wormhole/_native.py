@@ -161,6 +161,12 @@ def lib():
         "qp_fri_layer_free": (None, [VP]),
         "qp_fri_fold": (ctypes.c_int, [VP, U64P, ctypes.c_uint32, ctypes.c_uint32, U64P, U64P]),
         "qp_pow_grind": (ctypes.c_int, [VP, U64P, U32P, ctypes.c_uint32, ctypes.c_uint32, U64P]),
+        "qp_perm_new": (ctypes.c_int, [VP, U64P, U64P, ctypes.c_uint32, ctypes.c_uint32, PP]),
+        "qp_perm_free": (None, [VP]),
+        "qp_partial_products_and_zs": (ctypes.c_int, [VP, U64P, ctypes.c_uint32, U64P, U64P, ctypes.c_uint32, U64P]),
+        "qp_opening_set": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_uint32, U64P, U64P]),
+        "qp_batch_eval_ext": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, U64P, ctypes.c_uint32, U64P]),
+        "qp_fri_initial_poly": (ctypes.c_int, [VP, VP, VP, VP, VP, ctypes.c_uint32, U64P, U64P, U64P]),
         "qp_verifier_new": (ctypes.c_int, [VP, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
                                            ctypes.c_uint32, PP]),
         "qp_verifier_free": (None, [VP]),
@@ -263,6 +269,17 @@ class PolynomialBatch:
         sibs = np.zeros((len(idx), depth, 4), np.uint64)
         self.ctx.check(lib().qp_batch_open(self.h, idx, len(idx), leaves, sibs), "qp_batch_open")
         return leaves, sibs
+
+    def eval_ext(self, points, first=0, npolys=None):
+        """qp_batch_eval_ext: polynomials [first, first + npolys) at the extension
+        points [npts][2]; returns [npts][npolys][2]."""
+        pts = _ext_points(points)
+        npolys = self.npolys - first if npolys is None else npolys
+        if first < 0 or npolys < 1 or first + npolys > self.npolys:
+            raise ValueError(f"window [{first}, {first + npolys}) outside the batch's {self.npolys} polynomials")
+        out = np.zeros((pts.shape[0], npolys, 2), np.uint64)
+        self.ctx.check(lib().qp_batch_eval_ext(self.h, first, npolys, pts, pts.shape[0], out), "qp_batch_eval_ext")
+        return out
 
     def lde(self):
         out = np.zeros((self.npolys, 1 << (self.log_n + self.rate_bits)), np.uint64)
@@ -408,4 +425,86 @@ def pow_grind(ctx, states, pos, pow_bits):
     p = np.ascontiguousarray(pos, dtype=np.uint32)
     out = np.zeros(st.shape[0], np.uint64)
     ctx.check(lib().qp_pow_grind(ctx.h, st, p, st.shape[0], pow_bits, out), "qp_pow_grind")
+    return out
+
+
+def _ext_points(points):
+    """extension points as a uint64 array [npts][2]"""
+    pts = np.ascontiguousarray(points, dtype=np.uint64)
+    if pts.ndim != 2 or pts.shape[1] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [npts][2] (ext c0, c1)")
+    return pts
+
+
+def _cols(a, what, n=None):
+    """a column-major uint64 matrix [ncols][2^k] (2^k == n when given)"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1 or a.shape[1] & (a.shape[1] - 1):
+        raise ValueError(f"{what} must be [columns][2^k]")
+    if n is not None and a.shape[1] != n:
+        raise ValueError(f"{what} must have {n} rows per column, got {a.shape[1]}")
+    return a
+
+
+class PermutationData:
+    """A circuit's sigma columns and k_is on the device (qp_perm), uploaded once."""
+
+    def __init__(self, ctx, sigmas, k_is):
+        s = _cols(sigmas, "sigmas")
+        k = np.ascontiguousarray(k_is, dtype=np.uint64)
+        if k.ndim != 1 or k.size != s.shape[0]:
+            raise ValueError(f"k_is must hold one value per sigma column ({s.shape[0]})")
+        self.ctx, self.num_routed, self.n = ctx, s.shape[0], s.shape[1]
+        self.h = None
+        h = ctypes.c_void_p()
+        ctx.check(lib().qp_perm_new(ctx.h, s, k, s.shape[0], s.shape[1].bit_length() - 1, ctypes.byref(h)),
+                  "qp_perm_new")
+        self.h = h
+
+    def partial_products_and_zs(self, wires, qdf, betas, gammas):
+        """wires_permutation_partial_products_and_zs: wires [>= num_routed][n] ->
+        [nc * nchunks][n], all Zs first, then the partial products per challenge."""
+        w = _cols(wires, "wires", self.n)
+        if w.shape[0] < self.num_routed:
+            raise ValueError(f"wires must hold the {self.num_routed} routed columns")
+        b, g = _u64(betas), _u64(gammas)
+        if b.ndim != 1 or b.size < 1 or b.size != g.size:
+            raise ValueError("betas and gammas must hold one value per challenge")
+        qdf = int(qdf)
+        if qdf < 1:
+            raise ValueError("quotient_degree_factor must be positive")
+        nchunks = (self.num_routed + qdf - 1) // qdf
+        out = np.zeros((b.size * nchunks, self.n), np.uint64)
+        self.ctx.check(lib().qp_partial_products_and_zs(self.h, w, qdf, b, g, b.size, out),
+                       "qp_partial_products_and_zs")
+        return out
+
+    def free(self):
+        if self.h:
+            lib().qp_perm_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def opening_set(ctx, cs, wires, zs_pp, quotient, nc, zeta):
+    """OpeningSet::new: every polynomial of the four batches at zeta in oracle order,
+    then the nc Zs at g*zeta: [(sum of npolys) + nc][2]."""
+    z = _u64(zeta, 2)
+    out = np.zeros((cs.npolys + wires.npolys + zs_pp.npolys + quotient.npolys + int(nc), 2), np.uint64)
+    ctx.check(lib().qp_opening_set(ctx.h, cs.h, wires.h, zs_pp.h, quotient.h, int(nc), z, out), "qp_opening_set")
+    return out
+
+
+def fri_initial_poly(ctx, cs, wires, zs_pp, quotient, nc, alpha, zeta):
+    """The polynomial PolynomialBatch::prove_openings hands to FRI: ext coefficients
+    [2][n] (c0 row, c1 row), the layout FriLayer takes."""
+    a, z = _u64(alpha, 2), _u64(zeta, 2)
+    out = np.zeros((2, 1 << cs.log_n), np.uint64)
+    ctx.check(lib().qp_fri_initial_poly(ctx.h, cs.h, wires.h, zs_pp.h, quotient.h, int(nc), a, z, out),
+              "qp_fri_initial_poly")
     return out
