@@ -3,9 +3,11 @@
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <new>
+#include <vector>
 #include "ctx.h"
 #include "field.h"
 #include "kernels.h"
+#include "prover_kernels.h"
 
 extern "C" {
 
@@ -212,30 +214,32 @@ int qp_batch_open(qp_batch *b, const uint32_t *idx, uint32_t nidx, uint64_t *lea
   const uint32_t logN = b->log_n + b->rate_bits, W = b->npolys + b->nsalt, depth = logN - b->cap_h;
   for (uint32_t q = 0; q < nidx; q++)
     if (idx[q] >= N) { c->err = "leaf index out of range"; return QP_ERR_ARG; }
-  uint32_t *d_idx = nullptr;
-  uint64_t *d_rows = nullptr, *d_sib = nullptr;
-  QP_HIP_TRY(c, hipMalloc(&d_idx, nidx * 4ull + 4));
-  QP_HIP_TRY(c, hipMalloc(&d_rows, (size_t)nidx * W * 8 + 8));
-  QP_HIP_TRY(c, hipMalloc(&d_sib, (size_t)nidx * depth * 32 + 8));
-  QP_HIP_TRY(c, hipMemcpyAsync(d_idx, idx, nidx * 4ull, hipMemcpyHostToDevice, c->stream));
-  qpk::gather_rows(b->d_lde, N, b->npolys, d_idx, nidx, d_rows, c->stream);
-  qpk::gather_paths(b->d_dig, logN, b->cap_h, d_idx, nidx, d_sib, c->stream);
-  QP_HIP_TRY(c, hipGetLastError());
-  uint64_t *tmp = new uint64_t[(size_t)nidx * b->npolys + 1];
-  QP_HIP_TRY(c, hipMemcpyAsync(tmp, d_rows, (size_t)nidx * b->npolys * 8, hipMemcpyDeviceToHost, c->stream));
-  if (sib_out) QP_HIP_TRY(c, hipMemcpyAsync(sib_out, d_sib, (size_t)nidx * depth * 32, hipMemcpyDeviceToHost, c->stream));
-  hipError_t e = hipStreamSynchronize(c->stream);
-  if (!e && leaves_out) {
-    for (uint32_t q = 0; q < nidx; q++) {
-      memcpy(leaves_out + (size_t)q * W, tmp + (size_t)q * b->npolys, b->npolys * 8ull);
-      if (b->nsalt)
-        e = hipMemcpy(leaves_out + (size_t)q * W + b->npolys, b->d_salt + (size_t)idx[q] * b->nsalt, b->nsalt * 8ull,
-                      hipMemcpyDeviceToHost);
+  try {
+    DevBuf d_idx, d_rows, d_sib;
+    std::vector<uint64_t> tmp((size_t)nidx * b->npolys);
+    QP_HIP_TRY(c, d_idx.alloc((nidx + 1) / 2));
+    QP_HIP_TRY(c, d_rows.alloc((size_t)nidx * b->npolys));
+    QP_HIP_TRY(c, d_sib.alloc((size_t)nidx * depth * 4));
+    QP_HIP_TRY(c, hipMemcpyAsync(d_idx.p, idx, nidx * 4ull, hipMemcpyHostToDevice, c->stream));
+    qpk::gather_rows(b->d_lde, N, 0, b->npolys, d_idx.as<uint32_t>(), nidx, 0, d_rows.p, 0, 1, c->stream);
+    qpk::gather_paths(b->d_dig, 0, logN, b->cap_h, d_idx.as<uint32_t>(), nidx, 0, d_sib.p, 0, 1, c->stream);
+    QP_HIP_TRY(c, hipGetLastError());
+    QP_HIP_TRY(c, hipMemcpyAsync(tmp.data(), d_rows.p, tmp.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sib_out)
+      QP_HIP_TRY(c, hipMemcpyAsync(sib_out, d_sib.p, (size_t)nidx * depth * 32, hipMemcpyDeviceToHost, c->stream));
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (!e && leaves_out) {
+      for (uint32_t q = 0; q < nidx; q++) {
+        memcpy(leaves_out + (size_t)q * W, tmp.data() + (size_t)q * b->npolys, b->npolys * 8ull);
+        if (b->nsalt)
+          e = hipMemcpy(leaves_out + (size_t)q * W + b->npolys, b->d_salt + (size_t)idx[q] * b->nsalt, b->nsalt * 8ull,
+                        hipMemcpyDeviceToHost);
+      }
     }
+    QP_HIP_TRY(c, e);
+  } catch (const std::bad_alloc &) {
+    return QP_ERR_OOM;
   }
-  delete[] tmp;
-  (void)hipFree(d_idx); (void)hipFree(d_rows); (void)hipFree(d_sib);
-  QP_HIP_TRY(c, e);
   return QP_OK;
 }
 
@@ -255,14 +259,13 @@ int qp_ifft(qp_ctx *c, uint64_t *data, uint32_t ncols, uint32_t log_n) {
   int st = check_shape(c, ncols, log_n, 0, 0);
   if (st) return st;
   const size_t bytes = (size_t)ncols * 8 << log_n;
-  uint64_t *d = nullptr, *d2 = nullptr;
-  QP_HIP_TRY(c, hipMalloc(&d, bytes));
-  QP_HIP_TRY(c, hipMalloc(&d2, bytes));
-  QP_HIP_TRY(c, hipMemcpyAsync(d, data, bytes, hipMemcpyHostToDevice, c->stream));
-  qpk::intt(c->tw, d, 1ull << log_n, d2, 1ull << log_n, ncols, log_n, 1, 0, 0, c->stream);
-  QP_HIP_TRY(c, hipMemcpyAsync(data, d2, bytes, hipMemcpyDeviceToHost, c->stream));
+  DevBuf d, d2;
+  QP_HIP_TRY(c, d.alloc(bytes / 8));
+  QP_HIP_TRY(c, d2.alloc(bytes / 8));
+  QP_HIP_TRY(c, hipMemcpyAsync(d.p, data, bytes, hipMemcpyHostToDevice, c->stream));
+  qpk::intt(c->tw, d.p, 1ull << log_n, d2.p, 1ull << log_n, ncols, log_n, 1, 0, 0, c->stream);
+  QP_HIP_TRY(c, hipMemcpyAsync(data, d2.p, bytes, hipMemcpyDeviceToHost, c->stream));
   QP_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d); (void)hipFree(d2);
   return QP_OK;
 }
 
@@ -271,27 +274,25 @@ int qp_lde(qp_ctx *c, const uint64_t *coeffs, uint32_t ncols, uint32_t log_n, ui
   int st = check_shape(c, ncols, log_n, rate_bits, 0);
   if (st) return st;
   const uint64_t n = 1ull << log_n, N = n << rate_bits;
-  uint64_t *d = nullptr, *d2 = nullptr;
-  QP_HIP_TRY(c, hipMalloc(&d, ncols * n * 8));
-  QP_HIP_TRY(c, hipMalloc(&d2, ncols * N * 8));
-  QP_HIP_TRY(c, hipMemcpyAsync(d, coeffs, ncols * n * 8, hipMemcpyHostToDevice, c->stream));
-  qpk::lde(c->tw, d, n, d2, N, ncols, log_n, rate_bits, shift, 1, 0, 0, c->stream);
-  QP_HIP_TRY(c, hipMemcpyAsync(out, d2, ncols * N * 8, hipMemcpyDeviceToHost, c->stream));
+  DevBuf d, d2;
+  QP_HIP_TRY(c, d.alloc(ncols * n));
+  QP_HIP_TRY(c, d2.alloc(ncols * N));
+  QP_HIP_TRY(c, hipMemcpyAsync(d.p, coeffs, ncols * n * 8, hipMemcpyHostToDevice, c->stream));
+  qpk::lde(c->tw, d.p, n, d2.p, N, ncols, log_n, rate_bits, shift, 1, 0, 0, c->stream);
+  QP_HIP_TRY(c, hipMemcpyAsync(out, d2.p, ncols * N * 8, hipMemcpyDeviceToHost, c->stream));
   QP_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d); (void)hipFree(d2);
   return QP_OK;
 }
 
 int qp_poseidon_permute(qp_ctx *c, uint64_t *states, uint64_t n) {
   if (!c || (!states && n)) return QP_ERR_ARG;
   if (!n) return QP_OK;
-  uint64_t *d = nullptr;
-  QP_HIP_TRY(c, hipMalloc(&d, n * 96));
-  QP_HIP_TRY(c, hipMemcpyAsync(d, states, n * 96, hipMemcpyHostToDevice, c->stream));
-  qpk::permute_batch(d, n, c->stream);
-  QP_HIP_TRY(c, hipMemcpyAsync(states, d, n * 96, hipMemcpyDeviceToHost, c->stream));
+  DevBuf d;
+  QP_HIP_TRY(c, d.alloc(n * 12));
+  QP_HIP_TRY(c, hipMemcpyAsync(d.p, states, n * 96, hipMemcpyHostToDevice, c->stream));
+  qpk::permute_batch(d.p, n, c->stream);
+  QP_HIP_TRY(c, hipMemcpyAsync(states, d.p, n * 96, hipMemcpyDeviceToHost, c->stream));
   QP_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(d);
   return QP_OK;
 }
 

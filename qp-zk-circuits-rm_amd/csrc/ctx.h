@@ -25,6 +25,35 @@ struct qp_batch {
   uint64_t ndig() const { return qpk::tree_digest_count(log_n + rate_bits, cap_h); }
 };
 
+// A device allocation of 64-bit words, owned by a handle or by one ABI call:
+// every return path of the owner frees it.
+struct DevBuf {
+  uint64_t *p = nullptr;
+  size_t words = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), words(o.words) { o.p = nullptr; }
+  hipError_t alloc(size_t w) {  // at least one word: p is non-null after a successful alloc(0)
+    release();
+    words = w;
+    return hipMalloc(&p, (w ? w : 1) * 8);
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    words = 0;
+  }
+  template <class T>
+  T *as() const {
+    return reinterpret_cast<T *>(p);
+  }
+  // hipFree waits for the device, so freeing while launches on the context's
+  // stream are still running is safe.
+  ~DevBuf() { release(); }
+};
+
+// ctx: any handle with a std::string err (qp_ctx, qp_verifier)
 #define QP_HIP_TRY(ctx, expr)                                                    \
   do {                                                                           \
     hipError_t _e = (expr);                                                      \

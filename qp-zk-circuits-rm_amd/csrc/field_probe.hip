@@ -121,26 +121,20 @@ extern "C" int qp_debug_field_op(qp_ctx *c, uint32_t op, uint32_t param, const u
   if (!n) return QP_OK;
   if (!a || !out || (!b && !unary(op))) { c->err = "null argument"; return QP_ERR_ARG; }
   const uint64_t ngroups = n / G, nout = op == QP_FOP_ACC3 ? ngroups : n;
-  uint64_t *da = nullptr, *db = nullptr, *dout = nullptr;
-  auto release = [&] {
-    if (da) (void)hipFree(da);
-    if (db) (void)hipFree(db);
-    if (dout) (void)hipFree(dout);
-  };
+  DevBuf da, db, dout;  // db stays null for a unary op
   hipError_t e = hipSetDevice(c->device);
-  if (!e) e = hipMalloc(&da, n * 8);
-  if (!e && b) e = hipMalloc(&db, n * 8);
-  if (!e) e = hipMalloc(&dout, nout * 8);
-  if (!e) e = hipMemcpyAsync(da, a, n * 8, hipMemcpyHostToDevice, c->stream);
-  if (!e && b) e = hipMemcpyAsync(db, b, n * 8, hipMemcpyHostToDevice, c->stream);
+  if (!e) e = da.alloc(n);
+  if (!e && b) e = db.alloc(n);
+  if (!e) e = dout.alloc(nout);
+  if (!e) e = hipMemcpyAsync(da.p, a, n * 8, hipMemcpyHostToDevice, c->stream);
+  if (!e && b) e = hipMemcpyAsync(db.p, b, n * 8, hipMemcpyHostToDevice, c->stream);
   if (!e) {
     const dim3 grid((unsigned)std::min<uint64_t>((ngroups + 255) / 256, 1024));
-    launch(op, grid, c->stream, da, db, ngroups, param, dout);
+    launch(op, grid, c->stream, da.p, db.p, ngroups, param, dout.p);
     e = hipGetLastError();
   }
-  if (!e) e = hipMemcpyAsync(out, dout, nout * 8, hipMemcpyDeviceToHost, c->stream);
+  if (!e) e = hipMemcpyAsync(out, dout.p, nout * 8, hipMemcpyDeviceToHost, c->stream);
   if (!e) e = hipStreamSynchronize(c->stream);
-  release();
   if (e) {
     c->err = std::string("qp_debug_field_op: ") + hipGetErrorString(e);
     return e == hipErrorOutOfMemory ? QP_ERR_OOM : QP_ERR_HIP;

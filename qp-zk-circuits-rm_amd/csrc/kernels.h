@@ -112,13 +112,6 @@ inline uint64_t tree_level_offset(uint32_t log_N, uint32_t level) {  // in diges
   return o;
 }
 
-// row gather for query openings: out[q][c] = cols[c*stride + idx[q]]
-void gather_rows(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint32_t *idx, uint32_t nidx,
-                 uint64_t *out, hipStream_t s);
-// Merkle paths: out[q][k][4] = sibling digest at level k of leaf idx[q]
-void gather_paths(const uint64_t *digests, uint32_t log_N, uint32_t cap_h, const uint32_t *idx, uint32_t nidx,
-                  uint64_t *out, hipStream_t s);
-
 // bulk Poseidon permutations (states [n][12], in place)
 void permute_batch(uint64_t *states, uint64_t n, hipStream_t s);
 

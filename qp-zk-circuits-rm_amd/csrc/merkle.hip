@@ -1,4 +1,4 @@
-// merkle.hip — Poseidon leaf hashing, Merkle tree/cap, query gathers (gfx950).
+// merkle.hip — Poseidon leaf hashing, Merkle tree/cap (gfx950).
 // plonky2 hash/merkle_tree.rs semantics: leaf digest =
 // hash_or_noop(leaf), node = two_to_one(L, R), cap = 2^h subtree roots.
 // VALU-bound: one lane per leaf / node, the 12-element state in registers;
@@ -273,40 +273,6 @@ void leaf_hash_tree(const uint64_t *cols, uint64_t stride, uint32_t ncols, const
   const uint32_t first = leaf_hash_first(cols, stride, ncols, salt, nsalt, digests, log_N, cap_h, nbat, c_bstride,
                                          s_bstride, d_bstride, s);
   merkle_tree_from(digests, log_N, cap_h, nbat, d_bstride, first, s);
-}
-
-__global__ void k_gather_rows(const uint64_t *__restrict__ cols, uint64_t stride, uint32_t ncols,
-                              const uint32_t *__restrict__ idx, uint32_t nidx, uint64_t *__restrict__ out) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ncols * nidx) return;
-  const uint32_t q = t / ncols, c = t % ncols;
-  out[t] = cols[(uint64_t)c * stride + idx[q]];
-}
-
-void gather_rows(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint32_t *idx, uint32_t nidx,
-                 uint64_t *out, hipStream_t s) {
-  uint32_t tot = ncols * nidx;
-  if (!tot) return;
-  k_gather_rows<<<(tot + 255) / 256, 256, 0, s>>>(cols, stride, ncols, idx, nidx, out);
-}
-
-__global__ void k_gather_paths(const uint64_t *__restrict__ dig, uint32_t log_N, uint32_t cap_h,
-                               const uint32_t *__restrict__ idx, uint32_t nidx, uint64_t *__restrict__ out) {
-  const uint32_t depth = log_N - cap_h;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nidx * depth * 4) return;
-  const uint32_t q = t / (depth * 4), r = t % (depth * 4), k = r / 4, e = r % 4;
-  uint64_t off = 0;
-  for (uint32_t j = 0; j < k; j++) off += (uint64_t)1 << (log_N - j);
-  const uint64_t sib = (uint64_t)((idx[q] >> k) ^ 1u);
-  out[t] = dig[(off + sib) * 4 + e];
-}
-
-void gather_paths(const uint64_t *digests, uint32_t log_N, uint32_t cap_h, const uint32_t *idx, uint32_t nidx,
-                  uint64_t *out, hipStream_t s) {
-  uint32_t tot = nidx * (log_N - cap_h) * 4;
-  if (!tot) return;
-  k_gather_paths<<<(tot + 255) / 256, 256, 0, s>>>(digests, log_N, cap_h, idx, nidx, out);
 }
 
 __global__ void __launch_bounds__(256) k_permute(uint64_t *states, uint64_t n) {

@@ -33,18 +33,6 @@ namespace {
 
 using gl::ext;
 
-struct DevBuf {
-  uint64_t *p = nullptr;
-  size_t words = 0;
-  hipError_t alloc(size_t w) {
-    words = w;
-    return hipMalloc(&p, (w ? w : 1) * 8);
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 struct Tree {  // one Merkle-committed matrix per proof
   uint32_t npolys = 0, log_n = 0, rate_bits = 0, cap_h = 0;
   DevBuf vals, coeffs, lde, dig;
@@ -148,6 +136,29 @@ void perm_challenges(uint64_t *ch, const uint64_t *beta, const uint64_t *gamma, 
   }
 }
 
+void open_point_words(uint64_t *ch, ext zeta, uint32_t log_n) {
+  const ext zn = gl::ext_scale(zeta, gl::root_of_unity(log_n));
+  const ext zi = gl::ext_inv(zeta), zni = gl::ext_inv(zn);
+  ch[CH_ZETA] = zeta.c0; ch[CH_ZETA + 1] = zeta.c1;
+  ch[CH_ZETA_NEXT] = zn.c0; ch[CH_ZETA_NEXT + 1] = zn.c1;
+  ch[CH_ZETA_INV] = zi.c0; ch[CH_ZETA_INV + 1] = zi.c1;
+  ch[CH_ZETA_NEXT_INV] = zni.c0; ch[CH_ZETA_NEXT_INV + 1] = zni.c1;
+}
+
+void fri_alpha_words(uint64_t *ch, ext alpha, uint32_t nc) {
+  const ext ap = gl::ext_pow(alpha, nc);
+  ch[CH_FRI_ALPHA] = alpha.c0; ch[CH_FRI_ALPHA + 1] = alpha.c1;
+  ch[CH_ALPHA_POW_NC] = ap.c0; ch[CH_ALPHA_POW_NC + 1] = ap.c1;
+}
+
+void alpha_powers(uint64_t *apow, uint64_t alpha, uint32_t nterms) {
+  uint64_t p = 1;
+  for (uint32_t i = 0; i < nterms; i++) {
+    apow[i] = p;
+    p = gl::mul(p, alpha);
+  }
+}
+
 // proof-independent point tables of the quotient, leaf order t (point
 // x = g w_N^rev(t)): xtab[t] = x, l0tab[t] = L_0(x) = Z_H(x) / (n (x - 1))
 // (one batch inversion here instead of a field inversion per point per proof)
@@ -199,14 +210,7 @@ void pow_prestate(const uint64_t st12[12], uint32_t pos, uint64_t pre[24]) {
 
 namespace {
 
-#define TRY(expr)                                                              \
-  do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      P->ctx->err = std::string(#expr) + ": " + hipGetErrorString(_e);         \
-      return _e == hipErrorOutOfMemory ? QP_ERR_OOM : QP_ERR_HIP;              \
-    }                                                                          \
-  } while (0)
+#define TRY(expr) QP_HIP_TRY(P->ctx, expr)
 
 uint32_t oracle_width(const qp_prover *p, int o) {
   switch (o) {
@@ -384,7 +388,9 @@ int setup(qp_prover *P) {
       TRY(up32(P->wg_in_slots, cd.input_slots));
       TRY(P->wg_in.alloc((size_t)B * std::max<uint32_t>(P->wg_nin, 1)));
       TRY(P->wg_err.alloc((B + 1) / 2));
-      TRY(hipHostMalloc((void **)&P->h_in, (size_t)B * std::max<uint32_t>(P->wg_nin, 1) * 8, hipHostMallocDefault));
+      // not TRY: a macro argument handed on is expanded, and the error text would read 0x0 for the flag
+      QP_HIP_TRY(c, hipHostMalloc((void **)&P->h_in, (size_t)B * std::max<uint32_t>(P->wg_nin, 1) * 8,
+                                  hipHostMallocDefault));
       P->h_werr.assign(B, 0);
     }
     P->h_wpis.assign((size_t)B * std::max<uint32_t>(P->npis, 1), 0);
@@ -515,7 +521,6 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
                 const uint64_t *const *pis_host, uint32_t nb, uint8_t *out, size_t stride, size_t *lens) {
   qp_ctx *c = P->ctx;
   hipStream_t s = c->stream;
-  const uint64_t n = 1ull << P->log_n;
   const uint32_t logN = P->log_n + P->rate_bits;
   const uint64_t N = 1ull << logN;
   const size_t capw = 4u << P->cap_h;
@@ -574,19 +579,8 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
   lap(0);
 
   // ---- 2. partial products + Z (a9), commitment
-  const uint64_t pbs = (uint64_t)nc * P->nchunks * n;
-  if (P->R == 80 && P->qdf == 8 && nc == 2)
-    qpk::k_pp_rows_t<80, 8><<<dim3(cdiv(n, 256), nb), 256, 0, s>>>(wv, P->sigmas.p, P->kis.p, P->chal.p, P->prods.p,
-                                                                    P->log_n, P->wires.cbs(), pbs, c->tw.fwd);
-  else
-    qpk::k_pp_rows<<<dim3(cdiv(n, 256), nb), 256, 0, s>>>(wv, P->sigmas.p, P->kis.p, P->chal.p, P->prods.p,
-                                                           P->log_n, P->R, P->qdf, nc, P->wires.cbs(), pbs, c->tw.fwd);
-  if (P->log_n <= qpk::LDS_LOG_MAX)
-    qpk::k_z_scan<true><<<dim3(nc, nb), 1024, 8u * (qpk::ntt_lds_words(n) + 1024), s>>>(
-        P->prods.p, P->zs.vals.p, P->log_n, nc, P->nchunks, pbs, P->zs.cbs());
-  else
-    qpk::k_z_scan<false><<<dim3(nc, nb), 1024, 8u * 1024, s>>>(P->prods.p, P->zs.vals.p, P->log_n, nc, P->nchunks,
-                                                              pbs, P->zs.cbs());
+  qpk::partial_products_and_zs(c->tw, wv, P->wires.cbs(), P->sigmas.p, P->kis.p, P->chal.p, P->prods.p, P->zs.vals.p,
+                               P->zs.cbs(), P->log_n, P->R, P->qdf, nc, nb, s);
   P->zs.build_from_values(c, nb);
   TRY(hipGetLastError());
   if ((rc = fetch_caps(P, P->zs.dig.p, P->zs.dbs(), logN, nb))) return rc;
@@ -596,13 +590,8 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     S.t.observe(S.caps[1].data(), capw);
     uint64_t *ch = P->h_chal.data() + b * qpk::CHAL_STRIDE;
     for (uint32_t i = 0; i < nc; i++) ch[qpk::CH_ALPHA + i] = S.t.get();
-    for (uint32_t c2 = 0; c2 < 2; c2++) {
-      uint64_t *ap = P->h_apow.data() + (b * 2 + c2) * qpk::APOW_STRIDE, p = 1;
-      for (uint32_t i = 0; i < P->nterms; i++) {
-        ap[i] = p;
-        p = gl::mul(p, ch[qpk::CH_ALPHA + c2]);
-      }
-    }
+    for (uint32_t c2 = 0; c2 < 2; c2++)
+      qpk::alpha_powers(P->h_apow.data() + (b * 2 + c2) * qpk::APOW_STRIDE, ch[qpk::CH_ALPHA + c2], P->nterms);
   });
   if ((rc = push_chal(P, nb))) return rc;
   TRY(hipMemcpyAsync(P->apow.p, P->h_apow.data(), (size_t)nb * 2 * qpk::APOW_STRIDE * 8, hipMemcpyHostToDevice, s));
@@ -641,19 +630,11 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     TRY(hipGetLastError());
   }
   if ((rc = fetch_caps(P, P->quot.dig.p, P->quot.dbs(), logN, nb))) return rc;
-  const uint64_t g_n = gl::root_of_unity(P->log_n);
   P->pool->parallel_for(nb, [&](size_t b) {
     ProofState &S = st[b];
     S.caps[2].assign(P->h_caps.begin() + b * capw, P->h_caps.begin() + (b + 1) * capw);
     S.t.observe(S.caps[2].data(), capw);
-    ext z = S.t.get_ext();
-    ext zn = gl::ext_scale(z, g_n);
-    ext zi = gl::ext_inv(z), zni = gl::ext_inv(zn);
-    uint64_t *ch = P->h_chal.data() + b * qpk::CHAL_STRIDE;
-    ch[qpk::CH_ZETA] = z.c0; ch[qpk::CH_ZETA + 1] = z.c1;
-    ch[qpk::CH_ZETA_NEXT] = zn.c0; ch[qpk::CH_ZETA_NEXT + 1] = zn.c1;
-    ch[qpk::CH_ZETA_INV] = zi.c0; ch[qpk::CH_ZETA_INV + 1] = zi.c1;
-    ch[qpk::CH_ZETA_NEXT_INV] = zni.c0; ch[qpk::CH_ZETA_NEXT_INV + 1] = zni.c1;
+    qpk::open_point_words(P->h_chal.data() + b * qpk::CHAL_STRIDE, S.t.get_ext(), P->log_n);
   });
   if ((rc = push_chal(P, nb))) return rc;
   lap(2);
@@ -691,11 +672,7 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     const uint64_t *o = P->h_open.data() + b * qpk::OPEN_STRIDE;
     S.t.observe(o, 2 * (size_t)nopen);           // zeta batch in oracle order
     S.t.observe(o + 2 * (size_t)nopen, 2 * nc);  // g*zeta batch
-    ext al = S.t.get_ext();
-    ext ap = gl::ext_pow(al, nc);
-    uint64_t *ch = P->h_chal.data() + b * qpk::CHAL_STRIDE;
-    ch[qpk::CH_FRI_ALPHA] = al.c0; ch[qpk::CH_FRI_ALPHA + 1] = al.c1;
-    ch[qpk::CH_ALPHA_POW_NC] = ap.c0; ch[qpk::CH_ALPHA_POW_NC + 1] = ap.c1;
+    qpk::fri_alpha_words(P->h_chal.data() + b * qpk::CHAL_STRIDE, S.t.get_ext(), nc);
   });
   if ((rc = push_chal(P, nb))) return rc;
   lap(3);
@@ -710,12 +687,7 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
     fa.noracles = 4; fa.nnext = nc; fa.log_n = P->log_n;
     fa.chal = P->chal.p;
     fa.comp = P->comp.p;
-    qpk::k_fri_compose<<<dim3(cdiv(n, 256), nb), 256, 0, s>>>(fa);
-    if (n / std::min<uint64_t>(1024, n / 8) <= 16)
-      qpk::k_fri_divide<16><<<nb, (unsigned)std::min<uint64_t>(1024, n / 8), 0, s>>>(P->comp.p, P->fin.p, P->log_n,
-                                                                                   P->chal.p, 2 * N, N);
-    else
-      qpk::k_fri_divide<64><<<nb, 1024, 0, s>>>(P->comp.p, P->fin.p, P->log_n, P->chal.p, 2 * N, N);
+    qpk::fri_initial_poly(fa, P->fin.p, 2 * N, N, nb, s);
     TRY(hipGetLastError());
   }
   {
@@ -744,9 +716,7 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
       });
       if ((rc = push_chal(P, nb))) return rc;
       // fold: next coefficients (length 2^(lg-ab)); only the low 2^(coef_log-ab) can be nonzero
-      qpk::k_fold<<<dim3(cdiv(1ull << (lg - ab), 256), nb), 256, 0, s>>>(coef, P->fcoef[l].p, lg, ab, (uint32_t)l,
-                                                                        P->chal.p, coef_bs, 2ull << (lg - ab),
-                                                                        coef_log);
+      qpk::fold(coef, P->fcoef[l].p, lg, ab, (uint32_t)l, P->chal.p, coef_bs, 2ull << (lg - ab), coef_log, nb, s);
       TRY(hipGetLastError());
       coef = P->fcoef[l].p;
       lg -= ab;
@@ -819,25 +789,21 @@ int prove_batch(qp_prover *P, const uint64_t *d_wires, const uint64_t *const *wi
       Tree *t = trees[o];
       const uint32_t w = t->npolys;
       const uint64_t bs = o == 0 ? 0 : t->lbs(), dbs = o == 0 ? 0 : t->dbs();
-      qpk::k_gather_rows_b<<<dim3(cdiv((uint64_t)w * P->nq, 256), nb), 256, 0, s>>>(t->lde.p, N, bs, w, qi, P->nq, 0,
-                                                                                   P->qout.p + off, obs);
+      qpk::gather_rows(t->lde.p, N, bs, w, qi, P->nq, 0, P->qout.p + off, obs, nb, s);
       off += (uint64_t)w * P->nq;
       const uint32_t depth = logN - P->cap_h;
-      qpk::k_gather_paths_b<<<dim3(cdiv((uint64_t)P->nq * depth * 4, 256), nb), 256, 0, s>>>(
-          t->dig.p, dbs, logN, P->cap_h, qi, P->nq, 0, P->qout.p + off, obs);
+      qpk::gather_paths(t->dig.p, dbs, logN, P->cap_h, qi, P->nq, 0, P->qout.p + off, obs, nb, s);
       off += (uint64_t)P->nq * depth * 4;
     }
     uint32_t lg = logN, shift = 0;
     for (size_t l = 0; l < P->arity.size(); l++) {
       const uint32_t ab = P->arity[l];
       shift += ab;
-      qpk::k_gather_fri_leaf<<<dim3(cdiv((uint64_t)P->nq * (2u << ab), 256), nb), 256, 0, s>>>(
-          P->fvals[l].p, 2ull << lg, lg, ab, qi, P->nq, shift, P->qout.p + off, obs);
+      qpk::gather_fri_leaf(P->fvals[l].p, 2ull << lg, lg, ab, qi, P->nq, shift, P->qout.p + off, obs, nb, s);
       off += (uint64_t)P->nq * (2u << ab);
       const uint32_t depth = lg - ab - P->cap_h;
       const uint64_t dbs = qpk::tree_digest_count(lg - ab, P->cap_h) * 4;
-      qpk::k_gather_paths_b<<<dim3(cdiv((uint64_t)P->nq * depth * 4, 256), nb), 256, 0, s>>>(
-          P->fdig[l].p, dbs, lg - ab, P->cap_h, qi, P->nq, shift, P->qout.p + off, obs);
+      qpk::gather_paths(P->fdig[l].p, dbs, lg - ab, P->cap_h, qi, P->nq, shift, P->qout.p + off, obs, nb, s);
       off += (uint64_t)P->nq * depth * 4;
       lg -= ab;
     }
@@ -977,9 +943,8 @@ int gen_witness_batch(qp_prover *P, uint32_t nb) {
   } else {
     qpk::k_witness_gen<<<nb, wthreads, 0, s>>>(a);
   }
-  qpk::k_witness_expand<<<dim3((unsigned)std::min<uint64_t>(cdiv(nw, 256), 1024), nb), 256, 0, s>>>(
-      P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_wslot_cm.p, nw, P->wires.vals.p, P->wires.cbs(),
-      (const uint32_t *)P->wg_pi_slots.p, P->npis, P->wg_pis.p);
+  qpk::witness_expand(P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_wslot_cm.p, nw, P->wires.vals.p,
+                      P->wires.cbs(), (const uint32_t *)P->wg_pi_slots.p, P->npis, P->wg_pis.p, nb, s);
   TRY(hipGetLastError());
   TRY(hipMemcpyAsync(P->h_werr.data(), P->wg_err.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
   if (P->npis)
@@ -1226,9 +1191,8 @@ int qp_prover_prove(qp_prover *P, const qp_witness *const *w, uint32_t nproofs, 
       memcpy(pis.data() + (size_t)b * P->npis, pi.data(), P->npis * 8);
       pp[b] = pis.data() + (size_t)b * P->npis;
     }
-    qpk::k_witness_expand<<<dim3((unsigned)std::min<uint64_t>(cdiv(nw, 256), 1024), nb), 256, 0, s>>>(
-        P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_wslot_cm.p, nw, P->wires.vals.p, P->wires.cbs(),
-        (const uint32_t *)P->wg_pi_slots.p, P->npis, P->wg_pis.p);
+    qpk::witness_expand(P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_wslot_cm.p, nw, P->wires.vals.p,
+                        P->wires.cbs(), (const uint32_t *)P->wg_pi_slots.p, P->npis, P->wg_pis.p, nb, s);
     TRY(hipGetLastError());
     int rc;
     try {
@@ -1308,8 +1272,7 @@ int qp_prover_debug_drop_table(qp_prover *P, const char *name) {
   DevBuf *d = !strcmp(name, "wg_wslot_cm") ? &P->wg_wslot_cm : !strcmp(name, "wg_gens") ? &P->wg_gens
             : !strcmp(name, "qtab") ? &P->qtab : nullptr;
   if (!d) return QP_ERR_ARG;
-  if (d->p) (void)hipFree(d->p);
-  d->p = nullptr;
+  d->release();
   return QP_OK;
 }
 

@@ -1,7 +1,12 @@
 // prover_kernels.h — argument layouts and launchers of prover_kernels.hip.
+// Every stage of prove() has one launcher, declared next to the kernels it
+// launches: it owns the kernel choice and the grid, block and LDS sizes, and
+// both callers go through it: prove_batch (prover.cpp: nb proofs, per-proof
+// strides) and the seams (seams.cpp, capi.cpp: one proof, strides 0).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "field.h"
 #include "gates.h"
 #include "kernels.h"
 #include "ntt_device.h"
@@ -10,7 +15,7 @@
 
 namespace qpk {
 
-// host helpers shared by the prover and the routine-level seams (prover.cpp)
+// host helpers (prover.cpp)
 std::vector<uint64_t> quotient_point_tables(uint32_t log_n, uint32_t rate_bits);
 void pow_prestate(const uint64_t st12[12], uint32_t pos, uint64_t pre[24]);
 
@@ -28,6 +33,12 @@ enum : uint32_t {
 constexpr uint32_t MAX_FRI_LAYERS = (CH_BETA_INV - CH_FRI_BETA) / 2;
 // the permutation-argument words of the challenge block for challenges beta, gamma
 void perm_challenges(uint64_t *ch, const uint64_t *beta, const uint64_t *gamma, uint32_t nc, uint32_t R, uint32_t qdf);
+// zeta, g * zeta (g = w_n) and their inverses: CH_ZETA .. CH_ZETA_NEXT_INV (zeta != 0)
+void open_point_words(uint64_t *ch, gl::ext zeta, uint32_t log_n);
+// the FRI alpha and alpha^nc: CH_FRI_ALPHA, CH_ALPHA_POW_NC
+void fri_alpha_words(uint64_t *ch, gl::ext alpha, uint32_t nc);
+// apow[i] = alpha^i, i < nterms: one challenge's row of the quotient's table (APOW_STRIDE)
+void alpha_powers(uint64_t *apow, uint64_t alpha, uint32_t nterms);
 constexpr uint32_t OPEN_STRIDE = 520;  // 257 ext openings per proof (+pad)
 constexpr uint32_t APOW_STRIDE = 256;  // alpha_c^i, i < #vanishing terms (per challenge)
 
@@ -98,6 +109,15 @@ __global__ void k_pp_rows_t(const uint64_t *wires, const uint64_t *sigmas, const
 template <bool STAGE>
 __global__ void k_z_scan(const uint64_t *prods, uint64_t *zs, uint32_t log_n, uint32_t nc, uint32_t nchunks,
                          uint64_t p_bstride, uint64_t z_bstride);
+// wires_permutation_partial_products_and_zs for nb proofs: the chunk products
+// of every row (prods: scratch of nc * ceil(R / qdf) * n words per proof; the
+// compile-time kernel for the leaf circuits' shape), then their running
+// product into zs [nc * ceil(R / qdf)][n] per proof (rows staged in LDS up to
+// n = 2^LDS_LOG_MAX, read from HBM above)
+void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t w_bstride, const uint64_t *sigmas,
+                             const uint64_t *k_is, const uint64_t *chal, uint64_t *prods, uint64_t *zs,
+                             uint64_t z_bstride, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint32_t nb,
+                             hipStream_t s);
 __global__ void k_quotient_1r(QuotientArgs a);
 template <int PART>
 __global__ void k_quotient_part(QuotientArgs a, uint32_t gi, uint32_t last);
@@ -156,6 +176,12 @@ __global__ void k_fri_compose(FriComposeArgs a);
 template <int MAXPER>
 __global__ void k_fri_divide(const uint64_t *comp, uint64_t *fin, uint32_t log_n, const uint64_t *chal,
                              uint64_t f_bstride, uint64_t f_cstride);
+// the polynomial FRI starts from (PolynomialBatch::prove_openings) for nb
+// proofs: a.comp (4 n words per proof) = the alpha-reduced oracles, then
+// fin [2][f_cstride] per proof = alpha^nc comp / (X - zeta) + comp_next / (X - g zeta),
+// n coefficients each; 2^6 <= n <= 2^16
+void fri_initial_poly(const FriComposeArgs &a, uint64_t *fin, uint64_t f_bstride, uint64_t f_cstride, uint32_t nb,
+                      hipStream_t s);
 __global__ void k_fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
                            uint64_t d_bstride);
 __global__ void k_fri_leaf_row(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
@@ -172,6 +198,10 @@ void fri_layer_tree(const Twiddles &tw, const uint64_t *coef, uint64_t coef_cstr
                     uint64_t shift, uint32_t nb, hipStream_t s);
 __global__ void k_fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer,
                        const uint64_t *chal, uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz);
+// one FRI fold of nb proofs with beta = the layer's CH_FRI_BETA pair: cin
+// [2][2^log_len] -> cout [2][2^(log_len - ab)]; 2^log_nz: the possibly nonzero prefix of cin
+void fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer, const uint64_t *chal,
+          uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz, uint32_t nb, hipStream_t s);
 __global__ void k_pow_scan(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
                            uint32_t bits, uint64_t limit);
 // fri_proof_of_work's minimal witness per proof in one launch: found[b] = the
@@ -185,5 +215,15 @@ __global__ void k_gather_paths_b(const uint64_t *dig, uint64_t d_bstride, uint32
                                  const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
 __global__ void k_gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab,
                                   const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
+// query openings of nb proofs at leaves idx[b][q] >> shift: rows of an LDE
+// matrix (out[b][q][ncols]), Merkle paths (out[b][q][depth][4], depth =
+// log_leaves - cap_h) and FRI layer leaves (out[b][q][2 << ab]).  Nothing is
+// launched for an empty result (no queries, a tree that is all cap)
+void gather_rows(const uint64_t *cols, uint64_t stride, uint64_t bstride, uint32_t ncols, const uint32_t *idx,
+                 uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s);
+void gather_paths(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, uint32_t cap_h, const uint32_t *idx,
+                  uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s);
+void gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab, const uint32_t *idx,
+                     uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s);
 
 }  // namespace qpk

@@ -26,6 +26,8 @@ namespace qpk {
 
 using gl::ext;
 
+static inline unsigned cdiv(uint64_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }
+
 __device__ __forceinline__ uint64_t wpow_N(const uint64_t *__restrict__ tw, uint32_t j, uint32_t logN) {
   // w_N^j from the half table of w_{2^TW_LOG}: w_N^j = w_T^{j << (TW_LOG-logN)}
   return tw_get(tw, j << (TW_LOG - logN));
@@ -217,6 +219,26 @@ __global__ void __launch_bounds__(1024) k_z_scan(const uint64_t *__restrict__ pr
 }
 template __global__ void k_z_scan<true>(const uint64_t *, uint64_t *, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t);
 template __global__ void k_z_scan<false>(const uint64_t *, uint64_t *, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t);
+
+void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t w_bstride, const uint64_t *sigmas,
+                             const uint64_t *k_is, const uint64_t *chal, uint64_t *prods, uint64_t *zs,
+                             uint64_t z_bstride, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint32_t nb,
+                             hipStream_t s) {
+  const uint32_t n = 1u << log_n, nchunks = (R + qdf - 1) / qdf;
+  const uint64_t pbs = (uint64_t)nc * nchunks * n;
+  const dim3 rows(cdiv(n, 256), nb);
+  // the leaf circuits' shape takes the compile-time kernel
+  if (R == 80 && qdf == 8 && nc == 2)
+    k_pp_rows_t<80, 8><<<rows, 256, 0, s>>>(wires, sigmas, k_is, chal, prods, log_n, w_bstride, pbs, tw.fwd);
+  else
+    k_pp_rows<<<rows, 256, 0, s>>>(wires, sigmas, k_is, chal, prods, log_n, R, qdf, nc, w_bstride, pbs, tw.fwd);
+  // LDS: the T = 1024 partial products, after the staged rows
+  if (log_n <= LDS_LOG_MAX)
+    k_z_scan<true><<<dim3(nc, nb), 1024, 8u * (ntt_lds_words(n) + 1024), s>>>(prods, zs, log_n, nc, nchunks, pbs,
+                                                                               z_bstride);
+  else
+    k_z_scan<false><<<dim3(nc, nb), 1024, 8u * 1024, s>>>(prods, zs, log_n, nc, nchunks, pbs, z_bstride);
+}
 
 // ---------------------------------------------------------------- a8
 //
@@ -1514,6 +1536,19 @@ __global__ void __launch_bounds__(1024) k_fri_divide(const uint64_t *__restrict_
 template __global__ void k_fri_divide<16>(const uint64_t *, uint64_t *, uint32_t, const uint64_t *, uint64_t, uint64_t);
 template __global__ void k_fri_divide<64>(const uint64_t *, uint64_t *, uint32_t, const uint64_t *, uint64_t, uint64_t);
 
+void fri_initial_poly(const FriComposeArgs &a, uint64_t *fin, uint64_t f_bstride, uint64_t f_cstride, uint32_t nb,
+                      hipStream_t s) {
+  const uint64_t n = 1ull << a.log_n;
+  k_fri_compose<<<dim3(cdiv(n, 256), nb), 256, 0, s>>>(a);
+  // k_fri_divide: n / 8 threads up to 1024, n / threads values each (n >= 2^6: at least 8 threads;
+  // <16> holds 16 per thread, n <= 2^14; <64> holds 64, n <= 2^16)
+  const unsigned T = (unsigned)std::min<uint64_t>(1024, n / 8);
+  if (n / T <= 16)
+    k_fri_divide<16><<<nb, T, 0, s>>>(a.comp, fin, a.log_n, a.chal, f_bstride, f_cstride);
+  else
+    k_fri_divide<64><<<nb, 1024, 0, s>>>(a.comp, fin, a.log_n, a.chal, f_bstride, f_cstride);
+}
+
 // FRI layer leaves: leaf i = 2^ab consecutive leaf-order ext values, interleaved c0,c1
 __global__ void __launch_bounds__(256) k_fri_leaf(const uint64_t *__restrict__ vals, uint64_t *__restrict__ dig,
                                                   uint32_t log_len, uint32_t ab, uint64_t v_bstride, uint64_t d_bstride) {
@@ -1618,6 +1653,12 @@ __global__ void __launch_bounds__(256) k_fold(const uint64_t *__restrict__ cin, 
   }
   o[k] = acc.c0;
   o[nout + k] = acc.c1;
+}
+
+void fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer, const uint64_t *chal,
+          uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz, uint32_t nb, hipStream_t s) {
+  k_fold<<<dim3(cdiv(1ull << (log_len - ab), 256), nb), 256, 0, s>>>(cin, cout, log_len, ab, layer, chal, i_bstride,
+                                                                     o_bstride, log_nz);
 }
 
 // ---------------------------------------------------------------- a12
@@ -1728,6 +1769,29 @@ __global__ void k_gather_fri_leaf(const uint64_t *__restrict__ vals, uint64_t v_
   const uint64_t leaf = idx[b * nq + q] >> shift;
   const uint64_t L = 1ull << log_len;
   out[b * o_bstride + t] = vals[b * v_bstride + (e & 1) * L + (leaf << ab) + (e >> 1)];
+}
+
+void gather_rows(const uint64_t *cols, uint64_t stride, uint64_t bstride, uint32_t ncols, const uint32_t *idx,
+                 uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
+  const uint64_t tot = (uint64_t)ncols * nq;
+  if (!tot) return;
+  k_gather_rows_b<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(cols, stride, bstride, ncols, idx, nq, shift, out, o_bstride);
+}
+
+void gather_paths(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, uint32_t cap_h, const uint32_t *idx,
+                  uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
+  const uint64_t tot = (uint64_t)nq * (log_leaves - cap_h) * 4;
+  if (!tot) return;
+  k_gather_paths_b<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(dig, d_bstride, log_leaves, cap_h, idx, nq, shift, out,
+                                                            o_bstride);
+}
+
+void gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab, const uint32_t *idx,
+                     uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
+  const uint64_t tot = (uint64_t)nq * (2u << ab);
+  if (!tot) return;
+  k_gather_fri_leaf<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(vals, v_bstride, log_len, ab, idx, nq, shift, out,
+                                                             o_bstride);
 }
 
 }  // namespace qpk

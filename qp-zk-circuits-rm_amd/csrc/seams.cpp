@@ -28,38 +28,18 @@
 
 namespace {
 
-struct DMem {  // device allocation owned by one call
-  uint64_t *p = nullptr;
-  hipError_t alloc(size_t words) { return hipMalloc(&p, (words ? words : 1) * 8); }
-  ~DMem() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-inline unsigned cdiv(uint64_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }
-
 // degrees of the circuit-level seams (qp_quotient's): k_fri_divide runs n / 8
 // threads and holds at most 64 values per thread, k_z_scan has its two forms
 constexpr uint32_t SEAM_LOG_MIN = 6, SEAM_LOG_MAX = qpk::BIG_LOG_MAX - 1;
 constexpr uint32_t PP_MAX_CHUNKS = 16;  // k_pp_rows' per-row chunk arrays
 
-// zeta, g*zeta and their inverses: the opening words of a one-proof challenge block
-struct OpenPoint {
-  gl::ext z, zn, zi, zni;
-  void fill(uint64_t *ch) const {
-    ch[qpk::CH_ZETA] = z.c0; ch[qpk::CH_ZETA + 1] = z.c1;
-    ch[qpk::CH_ZETA_NEXT] = zn.c0; ch[qpk::CH_ZETA_NEXT + 1] = zn.c1;
-    ch[qpk::CH_ZETA_INV] = zi.c0; ch[qpk::CH_ZETA_INV + 1] = zi.c1;
-    ch[qpk::CH_ZETA_NEXT_INV] = zni.c0; ch[qpk::CH_ZETA_NEXT_INV + 1] = zni.c1;
-  }
-};
-
 // the shared preconditions of qp_opening_set and qp_fri_initial_poly: four
 // batches (constants||sigmas, wires, Zs||partial products, quotient) of ctx,
 // of one proof, unsalted, holding coefficients of one degree 2^6..2^15; 1 or 2
-// challenges with their Zs present; zeta invertible and outside H
+// challenges with their Zs present; zeta invertible and outside H.  Fills the
+// opening words of the one-proof challenge block ch
 int check_circuit_batches(qp_ctx *ctx, const char *fn, const qp_batch *const bt[4], uint32_t nc,
-                          const uint64_t *zeta, const void *out, OpenPoint *pt) {
+                          const uint64_t *zeta, const void *out, uint64_t *ch) {
   auto fail = [&](const char *why) {
     ctx->err = std::string(fn) + ": " + why;
     return (int)QP_ERR_ARG;
@@ -79,10 +59,7 @@ int check_circuit_batches(qp_ctx *ctx, const char *fn, const qp_batch *const bt[
   if (!(z.c0 | z.c1)) return fail("zeta = 0");
   const gl::ext zn_pow = gl::ext_pow(z, 1ull << log_n);
   if (zn_pow.c0 == 1 && zn_pow.c1 == 0) return fail("zeta^n = 1 (an opening point inside the subgroup)");
-  pt->z = z;
-  pt->zn = gl::ext_scale(z, gl::root_of_unity(log_n));
-  pt->zi = gl::ext_inv(z);
-  pt->zni = gl::ext_inv(pt->zn);
+  qpk::open_point_words(ch, z, log_n);
   return QP_OK;
 }
 
@@ -91,23 +68,15 @@ int check_circuit_batches(qp_ctx *ctx, const char *fn, const qp_batch *const bt[
 struct qp_perm {
   qp_ctx *ctx = nullptr;
   uint32_t R = 0, log_n = 0;
-  uint64_t *d_sigmas = nullptr;  // [R][n] values over H
-  uint64_t *d_kis = nullptr;     // [R]
-  ~qp_perm() {
-    if (d_sigmas) (void)hipFree(d_sigmas);
-    if (d_kis) (void)hipFree(d_kis);
-  }
+  DevBuf sigmas;  // [R][n] values over H
+  DevBuf kis;     // [R]
 };
 
 struct qp_fri_layer {
   qp_ctx *ctx = nullptr;
   uint32_t log_values = 0, arity_bits = 0, cap_h = 0;
-  uint64_t *d_vals = nullptr;  // [2][2^log_values] leaf order (c0 row, c1 row)
-  uint64_t *d_dig = nullptr;   // tree digests over 2^(log_values - arity_bits) leaves
-  ~qp_fri_layer() {
-    if (d_vals) (void)hipFree(d_vals);
-    if (d_dig) (void)hipFree(d_dig);
-  }
+  DevBuf vals;  // [2][2^log_values] leaf order (c0 row, c1 row)
+  DevBuf dig;   // tree digests over 2^(log_values - arity_bits) leaves
 };
 
 extern "C" {
@@ -191,15 +160,11 @@ int qp_quotient(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const qp
     for (uint32_t c = 0; c < 2; c++) {
       chal[qpk::CH_BETA + c] = gl::canon(betas[c]);
       chal[qpk::CH_GAMMA + c] = gl::canon(gammas[c]);
-      uint64_t p = 1;
-      for (uint32_t i = 0; i < nterms; i++) {
-        apow[c * qpk::APOW_STRIDE + i] = p;
-        p = gl::mul(p, gl::canon(alphas[c]));
-      }
+      qpk::alpha_powers(apow.data() + c * qpk::APOW_STRIDE, gl::canon(alphas[c]), nterms);
     }
     qpk::perm_challenges(chal.data(), chal.data() + qpk::CH_BETA, chal.data() + qpk::CH_GAMMA, 2, R, qdf);
     for (int i = 0; i < 4; i++) chal[qpk::CH_PIH + i] = gl::canon(pi_hash[i]);
-    DMem d_tab, d_chal, d_apow, d_q, d_cbuf, d_out;
+    DevBuf d_tab, d_chal, d_apow, d_q, d_cbuf, d_out;
     QP_HIP_TRY(ctx, d_tab.alloc(tab.size()));
     QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
     QP_HIP_TRY(ctx, d_apow.alloc(apow.size()));
@@ -277,11 +242,11 @@ int qp_fri_layer_commit(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs
   L->log_values = log_values;
   L->arity_bits = arity_bits;
   L->cap_h = cap_height;
-  DMem d_c;
+  DevBuf d_c;
   const uint64_t dbs = qpk::tree_digest_count(log_leaves, cap_height) * 4;
   hipError_t e = d_c.alloc(2 * Lc);
-  if (!e) e = hipMalloc(&L->d_vals, 2 * Lv * 8);
-  if (!e) e = hipMalloc(&L->d_dig, dbs * 8);
+  if (!e) e = L->vals.alloc(2 * Lv);
+  if (!e) e = L->dig.alloc(dbs);
   if (e) {
     delete L;
     ctx->err = std::string("qp_fri_layer_commit: ") + hipGetErrorString(e);
@@ -290,12 +255,12 @@ int qp_fri_layer_commit(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs
   e = hipMemcpy2DAsync(d_c.p, Lc * 8, coeffs, Lin * 8, Lc * 8, 2, hipMemcpyHostToDevice, s);
   if (!e) {
     // values = coset_fft(coeffs, shift), leaf (bit-reversed) order, and their tree
-    qpk::fri_layer_tree(ctx->tw, d_c.p, Lc, 2 * Lc, lc, L->d_vals, L->d_dig, log_values, arity_bits, cap_height, shift,
+    qpk::fri_layer_tree(ctx->tw, d_c.p, Lc, 2 * Lc, lc, L->vals.p, L->dig.p, log_values, arity_bits, cap_height, shift,
                         1, s);
     e = hipGetLastError();
   }
   if (!e)
-    e = hipMemcpyAsync(cap_out, L->d_dig + qpk::tree_level_offset(log_leaves, log_leaves - cap_height) * 4,
+    e = hipMemcpyAsync(cap_out, L->dig.p + qpk::tree_level_offset(log_leaves, log_leaves - cap_height) * 4,
                        (size_t)32 << cap_height, hipMemcpyDeviceToHost, s);
   if (!e) e = hipStreamSynchronize(s);
   if (e) {
@@ -321,17 +286,13 @@ int qp_fri_layer_open(qp_fri_layer *L, const uint32_t *idx, uint32_t nidx, uint6
   QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const uint32_t W = 2u << L->arity_bits, depth = log_leaves - L->cap_h;
-  DMem d_idx, d_ev, d_sib;
+  DevBuf d_idx, d_ev, d_sib;
   QP_HIP_TRY(ctx, d_idx.alloc((nidx + 1) / 2));
   QP_HIP_TRY(ctx, d_ev.alloc((uint64_t)nidx * W));
   QP_HIP_TRY(ctx, d_sib.alloc((uint64_t)nidx * depth * 4));
   QP_HIP_TRY(ctx, hipMemcpyAsync(d_idx.p, idx, nidx * 4ull, hipMemcpyHostToDevice, s));
-  const uint64_t dbs = qpk::tree_digest_count(log_leaves, L->cap_h) * 4;
-  qpk::k_gather_fri_leaf<<<dim3(cdiv((uint64_t)nidx * W, 256), 1), 256, 0, s>>>(
-      L->d_vals, 2ull << L->log_values, L->log_values, L->arity_bits, (const uint32_t *)d_idx.p, nidx, 0, d_ev.p, 0);
-  if (depth)
-    qpk::k_gather_paths_b<<<dim3(cdiv((uint64_t)nidx * depth * 4, 256), 1), 256, 0, s>>>(
-        L->d_dig, dbs, log_leaves, L->cap_h, (const uint32_t *)d_idx.p, nidx, 0, d_sib.p, 0);
+  qpk::gather_fri_leaf(L->vals.p, 0, L->log_values, L->arity_bits, d_idx.as<uint32_t>(), nidx, 0, d_ev.p, 0, 1, s);
+  qpk::gather_paths(L->dig.p, 0, log_leaves, L->cap_h, d_idx.as<uint32_t>(), nidx, 0, d_sib.p, 0, 1, s);
   QP_HIP_TRY(ctx, hipGetLastError());
   QP_HIP_TRY(ctx, hipMemcpyAsync(evals_out, d_ev.p, (uint64_t)nidx * W * 8, hipMemcpyDeviceToHost, s));
   if (depth)
@@ -352,14 +313,13 @@ int qp_fri_fold(qp_ctx *ctx, const uint64_t *coeffs, uint32_t log_coeffs, uint32
   std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
   chal[qpk::CH_FRI_BETA] = gl::canon(beta[0]);
   chal[qpk::CH_FRI_BETA + 1] = gl::canon(beta[1]);
-  DMem d_in, d_out, d_chal;
+  DevBuf d_in, d_out, d_chal;
   QP_HIP_TRY(ctx, d_in.alloc(2 * L));
   QP_HIP_TRY(ctx, d_out.alloc(2 * Lo));
   QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
   QP_HIP_TRY(ctx, hipMemcpyAsync(d_in.p, coeffs, 2 * L * 8, hipMemcpyHostToDevice, s));
   QP_HIP_TRY(ctx, hipMemcpyAsync(d_chal.p, chal.data(), chal.size() * 8, hipMemcpyHostToDevice, s));
-  qpk::k_fold<<<dim3(cdiv(Lo, 256), 1), 256, 0, s>>>(d_in.p, d_out.p, log_coeffs, arity_bits, 0, d_chal.p, 2 * L,
-                                                     2 * Lo, log_coeffs);
+  qpk::fold(d_in.p, d_out.p, log_coeffs, arity_bits, 0, d_chal.p, 0, 0, log_coeffs, 1, s);
   QP_HIP_TRY(ctx, hipGetLastError());
   QP_HIP_TRY(ctx, hipMemcpyAsync(coeffs_out, d_out.p, 2 * Lo * 8, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -383,7 +343,7 @@ int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint3
       for (int i = 0; i < 12; i++) st[i] = gl::canon(states[(size_t)b * 12 + i]);
       qpk::pow_prestate(st, pos[b], pre.data() + (size_t)b * 24);
     }
-    DMem d_pre, d_pos, d_next, d_found;
+    DevBuf d_pre, d_pos, d_next, d_found;
     QP_HIP_TRY(ctx, d_pre.alloc(pre.size()));
     QP_HIP_TRY(ctx, d_pos.alloc((n + 1) / 2));
     QP_HIP_TRY(ctx, d_next.alloc(n));
@@ -391,7 +351,7 @@ int qp_pow_grind(qp_ctx *ctx, const uint64_t *states, const uint32_t *pos, uint3
     QP_HIP_TRY(ctx, hipMemcpyAsync(d_pre.p, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, s));
     QP_HIP_TRY(ctx, hipMemcpyAsync(d_pos.p, pos, n * 4ull, hipMemcpyHostToDevice, s));
     // the prover's single-launch minimal-witness search (prover.cpp stage 6)
-    QP_HIP_TRY(ctx, qpk::pow_search(d_pre.p, (const uint32_t *)d_pos.p, d_found.p, d_next.p, n, pow_bits, s));
+    QP_HIP_TRY(ctx, qpk::pow_search(d_pre.p, d_pos.as<uint32_t>(), d_found.p, d_next.p, n, pow_bits, s));
     QP_HIP_TRY(ctx, hipMemcpyAsync(found.data(), d_found.p, n * 8ull, hipMemcpyDeviceToHost, s));
     QP_HIP_TRY(ctx, hipStreamSynchronize(s));
     for (uint32_t b = 0; b < n; b++)
@@ -433,10 +393,10 @@ int qp_perm_new(qp_ctx *ctx, const uint64_t *sigmas, const uint64_t *k_is, uint3
   const uint64_t n = 1ull << log_n;
   std::vector<uint64_t> k(num_routed);
   for (uint32_t j = 0; j < num_routed; j++) k[j] = gl::canon(k_is[j]);
-  hipError_t e = hipMalloc(&p->d_sigmas, (size_t)num_routed * n * 8);
-  if (!e) e = hipMalloc(&p->d_kis, (size_t)num_routed * 8);
-  if (!e) e = hipMemcpyAsync(p->d_sigmas, sigmas, (size_t)num_routed * n * 8, hipMemcpyHostToDevice, ctx->stream);
-  if (!e) e = hipMemcpyAsync(p->d_kis, k.data(), (size_t)num_routed * 8, hipMemcpyHostToDevice, ctx->stream);
+  hipError_t e = p->sigmas.alloc((size_t)num_routed * n);
+  if (!e) e = p->kis.alloc(num_routed);
+  if (!e) e = hipMemcpyAsync(p->sigmas.p, sigmas, (size_t)num_routed * n * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (!e) e = hipMemcpyAsync(p->kis.p, k.data(), (size_t)num_routed * 8, hipMemcpyHostToDevice, ctx->stream);
   if (!e) e = hipStreamSynchronize(ctx->stream);
   if (e) {
     delete p;
@@ -473,25 +433,16 @@ int qp_partial_products_and_zs(qp_perm *p, const uint64_t *wires, uint32_t qdf, 
     chal[qpk::CH_GAMMA + c] = gl::canon(gammas[c]);
   }
   qpk::perm_challenges(chal.data(), chal.data() + qpk::CH_BETA, chal.data() + qpk::CH_GAMMA, nc, R, qdf);
-  DMem d_w, d_prods, d_zs, d_chal;
+  DevBuf d_w, d_prods, d_zs, d_chal;
   QP_HIP_TRY(ctx, d_w.alloc((uint64_t)R * n));
   QP_HIP_TRY(ctx, d_prods.alloc(pbs));
   QP_HIP_TRY(ctx, d_zs.alloc(pbs));
   QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
   QP_HIP_TRY(ctx, hipMemcpyAsync(d_w.p, wires, (uint64_t)R * n * 8, hipMemcpyHostToDevice, s));
   QP_HIP_TRY(ctx, hipMemcpyAsync(d_chal.p, chal.data(), chal.size() * 8, hipMemcpyHostToDevice, s));
-  // prover.cpp stage 2: the leaf circuits' shape takes the compile-time kernel
-  if (R == 80 && qdf == 8 && nc == 2)
-    qpk::k_pp_rows_t<80, 8><<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(d_w.p, p->d_sigmas, p->d_kis, d_chal.p, d_prods.p,
-                                                                   log_n, 0, 0, ctx->tw.fwd);
-  else
-    qpk::k_pp_rows<<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(d_w.p, p->d_sigmas, p->d_kis, d_chal.p, d_prods.p, log_n, R,
-                                                          qdf, nc, 0, 0, ctx->tw.fwd);
-  if (log_n <= qpk::LDS_LOG_MAX)
-    qpk::k_z_scan<true><<<dim3(nc, 1), 1024, 8u * (qpk::ntt_lds_words(n) + 1024), s>>>(d_prods.p, d_zs.p, log_n, nc,
-                                                                                         nchunks, 0, 0);
-  else
-    qpk::k_z_scan<false><<<dim3(nc, 1), 1024, 8u * 1024, s>>>(d_prods.p, d_zs.p, log_n, nc, nchunks, 0, 0);
+  // prover.cpp stage 2
+  qpk::partial_products_and_zs(ctx->tw, d_w.p, 0, p->sigmas.p, p->kis.p, d_chal.p, d_prods.p, d_zs.p, 0, log_n, R, qdf,
+                               nc, 1, s);
   QP_HIP_TRY(ctx, hipGetLastError());
   QP_HIP_TRY(ctx, hipMemcpyAsync(zs_pp_out, d_zs.p, pbs * 8, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -502,8 +453,8 @@ int qp_opening_set(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const
                    const qp_batch *quotient, uint32_t nc, const uint64_t zeta[2], uint64_t *out) {
   if (!ctx) return QP_ERR_ARG;
   const qp_batch *bt[4] = {cs, wires, zs_pp, quotient};
-  OpenPoint pt;
-  int rc = check_circuit_batches(ctx, "qp_opening_set", bt, nc, zeta, out, &pt);
+  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
+  int rc = check_circuit_batches(ctx, "qp_opening_set", bt, nc, zeta, out, chal.data());
   if (rc) return rc;
   const uint32_t log_n = cs->log_n;
   const uint64_t total = (uint64_t)cs->npolys + wires->npolys + zs_pp->npolys + quotient->npolys + nc;
@@ -513,9 +464,7 @@ int qp_opening_set(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, const
   }
   QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
-  pt.fill(chal.data());
-  DMem d_chal, d_out, d_part;
+  DevBuf d_chal, d_out, d_part;
   QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
   QP_HIP_TRY(ctx, d_out.alloc(qpk::OPEN_STRIDE));
   QP_HIP_TRY(ctx, d_part.alloc((uint64_t)qpk::OPEN_MAX_SLICES * qpk::OPEN_STRIDE));
@@ -577,7 +526,7 @@ int qp_batch_eval_ext(const qp_batch *b, uint32_t first, uint32_t npolys, const 
     for (size_t i = 0; i < pts.size(); i++) pts[i] = gl::canon(points[i]);
     QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    DMem d_pts, d_out, d_part;
+    DevBuf d_pts, d_out, d_part;
     QP_HIP_TRY(ctx, d_pts.alloc(pts.size()));
     QP_HIP_TRY(ctx, d_out.alloc(res.size()));
     QP_HIP_TRY(ctx, d_part.alloc((uint64_t)qpk::OPEN_MAX_SLICES * qpk::OPEN_STRIDE));
@@ -607,8 +556,8 @@ int qp_fri_initial_poly(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, 
                         uint64_t *coeffs_out) {
   if (!ctx) return QP_ERR_ARG;
   const qp_batch *bt[4] = {cs, wires, zs_pp, quotient};
-  OpenPoint pt;
-  int rc = check_circuit_batches(ctx, "qp_fri_initial_poly", bt, nc, zeta, coeffs_out, &pt);
+  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
+  int rc = check_circuit_batches(ctx, "qp_fri_initial_poly", bt, nc, zeta, coeffs_out, chal.data());
   if (rc) return rc;
   if (!alpha) {
     ctx->err = "qp_fri_initial_poly: null argument";
@@ -618,14 +567,8 @@ int qp_fri_initial_poly(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, 
   const uint64_t n = 1ull << log_n;
   QP_HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  std::vector<uint64_t> chal(qpk::CHAL_STRIDE, 0);
-  pt.fill(chal.data());
-  const gl::ext al{gl::canon(alpha[0]), gl::canon(alpha[1])}, ap = gl::ext_pow(al, nc);
-  chal[qpk::CH_FRI_ALPHA] = al.c0;
-  chal[qpk::CH_FRI_ALPHA + 1] = al.c1;
-  chal[qpk::CH_ALPHA_POW_NC] = ap.c0;
-  chal[qpk::CH_ALPHA_POW_NC + 1] = ap.c1;
-  DMem d_chal, d_comp, d_fin;
+  qpk::fri_alpha_words(chal.data(), gl::ext{gl::canon(alpha[0]), gl::canon(alpha[1])}, nc);
+  DevBuf d_chal, d_comp, d_fin;
   QP_HIP_TRY(ctx, d_chal.alloc(chal.size()));
   QP_HIP_TRY(ctx, d_comp.alloc(4 * n));
   QP_HIP_TRY(ctx, d_fin.alloc(2 * n));
@@ -642,14 +585,7 @@ int qp_fri_initial_poly(qp_ctx *ctx, const qp_batch *cs, const qp_batch *wires, 
   fa.log_n = log_n;
   fa.chal = d_chal.p;
   fa.comp = d_comp.p;
-  qpk::k_fri_compose<<<dim3(cdiv(n, 256), 1), 256, 0, s>>>(fa);
-  // k_fri_divide: n / 8 threads up to 1024, n / threads values each (n >= 2^6: at least 8 threads;
-  // <16> holds 16 per thread, n <= 2^14; <64> holds 64, n <= 2^16)
-  const unsigned T = (unsigned)std::min<uint64_t>(1024, n / 8);
-  if (n / T <= 16)
-    qpk::k_fri_divide<16><<<1, T, 0, s>>>(d_comp.p, d_fin.p, log_n, d_chal.p, 0, n);
-  else
-    qpk::k_fri_divide<64><<<1, 1024, 0, s>>>(d_comp.p, d_fin.p, log_n, d_chal.p, 0, n);
+  qpk::fri_initial_poly(fa, d_fin.p, 0, n, 1, s);
   QP_HIP_TRY(ctx, hipGetLastError());
   QP_HIP_TRY(ctx, hipMemcpyAsync(coeffs_out, d_fin.p, 2 * n * 8, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(ctx, hipStreamSynchronize(s));

@@ -451,15 +451,6 @@ uint32_t reduce_proof(const Dims &d, uint32_t nb, uint32_t s, const uint8_t *ok,
   return QP_VERIFY_OK;
 }
 
-#define QV_HIP(v, expr)                                                          \
-  do {                                                                           \
-    hipError_t _e = (expr);                                                      \
-    if (_e != hipSuccess) {                                                      \
-      (v)->err = std::string(#expr) + ": " + hipGetErrorString(_e);              \
-      return _e == hipErrorOutOfMemory ? QP_ERR_OOM : QP_ERR_HIP;                \
-    }                                                                            \
-  } while (0)
-
 int verify_chunk(qp_verifier *V, const uint8_t *const *proofs, const size_t *lens, uint32_t nb, uint32_t *status) {
   const Dims &d = V->d;
   const Layout L = make_layout(d, nb);
@@ -486,16 +477,16 @@ int verify_chunk(qp_verifier *V, const uint8_t *const *proofs, const size_t *len
   qv::FriJob fj;
   if (V->ctx) {
     qp_ctx *c = V->ctx;
-    QV_HIP(V, hipSetDevice(c->device));
-    QV_HIP(V, hipMemcpyAsync(V->d_buf, buf, L.words * 8, hipMemcpyHostToDevice, c->stream));
+    QP_HIP_TRY(V, hipSetDevice(c->device));
+    QP_HIP_TRY(V, hipMemcpyAsync(V->d_buf, buf, L.words * 8, hipMemcpyHostToDevice, c->stream));
     make_jobs(V, L, nb, V->d_buf, V->d_ok, V->d_code, pj, fj);
     qv::launch_paths(pj, c->stream);
-    QV_HIP(V, hipGetLastError());
+    QP_HIP_TRY(V, hipGetLastError());
     qv::launch_fri(fj, c->stream);
-    QV_HIP(V, hipGetLastError());
-    QV_HIP(V, hipMemcpyAsync(V->h_ok.data(), V->d_ok, (size_t)lanes * d.ncls, hipMemcpyDeviceToHost, c->stream));
-    QV_HIP(V, hipMemcpyAsync(V->h_code.data(), V->d_code, (size_t)lanes * 4, hipMemcpyDeviceToHost, c->stream));
-    QV_HIP(V, hipStreamSynchronize(c->stream));
+    QP_HIP_TRY(V, hipGetLastError());
+    QP_HIP_TRY(V, hipMemcpyAsync(V->h_ok.data(), V->d_ok, (size_t)lanes * d.ncls, hipMemcpyDeviceToHost, c->stream));
+    QP_HIP_TRY(V, hipMemcpyAsync(V->h_code.data(), V->d_code, (size_t)lanes * 4, hipMemcpyDeviceToHost, c->stream));
+    QP_HIP_TRY(V, hipStreamSynchronize(c->stream));
   } else {
     make_jobs(V, L, nb, buf, V->h_ok.data(), V->h_code.data(), pj, fj);
     // one task per (proof, tree) and one per proof's arithmetic
@@ -575,11 +566,11 @@ int qp_verifier_new(qp_ctx *ctx, const uint8_t *verifier_only, size_t vlen, cons
     V->h_ok.assign(lanes * d.ncls, 0);
     V->h_code.assign(lanes, 0);
     if (ctx) {
-      QV_HIP(V, hipSetDevice(ctx->device));
-      QV_HIP(V, hipHostMalloc((void **)&V->h_buf, L.words * 8, hipHostMallocDefault));
-      QV_HIP(V, hipMalloc(&V->d_buf, L.words * 8));
-      QV_HIP(V, hipMalloc(&V->d_ok, lanes * d.ncls));
-      QV_HIP(V, hipMalloc(&V->d_code, lanes * 4));
+      QP_HIP_TRY(V, hipSetDevice(ctx->device));
+      QP_HIP_TRY(V, hipHostMalloc((void **)&V->h_buf, L.words * 8, hipHostMallocDefault));
+      QP_HIP_TRY(V, hipMalloc(&V->d_buf, L.words * 8));
+      QP_HIP_TRY(V, hipMalloc(&V->d_ok, lanes * d.ncls));
+      QP_HIP_TRY(V, hipMalloc(&V->d_code, lanes * 4));
     } else {
       V->h_buf = new uint64_t[L.words];
     }

@@ -56,10 +56,11 @@ extern "C" int qp_merkle_verify(qp_ctx *c, const uint64_t *leaves, uint32_t widt
   QP_HIP_TRY(c, hipSetDevice(c->device));
   const size_t lw = (size_t)n * width, sw = (size_t)n * nsib * 4, cw = (size_t)4 << cap_height;
   const size_t words = lw + sw + cw + (n + 1) / 2;
-  uint64_t *d = nullptr;
-  uint8_t *d_ok = nullptr;
-  hipError_t e = hipMalloc(&d, words * 8);
-  if (!e) e = hipMalloc(&d_ok, n);
+  DevBuf buf, ok;
+  hipError_t e = buf.alloc(words);
+  if (!e) e = ok.alloc(((size_t)n + 7) / 8);  // one byte per path
+  uint64_t *const d = buf.p;
+  uint8_t *const d_ok = ok.as<uint8_t>();
   if (!e) e = hipMemcpyAsync(d, leaves, lw * 8, hipMemcpyHostToDevice, c->stream);
   if (!e && sw) e = hipMemcpyAsync(d + lw, siblings, sw * 8, hipMemcpyHostToDevice, c->stream);
   if (!e) e = hipMemcpyAsync(d + lw + sw, cap, cw * 8, hipMemcpyHostToDevice, c->stream);
@@ -76,8 +77,6 @@ extern "C" int qp_merkle_verify(qp_ctx *c, const uint64_t *leaves, uint32_t widt
   }
   if (!e) e = hipMemcpyAsync(ok_out, d_ok, n, hipMemcpyDeviceToHost, c->stream);
   if (!e) e = hipStreamSynchronize(c->stream);
-  if (d) (void)hipFree(d);
-  if (d_ok) (void)hipFree(d_ok);
   QP_HIP_TRY(c, e);
   return QP_OK;
 }

@@ -497,4 +497,12 @@ __global__ void k_witness_expand(const uint64_t *vals, uint64_t v_bstride, const
   }
 }
 
+void witness_expand(const uint64_t *vals, uint64_t v_bstride, const uint32_t *wslot_cm, uint64_t nwires,
+                    uint64_t *wires, uint64_t w_bstride, const uint32_t *pi_slots, uint32_t npis, uint64_t *pis,
+                    uint32_t nb, hipStream_t s) {
+  const uint64_t blocks = (nwires + 255) / 256;  // grid-stride above 1024
+  k_witness_expand<<<dim3(blocks < 1024 ? (unsigned)blocks : 1024u, nb), 256, 0, s>>>(vals, v_bstride, wslot_cm, nwires, wires, w_bstride, pi_slots, npis,
+                                                    pis);
+}
+
 }  // namespace qpk

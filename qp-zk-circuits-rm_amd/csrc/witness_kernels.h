@@ -29,5 +29,9 @@ __global__ void k_witness_level(const WitnessGenArgs a, uint32_t l, uint32_t na)
 __global__ void k_witness_expand(const uint64_t *vals, uint64_t v_bstride, const uint32_t *wslot_cm, uint64_t nwires,
                                  uint64_t *wires, uint64_t w_bstride, const uint32_t *pi_slots, uint32_t npis,
                                  uint64_t *pis);
+// slot values of nb proofs -> their wire matrices and public inputs (device- and host-generated witnesses)
+void witness_expand(const uint64_t *vals, uint64_t v_bstride, const uint32_t *wslot_cm, uint64_t nwires,
+                    uint64_t *wires, uint64_t w_bstride, const uint32_t *pi_slots, uint32_t npis, uint64_t *pis,
+                    uint32_t nb, hipStream_t s);
 
 }  // namespace qpk

@@ -83,6 +83,7 @@ def test_lde_leaf_order(ctx, log_n, rate_bits):
     (20, 9, 3, 4, 0),
     (84, 8, 3, 4, 0),    # constants||sigmas width
     (135, 8, 3, 4, 4),   # salted wires width 139
+    (2, 3, 1, 4, 0),     # cap_h = log N: the tree is all cap, depth 0, no siblings to gather
 ])
 def test_commit_values_parity(ctx, npolys, log_n, rate_bits, cap_h, nsalt):
     import qp_wormhole
@@ -105,7 +106,7 @@ def test_commit_values_parity(ctx, npolys, log_n, rate_bits, cap_h, nsalt):
     olib().ora_merkle(np.ascontiguousarray(leaves_o), log_n + rate_bits, leaves_o.shape[1], cap_h, cap2,
                       idx.astype(np.uint64), len(idx), sib_o)
     assert (cap2 == cap_o).all()
-    assert (sibs == sib_o).all()
+    assert sibs.shape == sib_o.shape and (sibs == sib_o).all()
     b.free()
 
 
