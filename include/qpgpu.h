@@ -315,7 +315,8 @@ int qp_prover_debug_drop_table(qp_prover *p, const char *name);
  * (csrc/field_probe.hip).  Lane i applies `op` to a[i], b[i] and stores the
  * RAW result (no canonicalisation) to out[i]; the kernel calls the functions
  * the production kernels call (ntt16.h nt::, field_nc.h gfn::,
- * poseidon_fast.h pf::, field.h gl::).  The operands must respect the
+ * poseidon_fast.h pf::, field.h gl::; the op names keep the namespace the
+ * function had when the probe was written).  The operands must respect the
  * function's own contract (noted per op); the probe does not check them.
  * The 4-wide and K-wide forms take a group of consecutive elements per lane
  * (n a multiple of the group size) and store the group's results in place,
@@ -329,7 +330,7 @@ enum {
     QP_FOP_GFN_ADD_C,         /* gfn::add_c: b < p                                         */
     QP_FOP_PF_ADD_C,          /* pf::add_c: b < p                                          */
     QP_FOP_GL_ADD,            /* gl::add: a, b < p; result < p                             */
-    QP_FOP_NT_SUB,            /* nt::sub = gfn::sub: a - b, any u64                        */
+    QP_FOP_NT_SUB,            /* nt::sub (gfn::sub by name): a - b, any u64                */
     QP_FOP_NT_SUB4,           /* nt::sub4: groups of 4                                     */
     QP_FOP_GL_SUB,            /* gl::sub: a, b < p; result < p                             */
     QP_FOP_NT_REDUCE,         /* nt::reduce(lo = a, hi = b)                                */
@@ -338,10 +339,10 @@ enum {
     QP_FOP_PF_REDUCE_ROW,     /* pf::reduce_row(al = a, ah = b): a, b < 2^42               */
     QP_FOP_PF_REDUCE_ROW_C,   /* pf::reduce_row_c, same operands                           */
     QP_FOP_PF_SUB_SMALL,      /* pf::sub_small(r = a, y = b): b < 2^40                     */
-    QP_FOP_PF_MUL,            /* pf::mul                                                   */
-    QP_FOP_PF_MUL_C,          /* pf::mul_c                                                 */
-    QP_FOP_PF_MULK2,          /* pf::mulk<2>: groups of 2                                  */
-    QP_FOP_PF_MULK3,          /* pf::mulk<3>: groups of 3                                  */
+    QP_FOP_PF_MUL,            /* gfn::mul (pf::mul, nt::mul by name)                       */
+    QP_FOP_PF_MUL_C,          /* gfn::mul_c                                                */
+    QP_FOP_PF_MULK2,          /* gfn::mulk<2>: groups of 2                                 */
+    QP_FOP_PF_MULK3,          /* gfn::mulk<3>: groups of 3                                 */
     QP_FOP_GL_MUL,            /* gl::mul (device mul_wide); result < p                     */
     QP_FOP_PF_SBOX,           /* pf::sbox(a) = a^7                                         */
     QP_FOP_PF_SBOX_C,         /* pf::sbox_c(a)                                             */

@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) k_field_op(const uint64_t *__restrict__ a
         x[i] = a[K * g + i];
         y[i] = b[K * g + i];
       }
-      pf::mulk<K>(x, y, r);
+      gfn::mulk<K>(x, y, r);
 #pragma unroll
       for (int i = 0; i < K; i++) out[K * g + i] = r[i];
     } else if constexpr (OP == QP_FOP_ACC3) {
@@ -88,9 +88,9 @@ __global__ void __launch_bounds__(256) k_field_op(const uint64_t *__restrict__ a
       else if constexpr (OP == QP_FOP_GL_REDUCE128) r = gl::reduce128(x, y);
       else if constexpr (OP == QP_FOP_PF_REDUCE_ROW) r = pf::reduce_row(x, y);
       else if constexpr (OP == QP_FOP_PF_REDUCE_ROW_C) r = pf::reduce_row_c(x, y);
-      else if constexpr (OP == QP_FOP_PF_SUB_SMALL) r = pf::sub_small(x, pf::lo32(y), pf::hi32(y));
-      else if constexpr (OP == QP_FOP_PF_MUL) r = pf::mul(x, y);
-      else if constexpr (OP == QP_FOP_PF_MUL_C) r = pf::mul_c(x, y);
+      else if constexpr (OP == QP_FOP_PF_SUB_SMALL) r = pf::sub_small(x, gfn::lo32(y), gfn::hi32(y));
+      else if constexpr (OP == QP_FOP_PF_MUL) r = gfn::mul(x, y);
+      else if constexpr (OP == QP_FOP_PF_MUL_C) r = gfn::mul_c(x, y);
       else if constexpr (OP == QP_FOP_GL_MUL) r = gl::mul(x, y);
       else if constexpr (OP == QP_FOP_PF_SBOX) r = pf::sbox(x);
       else if constexpr (OP == QP_FOP_PF_SBOX_C) r = pf::sbox_c(x);

@@ -23,12 +23,15 @@
 #pragma once
 #include "field.h"
 #include "kernels.h"
-#include "poseidon_fast.h"
 #include "field_nc.h"
 
 namespace nt {
 
-constexpr uint64_t EPS = 0xFFFFFFFFull;
+// sub, the general product and canon are field_nc.h's
+using gfn::EPS;
+using gfn::canon;
+using gfn::mul;
+using gfn::sub;
 
 // Branch-free 32-bit carry chains (field_nc.h) rather than 64-bit
 // compare-and-branch forms; additions with the wrap corrections as
@@ -52,8 +55,6 @@ __device__ __forceinline__ uint64_t add_mad(uint64_t a, uint64_t b) {
 
 __device__ __forceinline__ uint64_t add(uint64_t a, uint64_t b) { return add_mad(a, b); }
 
-__device__ __forceinline__ uint64_t sub(uint64_t a, uint64_t b) { return gfn::sub(a, b); }
-
 __device__ __forceinline__ uint64_t reduce(uint64_t lo, uint64_t hi) {
   const uint64_t hh = hi >> 32, hl = hi & EPS;
   uint64_t t0 = lo - hh;
@@ -63,11 +64,8 @@ __device__ __forceinline__ uint64_t reduce(uint64_t lo, uint64_t hi) {
   return r + (r < t1 ? EPS : 0);
 }
 
-// general product: the asm form (5 mads + 8-op reduction, poseidon_fast.h)
-__device__ __forceinline__ uint64_t mul(uint64_t a, uint64_t b) { return pf::mul(a, b); }
-
 // r[m] *= tw(m) for m = 1..15 (a group's twiddles); K = true (the LDS passes)
-// issues them as five interleaved triples (pf::mulk<3>: each carry is read two
+// issues them as five interleaved triples (gfn::mulk<3>: each carry is read two
 // products later instead of after hazard pads), K = false one at a time (the
 // coset LDE's first pass, at its register cap)
 template <bool K = true, class TW>
@@ -77,7 +75,7 @@ __device__ __forceinline__ void mul_rows(uint64_t r[16], const TW &tw) {
     for (int m = 1; m < 16; m += 3) {
       const uint64_t a[3] = {r[m], r[m + 1], r[m + 2]}, b[3] = {tw(m), tw(m + 1), tw(m + 2)};
       uint64_t o[3];
-      pf::mulk<3>(a, b, o);
+      gfn::mulk<3>(a, b, o);
       r[m] = o[0];
       r[m + 1] = o[1];
       r[m + 2] = o[2];
@@ -87,8 +85,6 @@ __device__ __forceinline__ void mul_rows(uint64_t r[16], const TW &tw) {
     for (int m = 1; m < 16; m++) r[m] = mul(r[m], tw(m));
   }
 }
-
-__device__ __forceinline__ uint64_t canon(uint64_t x) { return x >= gl::P ? x - gl::P : x; }
 
 __device__ __forceinline__ uint64_t neg(uint64_t x) {
   x = canon(x);

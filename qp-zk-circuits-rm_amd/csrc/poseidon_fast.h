@@ -5,15 +5,9 @@
 // its VALU instruction count and v_mad_u64_u32 — a 32x32+64 product-sum in one
 // issue — is the densest instruction there is.
 //
-// Hazard rule (gfx950): a VALU instruction reading a carry/mask SGPR written
-// by the previous VALU instruction needs 2 wait states (hipcc puts s_nop 1
-// between its own v_add_co/v_addc pairs).  Around inline asm hipcc adds only a
-// fixed 1-state pad, so every asm statement below that reads a carry written
-// by the preceding one opens with its own s_nop 0.
-// (Dropping it measured no faster, profiles/r02_ab_carry_wait.log.)
-#define QP_CWAIT "s_nop 0\n\t"
-//
-// Same function as ps::permute (poseidon.h); arithmetic discipline:
+// Same function as ps::permute (poseidon.h), on the non-canonical field
+// arithmetic of field_nc.h (the general product, the carry hazard rule and
+// its QP_CWAIT pad live there); arithmetic discipline:
 //   * state NON-canonical in [0, 2^64) (plonky2's GoldilocksField form);
 //   * MDS row r = sum_i CIRC[i] * s[(i+r)%12] (+ DIAG) computed on 32-bit
 //     halves as 24 explicit v_mad_u64_u32 with the small constants inline
@@ -25,32 +19,25 @@
 //   * each row reduces in 4 instructions: value = al + 2^32 ah with
 //     al, ah < 2^41 -> t = al + eps*hi32(ah) (one mad), t.hi += lo32(ah) with
 //     carry c, t += c*eps.
-//   * sbox x^7 = x^3 * x^4 with a 5-mad product and an 8-instruction
-//     Goldilocks reduction whose carries come straight from the mad/sub
-//     carry-outs.
+//   * sbox x^7 = x^3 * x^4 on gfn::mul.
+// One form of each piece: the code-shape variants that were measured and lost
+// (compiler mads, C reductions, rolled rounds, multi-row asm blocks) are rows
+// of DESIGN.md §10.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "field_nc.h"
 #include "poseidon.h"
-#include "poseidon_mds_asm.h"
 #include "poseidon_partial_consts.h"
 
 namespace pf {
 
-constexpr uint64_t EPS = 0xFFFFFFFFull;
-constexpr uint64_t P = 0xFFFFFFFF00000001ull;
-
-__device__ __forceinline__ uint32_t lo32(uint64_t x) { return (uint32_t)x; }
-__device__ __forceinline__ uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32); }
-
-// C as a value the compiler cannot see through (an SGPR; no instruction is
-// emitted for the empty asm), so x * C stays one v_mad_u64_u32
-template <int C>
-__device__ __forceinline__ uint32_t opaque() {
-  uint32_t c;
-  asm("" : "=s"(c) : "0"((uint32_t)C));
-  return c;
-}
+using gfn::EPS;
+using gfn::canon;
+using gfn::hi32;
+using gfn::lo32;
+using gfn::mul;
+using gfn::mul_c;
 
 // acc = x * C + add   (C an inline constant in [0, 64])
 template <int C>
@@ -84,39 +71,6 @@ __device__ __forceinline__ uint64_t reduce_row(uint64_t al, uint64_t ah) {
   return r;
 }
 
-// a * b mod p, a, b in [0, 2^64), result in [0, 2^64)
-__device__ __forceinline__ uint64_t mul(uint64_t a, uint64_t b) {
-  const uint32_t a0 = lo32(a), a1 = hi32(a), b0 = lo32(b), b1 = hi32(b);
-  // middle column as one 65-bit sum: T = a0 b1 + L.hi, U = a1 b0 + T with its
-  // carry-out c (worth 2^96), W = a1 b1 + (U.hi | c << 32): one zero-extension
-  // and no separate 64-bit add (the textbook four-product form, mul_c below,
-  // needs three and a v_lshl_add_u64; profiles/r02_ab_mul_form_dot_halves.log)
-  const uint64_t L = (uint64_t)a0 * b0;
-  const uint64_t T = (uint64_t)a0 * b1 + hi32(L);
-  uint64_t U, cu;
-  uint32_t ce;
-  asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(U), "=s"(cu) : "v"(a1), "v"(b0), "v"(T));
-  asm(QP_CWAIT "v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(ce) : "s"(cu));
-  const uint64_t W = (uint64_t)a1 * b1 + (((uint64_t)ce << 32) | hi32(U));  // < 2^64 (high half)
-  const uint64_t X = ((uint64_t)lo32(U) << 32) | lo32(L);
-  // 128-bit product = X + 2^64 W, X = (L0, U0);  ≡ X + eps*w2 - w3
-  uint64_t t, c1, c2, c3;
-  uint32_t e;
-  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c1) : "v"(lo32(W)), "v"(X));
-  asm(QP_CWAIT "v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(e) : "s"(c1));
-  // carry: true value t + 2^64 ≡ t + eps; t < 2^64 - 2^33 then, no overflow
-  asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(t), "=s"(c2) : "v"(e), "v"(t));
-  // t - w3, borrow b (worth -2^64 ≡ -eps)
-  uint32_t r0 = lo32(t), r1 = hi32(t);
-  asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(r0), "=s"(c3) : "v"(r0), "v"(hi32(W)));
-  asm(QP_CWAIT "v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r1), "=s"(c3) : "v"(r1), "s"(c3));
-  asm(QP_CWAIT "v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(e) : "s"(c3));
-  // borrow: t - w3 + 2^64 >= 2^64 - 2^32, minus eps stays >= 0
-  asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(r0), "=s"(c3) : "v"(r0), "v"(e));
-  asm(QP_CWAIT "v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r1), "=s"(c3) : "v"(r1), "s"(c3));
-  return ((uint64_t)r1 << 32) | r0;
-}
-
 // C forms of the same (compiler-chosen carries)
 __device__ __forceinline__ uint64_t reduce_row_c(uint64_t al, uint64_t ah) {
   const uint64_t t = al + (ah >> 32) * EPS;
@@ -124,147 +78,11 @@ __device__ __forceinline__ uint64_t reduce_row_c(uint64_t al, uint64_t ah) {
   const uint64_t r = ((uint64_t)t1 << 32) | lo32(t);
   return t1 < lo32(ah) ? r + EPS : r;
 }
-__device__ __forceinline__ uint64_t mul_c(uint64_t a, uint64_t b) {
-  const uint32_t a0 = lo32(a), a1 = hi32(a), b0 = lo32(b), b1 = hi32(b);
-  const uint64_t L = (uint64_t)a0 * b0;
-  const uint64_t T = (uint64_t)a0 * b1 + hi32(L);
-  const uint64_t U = (uint64_t)a1 * b0 + lo32(T);
-  const uint64_t V = (uint64_t)a1 * b1 + hi32(T);
-  const uint64_t W = V + hi32(U);
-  const uint64_t X = ((uint64_t)lo32(U) << 32) | lo32(L);
-  uint64_t t = X + (uint64_t)lo32(W) * EPS;
-  t = t < X ? t + EPS : t;
-  const uint64_t w3 = hi32(W);
-  const uint64_t r = t - w3;
-  return t < w3 ? r - EPS : r;
-}
 __device__ __forceinline__ uint64_t sbox_c(uint64_t x) {
   const uint64_t x2 = mul_c(x, x);
   const uint64_t x3 = mul_c(x2, x);
   const uint64_t x4 = mul_c(x2, x2);
   return mul_c(x3, x4);
-}
-
-// ---- K independent products with their carry steps interleaved (K = 2, 3):
-// each asm statement below issues one step of every product, so a carry SGPR
-// written by product i's instruction is read K - 1 instructions (plus the
-// compiler's one-state pad after an asm statement) later — the gfx950 carry
-// hazard's two wait states are met by the other products' work instead of
-// s_nop (one product alone needs ~14 pad states).  Same arithmetic as mul():
-// U = a1 b0 + T with carry, W = a1 b1 + (U.hi | c << 32), X = (U.lo, L.lo),
-// then the 8-step reduction.  The NTT passes use it (nt::mul_rows); in the
-// Poseidon S-boxes it measured slower (leaf hash +4 %, e2e -2 %,
-// profiles/r02_ab_mulk.log): at 7 waves/SIMD the pads it removes (8.0k -> 2.9k
-// s_nop per permutation) were nearly free and it adds ~500 register-pair
-// moves, so the S-boxes keep one product at a time.
-#define QP_W2 QP_CWAIT  // K = 2: one explicit wait state before each carry read
-template <int K>
-__device__ __forceinline__ void mulk(const uint64_t *a, const uint64_t *b, uint64_t *r) {
-  static_assert(K == 2 || K == 3, "K");
-  uint64_t T[K], U[K], W[K], X[K], t[K], cs[K];
-  uint32_t ce[K], e[K], r0[K], r1[K];
-#pragma unroll
-  for (int i = 0; i < K; i++) {
-    const uint64_t L = (uint64_t)lo32(a[i]) * lo32(b[i]);
-    T[i] = (uint64_t)lo32(a[i]) * hi32(b[i]) + hi32(L);
-    X[i] = lo32(L);
-  }
-  if constexpr (K == 3) {
-    asm("v_mad_u64_u32 %0, %3, %6, %9, %12\n\t"
-        "v_mad_u64_u32 %1, %4, %7, %10, %13\n\t"
-        "v_mad_u64_u32 %2, %5, %8, %11, %14"
-        : "=&v"(U[0]), "=&v"(U[1]), "=&v"(U[2]), "=&s"(cs[0]), "=&s"(cs[1]), "=&s"(cs[2])
-        : "v"(hi32(a[0])), "v"(hi32(a[1])), "v"(hi32(a[2])), "v"(lo32(b[0])), "v"(lo32(b[1])), "v"(lo32(b[2])),
-          "v"(T[0]), "v"(T[1]), "v"(T[2]));
-    asm("v_cndmask_b32_e64 %0, 0, 1, %3\n\t"
-        "v_cndmask_b32_e64 %1, 0, 1, %4\n\t"
-        "v_cndmask_b32_e64 %2, 0, 1, %5"
-        : "=v"(ce[0]), "=v"(ce[1]), "=v"(ce[2]) : "s"(cs[0]), "s"(cs[1]), "s"(cs[2]));
-  } else {
-    asm("v_mad_u64_u32 %0, %2, %4, %6, %8\n\t"
-        "v_mad_u64_u32 %1, %3, %5, %7, %9"
-        : "=&v"(U[0]), "=&v"(U[1]), "=&s"(cs[0]), "=&s"(cs[1])
-        : "v"(hi32(a[0])), "v"(hi32(a[1])), "v"(lo32(b[0])), "v"(lo32(b[1])), "v"(T[0]), "v"(T[1]));
-    asm(QP_W2 "v_cndmask_b32_e64 %0, 0, 1, %2\n\t"
-        "v_cndmask_b32_e64 %1, 0, 1, %3"
-        : "=v"(ce[0]), "=v"(ce[1]) : "s"(cs[0]), "s"(cs[1]));
-  }
-#pragma unroll
-  for (int i = 0; i < K; i++) {
-    W[i] = (uint64_t)hi32(a[i]) * hi32(b[i]) + (((uint64_t)ce[i] << 32) | hi32(U[i]));
-    X[i] |= (uint64_t)lo32(U[i]) << 32;
-  }
-  if constexpr (K == 3) {
-    // t = X + eps w2 (carry c1); e = c1 ? eps : 0; t += e
-    asm("v_mad_u64_u32 %0, %3, %6, -1, %9\n\t"
-        "v_mad_u64_u32 %1, %4, %7, -1, %10\n\t"
-        "v_mad_u64_u32 %2, %5, %8, -1, %11"
-        : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&s"(cs[0]), "=&s"(cs[1]), "=&s"(cs[2])
-        : "v"(lo32(W[0])), "v"(lo32(W[1])), "v"(lo32(W[2])), "v"(X[0]), "v"(X[1]), "v"(X[2]));
-    asm("v_cndmask_b32_e64 %0, 0, -1, %3\n\t"
-        "v_cndmask_b32_e64 %1, 0, -1, %4\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, %5"
-        : "=v"(e[0]), "=v"(e[1]), "=v"(e[2]) : "s"(cs[0]), "s"(cs[1]), "s"(cs[2]));
-    asm("v_mad_u64_u32 %0, vcc, %3, 1, %0\n\t"
-        "v_mad_u64_u32 %1, vcc, %4, 1, %1\n\t"
-        "v_mad_u64_u32 %2, vcc, %5, 1, %2"
-        : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]) : "v"(e[0]), "v"(e[1]), "v"(e[2]) : "vcc");
-    // r = t - w3 (borrow b); e = b ? eps : 0; r -= e
-    asm("v_sub_co_u32_e64 %0, %3, %6, %9\n\t"
-        "v_sub_co_u32_e64 %1, %4, %7, %10\n\t"
-        "v_sub_co_u32_e64 %2, %5, %8, %11"
-        : "=&v"(r0[0]), "=&v"(r0[1]), "=&v"(r0[2]), "=&s"(cs[0]), "=&s"(cs[1]), "=&s"(cs[2])
-        : "v"(lo32(t[0])), "v"(lo32(t[1])), "v"(lo32(t[2])), "v"(hi32(W[0])), "v"(hi32(W[1])), "v"(hi32(W[2])));
-    asm("v_subb_co_u32_e64 %0, %3, %6, 0, %3\n\t"
-        "v_subb_co_u32_e64 %1, %4, %7, 0, %4\n\t"
-        "v_subb_co_u32_e64 %2, %5, %8, 0, %5"
-        : "=&v"(r1[0]), "=&v"(r1[1]), "=&v"(r1[2]), "+s"(cs[0]), "+s"(cs[1]), "+s"(cs[2])
-        : "v"(hi32(t[0])), "v"(hi32(t[1])), "v"(hi32(t[2])));
-    asm("v_cndmask_b32_e64 %0, 0, -1, %3\n\t"
-        "v_cndmask_b32_e64 %1, 0, -1, %4\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, %5"
-        : "=v"(e[0]), "=v"(e[1]), "=v"(e[2]) : "s"(cs[0]), "s"(cs[1]), "s"(cs[2]));
-    asm("v_sub_co_u32_e64 %0, %3, %0, %6\n\t"
-        "v_sub_co_u32_e64 %1, %4, %1, %7\n\t"
-        "v_sub_co_u32_e64 %2, %5, %2, %8"
-        : "+v"(r0[0]), "+v"(r0[1]), "+v"(r0[2]), "=&s"(cs[0]), "=&s"(cs[1]), "=&s"(cs[2])
-        : "v"(e[0]), "v"(e[1]), "v"(e[2]));
-    asm("v_subb_co_u32_e64 %0, vcc, %0, 0, %3\n\t"
-        "v_subb_co_u32_e64 %1, vcc, %1, 0, %4\n\t"
-        "v_subb_co_u32_e64 %2, vcc, %2, 0, %5"
-        : "+v"(r1[0]), "+v"(r1[1]), "+v"(r1[2]) : "s"(cs[0]), "s"(cs[1]), "s"(cs[2]) : "vcc");
-  } else {
-    asm("v_mad_u64_u32 %0, %2, %4, -1, %6\n\t"
-        "v_mad_u64_u32 %1, %3, %5, -1, %7"
-        : "=&v"(t[0]), "=&v"(t[1]), "=&s"(cs[0]), "=&s"(cs[1])
-        : "v"(lo32(W[0])), "v"(lo32(W[1])), "v"(X[0]), "v"(X[1]));
-    asm(QP_W2 "v_cndmask_b32_e64 %0, 0, -1, %2\n\t"
-        "v_cndmask_b32_e64 %1, 0, -1, %3"
-        : "=v"(e[0]), "=v"(e[1]) : "s"(cs[0]), "s"(cs[1]));
-    asm("v_mad_u64_u32 %0, vcc, %2, 1, %0\n\t"
-        "v_mad_u64_u32 %1, vcc, %3, 1, %1"
-        : "+v"(t[0]), "+v"(t[1]) : "v"(e[0]), "v"(e[1]) : "vcc");
-    asm("v_sub_co_u32_e64 %0, %2, %4, %6\n\t"
-        "v_sub_co_u32_e64 %1, %3, %5, %7"
-        : "=&v"(r0[0]), "=&v"(r0[1]), "=&s"(cs[0]), "=&s"(cs[1])
-        : "v"(lo32(t[0])), "v"(lo32(t[1])), "v"(hi32(W[0])), "v"(hi32(W[1])));
-    asm(QP_W2 "v_subb_co_u32_e64 %0, %2, %4, 0, %2\n\t"
-        "v_subb_co_u32_e64 %1, %3, %5, 0, %3"
-        : "=&v"(r1[0]), "=&v"(r1[1]), "+s"(cs[0]), "+s"(cs[1])
-        : "v"(hi32(t[0])), "v"(hi32(t[1])));
-    asm(QP_W2 "v_cndmask_b32_e64 %0, 0, -1, %2\n\t"
-        "v_cndmask_b32_e64 %1, 0, -1, %3"
-        : "=v"(e[0]), "=v"(e[1]) : "s"(cs[0]), "s"(cs[1]));
-    asm("v_sub_co_u32_e64 %0, %2, %0, %4\n\t"
-        "v_sub_co_u32_e64 %1, %3, %1, %5"
-        : "+v"(r0[0]), "+v"(r0[1]), "=&s"(cs[0]), "=&s"(cs[1])
-        : "v"(e[0]), "v"(e[1]));
-    asm(QP_W2 "v_subb_co_u32_e64 %0, vcc, %0, 0, %2\n\t"
-        "v_subb_co_u32_e64 %1, vcc, %1, 0, %3"
-        : "+v"(r1[0]), "+v"(r1[1]) : "s"(cs[0]), "s"(cs[1]) : "vcc");
-  }
-#pragma unroll
-  for (int i = 0; i < K; i++) r[i] = ((uint64_t)r1[i] << 32) | r0[i];
 }
 
 __device__ __forceinline__ uint64_t sbox(uint64_t x) {
@@ -286,22 +104,14 @@ __device__ __forceinline__ uint64_t add_c(uint64_t a, uint64_t c) {
   return s + (s < c ? EPS : 0);
 }
 
-__device__ __forceinline__ uint64_t canon(uint64_t x) { return x >= P ? x - P : x; }
-
-// MDS row R with the next round's constant k folded in (k < p, as SGPR halves)
-template <int M, int R, int I>
+// terms I..11 of MDS row R, one mad per half and term
+template <int R, int I>
 __device__ __forceinline__ void row_terms(uint64_t &al, uint64_t &ah, const uint32_t lo[12], const uint32_t hi[12]) {
   if constexpr (I < 12) {
     constexpr int C = (int)ps::mds_circ(I) + ((R == 0 && I == 0) ? 8 : 0);
-    if constexpr (M == 0) {
-      al = mad_c<C>(lo[(I + R) % 12], al);
-      ah = mad_c<C>(hi[(I + R) % 12], ah);
-    } else {
-      const uint32_t c = opaque<C>();
-      al += (uint64_t)lo[(I + R) % 12] * c;
-      ah += (uint64_t)hi[(I + R) % 12] * c;
-    }
-    row_terms<M, R, I + 1>(al, ah, lo, hi);
+    al = mad_c<C>(lo[(I + R) % 12], al);
+    ah = mad_c<C>(hi[(I + R) % 12], ah);
+    row_terms<R, I + 1>(al, ah, lo, hi);
   }
 }
 
@@ -313,7 +123,7 @@ __device__ __forceinline__ void mds_rows_k(uint64_t s[12], const uint32_t lo[12]
     constexpr int C0 = (int)ps::mds_circ(0) + (R == 0 ? 8 : 0);
     uint64_t al = mad_cs<C0>(lo[R], k[R] & EPS);
     uint64_t ah = mad_cs<C0>(hi[R], k[R] >> 32);
-    row_terms<0, R, 1>(al, ah, lo, hi);
+    row_terms<R, 1>(al, ah, lo, hi);
     s[R] = reduce_row(al, ah);
     mds_rows_k<R + 1>(s, lo, hi, k);
   }
@@ -329,30 +139,29 @@ __device__ __forceinline__ void mds_k(uint64_t s[12], const uint64_t k[12]) {
   mds_rows_k<0>(s, lo, hi, k);
 }
 
-template <int M, int R, int RC>
-__device__ __forceinline__ void mds_rows(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12]) {
+template <int R>
+__device__ __forceinline__ void mds_rows_mads(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12]) {
   if constexpr (R < 12) {
     constexpr int C0 = (int)ps::mds_circ(0) + (R == 0 ? 8 : 0);
-    uint64_t al, ah;
-    constexpr uint64_t k = RC >= 0 ? ps::rc_cx(RC * 12 + R) : 0;
-    if constexpr (M == 0) {
-      // constant of the next round folded into the accumulators' start
-      if constexpr (RC >= 0) {
-        al = mad_cs<C0>(lo[R], k & EPS);
-        ah = mad_cs<C0>(hi[R], k >> 32);
-      } else {
-        al = mad_c<C0>(lo[R], 0);
-        ah = mad_c<C0>(hi[R], 0);
-      }
-    } else {
-      const uint32_t c = opaque<C0>();
-      al = (uint64_t)lo[R] * c + (k & EPS);
-      ah = (uint64_t)hi[R] * c + (k >> 32);
-    }
-    row_terms<M, R, 1>(al, ah, lo, hi);
-    s[R] = M == 2 ? reduce_row_c(al, ah) : reduce_row(al, ah);
-    mds_rows<M, R + 1, RC>(s, lo, hi);
+    uint64_t al = mad_c<C0>(lo[R], 0);
+    uint64_t ah = mad_c<C0>(hi[R], 0);
+    row_terms<R, 1>(al, ah, lo, hi);
+    s[R] = reduce_row(al, ah);
+    mds_rows_mads<R + 1>(s, lo, hi);
   }
+}
+
+// The per-mad MDS, s <- MDS(s) with no constant: every product its own asm
+// statement, as in mds_k and capz_mds.  The quotient's Poseidon-gate rounds
+// use it.
+__device__ __forceinline__ void mds_mads(uint64_t s[12]) {
+  uint32_t lo[12], hi[12];
+#pragma unroll
+  for (int i = 0; i < 12; i++) {
+    lo[i] = lo32(s[i]);
+    hi[i] = hi32(s[i]);
+  }
+  mds_rows_mads<0>(s, lo, hi);
 }
 
 // One MDS row as a single asm block: 24 v_mad_u64_u32 on the rotated halves
@@ -421,50 +230,19 @@ __device__ __forceinline__ void mds_rows_block(uint64_t s[12], const uint32_t lo
   }
 }
 
-// modes 6-9: blocks of NR = 2, 3, 4, 6 rows, their 2*NR accumulate chains
-// interleaved in one asm block (poseidon_mds_asm.h) so a wave keeps 2*NR
-// independent v_mad_u64_u32 chains in flight instead of 2
-template <int M>
-constexpr int mds_block_rows() { return M == 6 ? 2 : M == 7 ? 3 : M == 8 ? 4 : 6; }
-
-template <int NR, int R>
-__device__ __forceinline__ void mds_asm_rows(uint64_t acc[2 * NR], const uint32_t lo[12], const uint32_t hi[12],
-                                             const uint64_t k[2 * NR]) {
-  if constexpr (NR == 2) mds_asm_rows2<R>(acc, lo, hi, k);
-  else if constexpr (NR == 3) mds_asm_rows3<R>(acc, lo, hi, k);
-  else if constexpr (NR == 4) mds_asm_rows4<R>(acc, lo, hi, k);
-  else mds_asm_rows6<R>(acc, lo, hi, k);
-}
-
-template <int NR, int R, int RC>
-__device__ __forceinline__ void mds_rows_multi(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12]) {
-  if constexpr (R < 12) {
-    uint64_t k[2 * NR], acc[2 * NR];
-#pragma unroll
-    for (int r = 0; r < NR; r++) {
-      const uint64_t kk = RC >= 0 ? ps::rc_cx(RC * 12 + R + r) : 0;
-      k[2 * r] = kk & EPS;
-      k[2 * r + 1] = kk >> 32;
-    }
-    mds_asm_rows<NR, R>(acc, lo, hi, k);
-#pragma unroll
-    for (int r = 0; r < NR; r++) s[R + r] = reduce_row(acc[2 * r], acc[2 * r + 1]);
-    mds_rows_multi<NR, R + NR, RC>(s, lo, hi);
-  }
-}
-
-// s <- MDS(s) + RC[next] (next < 0: no constant); OUT: the output rows needed
-template <int M, int NEXT, uint32_t OUT = 0xFFFu>
-__device__ __forceinline__ void mds(uint64_t s[12]) {
+// The row-block MDS, s <- MDS(s) + RC[NEXT] (NEXT < 0: no constant), each row
+// one asm block; OUT: the output rows needed.  The hashing permutation uses it
+// (2.35 against 2.24 Gperm/s for the per-mad form in isolation, e2e 932 -> 942
+// proofs/s, profiles/r02_ab_poseidon_mode3.log).
+template <int NEXT, uint32_t OUT = 0xFFFu>
+__device__ __forceinline__ void mds_block(uint64_t s[12]) {
   uint32_t lo[12], hi[12];
 #pragma unroll
   for (int i = 0; i < 12; i++) {
     lo[i] = lo32(s[i]);
     hi[i] = hi32(s[i]);
   }
-  if constexpr (M >= 6) mds_rows_multi<mds_block_rows<M>(), 0, NEXT>(s, lo, hi);
-  else if constexpr (M >= 3) mds_rows_block<0, NEXT, OUT>(s, lo, hi);
-  else mds_rows<M, 0, NEXT>(s, lo, hi);
+  mds_rows_block<0, NEXT, OUT>(s, lo, hi);
 }
 
 // block-asm MDS with the next round's constants read at run time (uniform
@@ -482,7 +260,7 @@ __device__ __forceinline__ void mds_rows_block_dyn(uint64_t s[12], const uint32_
 }
 
 // one full round (12 S-boxes + MDS folding the next round's constants, read at
-// run time) — the body of the rolled full-round loops of mode 5
+// run time) — the body of the witness kernel's rolled full-round loops
 __device__ __forceinline__ void full_round_dyn(uint64_t s[12], const uint64_t *__restrict__ knext) {
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = sbox(s[i]);
@@ -500,7 +278,7 @@ __device__ __forceinline__ void full_round_dyn(uint64_t s[12], const uint64_t *_
 // dot product for lane 0 and 11 scalar multiply-adds.  Dense constants act on
 // 22-bit limbs (x = l0 + 2^22 l1 + 2^44 l2) through precomputed c 2^(22k) mod
 // p halves, so every accumulator stays < 2^60 and reduces in 4 instructions.
-// Same permutation as the plain rounds (modes 3 and 10 take this form).
+// Same permutation as the plain rounds.
 
 __device__ __forceinline__ void limbs22(uint64_t x, uint32_t l[3]) {
   const uint32_t lo = lo32(x), hi = hi32(x);
@@ -702,66 +480,25 @@ __device__ __forceinline__ void partial_group(uint64_t s[12], const HK &hook = H
   s[0] = s0;
 }
 
-// OUT: bit mask of the output lanes the caller reads (the last MDS computes
-// only those rows; digests need lanes 0..3, the PoW lane 7)
-template <int M, int R, uint32_t OUT = 0xFFFu>
+// rounds R..29.  OUT: bit mask of the output lanes the caller reads (the last
+// MDS computes only those rows; digests need lanes 0..3, the PoW lane 7)
+template <int R, uint32_t OUT = 0xFFFu>
 __device__ __forceinline__ void rounds(uint64_t s[12]) {
-  if constexpr (M == 10 && R == 0) {
-    // mode 10: mode 3 with the full rounds 0-2 and 26-28 rolled (a third of
-    // the code; round constants from memory)
-#pragma unroll 1
-    for (int r = 0; r < 3; r++) full_round_dyn(s, ps::RC_DEV + (r + 1) * 12);
-    rounds<M, 3, OUT>(s);
-  } else if constexpr (M == 10 && R == 26) {
-#pragma unroll 1
-    for (int r = 26; r < 29; r++) full_round_dyn(s, ps::RC_DEV + (r + 1) * 12);
-    rounds<3, 29, OUT>(s);
-  } else if constexpr ((M == 3 || M == 10) && R == 3) {
+  if constexpr (R == 3) {
+    // the last full round before the partial rounds: its MDS merged with D_4
     sbox12(s);
     mds_init_sparse(s);
-    rounds<M, 4, OUT>(s);
-  } else if constexpr ((M == 3 || M == 10) && R >= 4 && R < 26) {
+    rounds<4, OUT>(s);
+  } else if constexpr (R >= 4 && R < 26) {
     constexpr int T0 = R - 4, G = (22 - T0) < PF_GROUP ? (22 - T0) : PF_GROUP;
     if constexpr (G > 1) partial_group<T0, G>(s);
     else partial_sparse<T0>(s);
-    rounds<M, R + G, OUT>(s);
-  } else if constexpr (M == 5 && R == 0) {
-    // every round rolled: a ~4k-instruction permutation
-#pragma unroll 1
-    for (int r = 0; r < 4; r++) full_round_dyn(s, ps::RC_DEV + (r + 1) * 12);
-    rounds<5, 4>(s);  // rolled partial rounds, then the rolled tail
-  } else if constexpr (M == 5 && R == 26) {
-#pragma unroll 1
-    for (int r = 26; r < 29; r++) full_round_dyn(s, ps::RC_DEV + (r + 1) * 12);
-    rounds<3, 29>(s);  // the last round: MDS without a next constant
-  } else if constexpr ((M == 4 || M == 5) && R == 4) {
-    // 22 partial rounds as a loop: ~9k fewer instructions of code (the
-    // unrolled permutation is several times the instruction cache)
-#pragma unroll 1
-    for (int r = 4; r < 26; r++) {
-      s[0] = sbox(s[0]);
-      uint32_t lo[12], hi[12];
-#pragma unroll
-      for (int i = 0; i < 12; i++) {
-        lo[i] = lo32(s[i]);
-        hi[i] = hi32(s[i]);
-      }
-      mds_rows_block_dyn<0>(s, lo, hi, ps::RC_DEV + (r + 1) * 12);
-    }
-    rounds<M, 26>(s);
+    rounds<R + G, OUT>(s);
   } else if constexpr (R < 30) {
-    constexpr bool full = R < 4 || R >= 26;
-    if constexpr (full && M == 3) {
-      sbox12(s);
-    } else if constexpr (full) {
-#pragma unroll
-      for (int i = 0; i < 12; i++) s[i] = M == 2 ? sbox_c(s[i]) : sbox(s[i]);
-    } else {
-      s[0] = M == 2 ? sbox_c(s[0]) : sbox(s[0]);
-    }
-    if constexpr (R == 29) mds<M, -1, OUT>(s);
-    else mds<M, R + 1>(s);
-    rounds<M, R + 1, OUT>(s);
+    sbox12(s);
+    if constexpr (R == 29) mds_block<-1, OUT>(s);
+    else mds_block<R + 1>(s);
+    rounds<R + 1, OUT>(s);
   }
 }
 
@@ -791,7 +528,7 @@ __device__ __forceinline__ void capz_mds(uint64_t s[12], const uint32_t lo[12], 
   }
 }
 
-// permute_nc for s[8..11] == 0 on entry (mode 3), reading only lanes OUT
+// permute_nc for s[8..11] == 0 on entry, reading only lanes OUT
 // (profiles/r02_ab_capz.log)
 template <uint32_t OUT = 0xFFFu>
 __device__ __forceinline__ void permute_nc_capz(uint64_t s[12]) {
@@ -803,24 +540,18 @@ __device__ __forceinline__ void permute_nc_capz(uint64_t s[12]) {
     hi[i] = hi32(s[i]);
   }
   capz_mds(s, lo, hi);
-  rounds<3, 1, OUT>(s);
+  rounds<1, OUT>(s);
 }
 
 // permutation; inputs in [0, 2^64), outputs in [0, 2^64) (canon() lanes read out)
-// M: 0 = asm mads, 1 = compiler mads on opaque constants, 2 = 1 + C reductions,
-//    3 = 0 with each MDS row's 24 mads in one asm block, 4 = 3 with the
-//    partial rounds rolled into a loop, 5 = every round rolled,
-//    6..9 = MDS in blocks of 2 / 3 / 4 / 6 rows with interleaved chains
-template <int M = 1>
 __device__ __forceinline__ void permute_nc(uint64_t s[12]) {
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = add_c(s[i], ps::rc_cx(i));
-  rounds<M, 0>(s);
+  rounds<0>(s);
 }
 
-template <int M = 1>
 __device__ __forceinline__ void permute(uint64_t s[12]) {
-  permute_nc<M>(s);
+  permute_nc(s);
 #pragma unroll
   for (int i = 0; i < 12; i++) s[i] = canon(s[i]);
 }

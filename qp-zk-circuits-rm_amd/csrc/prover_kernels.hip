@@ -249,7 +249,7 @@ void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t
 
 #define WV(j) wl[(uint64_t)(j) * N]
 
-// two independent products (an interleaved pf::mulk<2> form measured no
+// two independent products (an interleaved gfn::mulk<2> form measured no
 // change, profiles/r03_ab_quotient_mulk.log)
 __device__ __forceinline__ void mul2(uint64_t a0, uint64_t b0, uint64_t a1, uint64_t b1, uint64_t &r0, uint64_t &r1) {
   r0 = gfn::mul(a0, b0);
@@ -380,7 +380,7 @@ __device__ __forceinline__ void poseidon_gate_rd(const RD &WR, TermAcc &A) {
       rc_row(k, 27 + r);
       pf::mds_k(s, k);
     } else {
-      pf::mds<0, -1>(s);
+      pf::mds_mads(s);
     }
   }
 #pragma unroll
@@ -483,8 +483,8 @@ __device__ __forceinline__ void recursion_gate_body(uint32_t kind, uint32_t q0, 
         a[i] = WV(2 * i);
         b[i] = WV(2 * i + 1);
       }
-      pf::mds<0, -1>(a);
-      pf::mds<0, -1>(b);
+      pf::mds_mads(a);
+      pf::mds_mads(b);
 #pragma unroll
       for (int r = 0; r < 12; r++) {
         A.emit(gfn::sub(WV(24 + 2 * r), a[r]));
@@ -1680,7 +1680,7 @@ __device__ __forceinline__ bool pow_hit(const uint64_t *__restrict__ pre, uint32
     const uint32_t c = (uint32_t)pre[12 + r];
     s[r] = pf::reduce_row((uint64_t)y0 * c + (pre[r] & pf::EPS), (uint64_t)y1 * c + (pre[r] >> 32));
   }
-  pf::rounds<QP_POSEIDON_MODE, 1, 0x80u>(s);  // only lane 7 is read
+  pf::rounds<1, 0x80u>(s);  // only lane 7 is read
   return (psd::canon(s[7]) >> (64 - bits)) == 0;
 }
 

@@ -156,7 +156,7 @@ __device__ __noinline__ bool poseidon_witness_rolled(uint64_t *v, const uint32_t
   for (int i = 0; i < 12; i++) wput(v, sl[i], s[i], ok);
   slots_load(sl, ws, 12);
   pf::sbox12(s);
-  pf::mds<3, -1>(s);
+  pf::mds_block<-1>(s);
 #pragma unroll
   for (int i = 0; i < 12; i++) wput(v, sl[i], s[i], ok);
   return ok;

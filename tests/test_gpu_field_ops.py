@@ -2,9 +2,11 @@
 
 The hot kernels do not use the readable gl:: functions: they run hand-written
 carry chains and inline assembly on non-canonical values in [0, 2^64)
-(ntt16.h nt::, field_nc.h gfn::, poseidon_fast.h pf::).  Under uniform inputs
-a single wrap or borrow in those chains has probability about 2^-32 and the
-double wraps about 2^-64, so the bit-exact whole-kernel tests never take them.
+(field_nc.h gfn::, which holds the general products mul, mul_c and mulk<K> that
+the PF_MUL* ops probe, and ntt16.h nt:: and poseidon_fast.h pf:: built on it).
+Under uniform inputs a single wrap or borrow in those chains has probability
+about 2^-32 and the double wraps about 2^-64, so the bit-exact whole-kernel
+tests never take them.
 Here the TEST-ONLY probe qp_debug_field_op (csrc/field_probe.hip) applies one
 device function per lane to chosen operands and returns the raw u64:
 
@@ -135,7 +137,7 @@ def m_gfn_reduce(lo, hi):
 
 
 def m_mul(a, b):
-    """pf::mul: U = a1 b0 + T with carry cu; W = a1 b1 + (U.hi | cu << 32);
+    """gfn::mul: U = a1 b0 + T with carry cu; W = a1 b1 + (U.hi | cu << 32);
     t = X + eps w2 (carry c1: + eps, cannot wrap); r = t - w3 (borrow: - eps,
     cannot borrow)."""
     a0, a1, b0, b1 = lo32(a), hi32(a), lo32(b), hi32(b)
@@ -552,7 +554,7 @@ def test_four_wide(ctx, name, op, model):
 
 @gpu
 def test_products_agree_raw(ctx):
-    """pf::mul, pf::mul_c and pf::mulk<2|3> claim the same arithmetic: equal as
+    """gfn::mul, gfn::mul_c and gfn::mulk<2|3> claim the same arithmetic: equal as
     raw u64, with each edge pair at each position of the K-wide forms."""
     check_coverage("mul")
     a, b = pair_set("u64", "u64")
