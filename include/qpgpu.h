@@ -336,7 +336,7 @@ enum {
     QP_FOP_NT_REDUCE,         /* nt::reduce(lo = a, hi = b)                                */
     QP_FOP_GFN_REDUCE,        /* gfn::reduce(lo = a, hi = b)                               */
     QP_FOP_GL_REDUCE128,      /* gl::reduce128(lo = a, hi = b); result < p                 */
-    QP_FOP_PF_REDUCE_ROW,     /* pf::reduce_row(al = a, ah = b): a, b < 2^42               */
+    QP_FOP_PF_REDUCE_ROW,     /* pf::reduce_row(al = a, ah = b): a, b < 2^60               */
     QP_FOP_PF_REDUCE_ROW_C,   /* pf::reduce_row_c, same operands                           */
     QP_FOP_PF_SUB_SMALL,      /* pf::sub_small(r = a, y = b): b < 2^40                     */
     QP_FOP_PF_MUL,            /* gfn::mul (pf::mul, nt::mul by name)                       */
@@ -353,6 +353,35 @@ enum {
 };
 int qp_debug_field_op(qp_ctx *ctx, uint32_t op, uint32_t param, const uint64_t *a, const uint64_t *b, uint64_t n,
                       uint64_t *out);
+/* TEST-ONLY: the device Poseidon forms, one at a time (csrc/poseidon_probe.hip).
+ * State i is states[12 i .. 12 i + 12); out gets 12 RAW words per state (no
+ * canonicalisation).  The one-lane forms (pf::, poseidon_fast.h) run one state
+ * per lane; the cooperative forms (pc::, poseidon_coop.h) hold element j on lane
+ * j < 12 of a 64-lane wave or of a 16-lane row (four states per wave), every
+ * launched wave whole and a wave / row past nstates exiting whole.  Inputs are
+ * any u64 unless noted; `param` is 0 where none is taken.  Unknown form or
+ * param, a null pointer, more than 2^20 states or a capz state whose lanes
+ * 8..11 are not 0: QP_ERR_ARG.                                             */
+enum {
+    QP_PFORM_PERMUTE_NC = 0,   /* pf::permute_nc                                            */
+    QP_PFORM_PERMUTE_CAPZ,     /* pf::permute_nc_capz<0xF>: lanes 8..11 enter 0; lanes 0..3 defined */
+    QP_PFORM_ROUNDS1_L7,       /* pf::rounds<1, 0x80> on the state entering round 1; lane 7 defined */
+    QP_PFORM_COOP_PERMUTE,     /* pc::permute, one state per wave                           */
+    QP_PFORM_ROW_PERMUTE,      /* pc::permute_row, one state per 16-lane row                */
+    QP_PFORM_MDS_BLOCK,        /* pf::mds_block<-1> (param 0) or mds_block<27> (param 27)   */
+    QP_PFORM_MDS_K,            /* pf::mds_k(s, RC[param]), param 1..29                      */
+    QP_PFORM_MDS_MADS,         /* pf::mds_mads                                              */
+    QP_PFORM_CAPZ_ROUND0,      /* round 0 of permute_nc_capz (8 S-boxes, capz_mds): lanes 8..11 enter 0 */
+    QP_PFORM_MDS_INIT_SPARSE,  /* pf::mds_init_sparse                                       */
+    QP_PFORM_PARTIAL_GROUP,    /* pf::partial_group<param, 4>, param 0, 4, .., 16; <20, 2> folds KLAST */
+    QP_PFORM_FULL_ROUND_DYN,   /* pf::full_round_dyn folding RC[param], param 1..29         */
+    QP_PFORM_PARTIAL_DYN,      /* pf::sbox on lane 0, then mds_rows_block_dyn folding RC[param], 1..29 */
+    QP_PFORM_COOP_MDS,         /* pc::wave_mds_row with pc::mds_coef, one state per wave    */
+    QP_PFORM_ROW_MDS,          /* pc::row_mds with pc::mds_coef, one state per 16-lane row  */
+    QP_PFORM_COUNT
+};
+int qp_debug_poseidon_op(qp_ctx *ctx, uint32_t form, uint32_t param, const uint64_t *states, uint64_t nstates,
+                         uint64_t *out);
 /* host threads (the caller included) of the prover's pool for commit() and the
  * per-proof host stages; default min(hardware threads, 16).  Several provers in
  * one process should split the host cores (cores / provers each).           */

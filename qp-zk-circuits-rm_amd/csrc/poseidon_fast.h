@@ -17,8 +17,8 @@
 //     (addend = the constant's halves), so no round-constant additions are
 //     executed except the first round's;
 //   * each row reduces in 4 instructions: value = al + 2^32 ah with
-//     al, ah < 2^41 -> t = al + eps*hi32(ah) (one mad), t.hi += lo32(ah) with
-//     carry c, t += c*eps.
+//     al, ah < 2^60 (reduce_row) -> t = al + eps*hi32(ah) (one mad),
+//     t.hi += lo32(ah) with carry c, t += c*eps.
 //   * sbox x^7 = x^3 * x^4 on gfn::mul.
 // One form of each piece: the code-shape variants that were measured and lost
 // (compiler mads, C reductions, rolled rounds, multi-row asm blocks) are rows
@@ -54,17 +54,20 @@ __device__ __forceinline__ uint64_t mad_cs(uint32_t x, uint64_t add) {
   return r;
 }
 
-// value = al + 2^32 ah (al, ah < 2^42)  ->  [0, 2^64), same residue
+// value = al + 2^32 ah (al, ah < 2^60)  ->  [0, 2^64), same residue.
+// The dense MDS rows stay below 2^41; the sparse partial rounds hand in up to
+// 2^58.2 (tests/test_poseidon_sparse.py computes the maxima from the tables).
 __device__ __forceinline__ uint64_t reduce_row(uint64_t al, uint64_t ah) {
   uint64_t t, c1, c2;
   uint32_t e;
-  // t = al + eps * hi32(ah)   (< 2^43, no overflow)
+  // t = al + eps * hi32(ah)   (hi32(ah) < 2^28: t < 2^61, no overflow)
   asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c1) : "v"(hi32(ah)), "v"(al));
   // t.hi += lo32(ah), carry c2 (worth 2^64 = eps)
   uint32_t t0 = lo32(t), t1 = hi32(t);
   asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(t1), "=s"(c2) : "v"(t1), "v"(lo32(ah)));
   asm(QP_CWAIT "v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(e) : "s"(c2));
-  // t + e: when c2, t < 2^42 so no overflow
+  // t + e: on a carry the new hi32(t) = old + lo32(ah) - 2^32 < old < 2^29, so
+  // t < 2^61 and adding eps cannot overflow
   const uint64_t tt = ((uint64_t)t1 << 32) | t0;
   uint64_t r;
   asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(r), "=s"(c1) : "v"(e), "v"(tt));
@@ -348,17 +351,6 @@ __device__ __forceinline__ void mds_init_sparse(uint64_t s[12]) {
   for (int i = 0; i < 12; i++) s[i] = out[i];
 }
 
-template <int T, int I = 1>
-__device__ __forceinline__ void sparse_col0(uint64_t s[12], const uint32_t l0[3]) {
-  if constexpr (I < 12) {
-    uint64_t bl = (uint64_t)lo32(s[I]) + (T == 21 ? pfp::KLAST[2 * I] : 0u);
-    uint64_t bh = (uint64_t)hi32(s[I]) + (T == 21 ? pfp::KLAST[2 * I + 1] : 0u);
-    mac_limbs<PT_BV, (T * 11 + I - 1) * 6>(bl, bh, l0);
-    s[I] = reduce_row(bl, bh);
-    sparse_col0<T, I + 1>(s, l0);
-  }
-}
-
 // lane-0 dot product on the 32-bit halves of lanes 1..11 (AH2 pieces of
 // weights 1, 2^22, 2^44; each accumulator < 2^59)
 template <int T, int J = 1, int H = 0, int K = 0>
@@ -384,31 +376,6 @@ __device__ __forceinline__ uint64_t sub_small(uint64_t r, uint32_t y0, uint32_t 
   asm("v_sub_co_u32_e64 %0, %1, %2, %3" : "=v"(r0), "=s"(c) : "v"(r0), "v"(e));
   asm(QP_CWAIT "v_subb_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(r1), "=s"(c) : "v"(r1), "s"(c));
   return ((uint64_t)r1 << 32) | r0;
-}
-
-// partial round 4 + T in sparse form (the next round's constants folded in)
-template <int T>
-__device__ __forceinline__ void partial_sparse(uint64_t s[12]) {
-  const uint64_t x0 = sbox(s[0]);
-  uint32_t l0[3];
-  limbs22(x0, l0);
-  // lane 0's dot product on the S-box output's 32-bit halves (the 22-bit limb
-  // form measured slower: profiles/r02_ab_mul_form_dot_halves.log)
-  // V = S0 + 2^22 S1 + 2^44 S2 + k,  25 x0 = 25 lo + (25 2^10) 2^22 hi
-  constexpr uint32_t kl = pfp::K0[2 * T], kh = pfp::K0[2 * T + 1];
-  uint64_t S[3];
-  asm("v_mad_u64_u32 %0, vcc, %1, 25, %2" : "=v"(S[0]) : "v"(lo32(x0)), "s"((uint64_t)kl) : "vcc");
-  S[1] = (uint64_t)hi32(x0) * 25600u;
-  S[2] = 0;
-  sparse_row0_h<T>(S, s);
-  sparse_col0<T>(s, l0);
-  // al + 2^32 ah - y:  2^22 S1 = 2^22 S1.lo + 2^32 (2^22 S1.hi);
-  // 2^44 S2 = 2^32 (2^12 S2.lo) + 2^76 S2.hi, 2^76 = 2^32 2^12 - 2^12 (mod p)
-  const uint64_t al = S[0] + (uint64_t)lo32(S[1]) * (1u << 22);
-  uint64_t ah = (uint64_t)kh + (uint64_t)hi32(S[1]) * (1u << 22);
-  ah += (uint64_t)lo32(S[2]) * (1u << 12);
-  ah += (uint64_t)hi32(S[2]) * (1u << 12);
-  s[0] = sub_small(reduce_row(al, ah), hi32(S[2]) << 12, hi32(S[2]) >> 20);
 }
 
 // ---- groups of G partial rounds (tools/gen_poseidon_partial.py
@@ -491,8 +458,8 @@ __device__ __forceinline__ void rounds(uint64_t s[12]) {
     rounds<4, OUT>(s);
   } else if constexpr (R >= 4 && R < 26) {
     constexpr int T0 = R - 4, G = (22 - T0) < PF_GROUP ? (22 - T0) : PF_GROUP;
-    if constexpr (G > 1) partial_group<T0, G>(s);
-    else partial_sparse<T0>(s);
+    static_assert(G > 1, "22 partial rounds in groups of PF_GROUP leave no single round");
+    partial_group<T0, G>(s);
     rounds<R + G, OUT>(s);
   } else if constexpr (R < 30) {
     sbox12(s);

@@ -312,14 +312,8 @@ template <int T, class RD>
 __device__ __forceinline__ void qpos_partial(const RD &WR, TermAcc &A, uint64_t s[12]) {
   if constexpr (T < 22) {
     constexpr int G = (22 - T) < pf::PF_GROUP ? (22 - T) : pf::PF_GROUP;
-    if constexpr (G > 1) {
-      pf::partial_group<T, G>(s, QposHook<RD>{WR, A});
-    } else {
-      const uint64_t sb = WR(65 + T);
-      A.emit(gfn::sub(s[0], sb));
-      s[0] = sb;
-      pf::partial_sparse<T>(s);
-    }
+    static_assert(G > 1, "22 partial rounds in groups of PF_GROUP leave no single round");
+    pf::partial_group<T, G>(s, QposHook<RD>{WR, A});
     qpos_partial<T + G>(WR, A, s);
   }
 }

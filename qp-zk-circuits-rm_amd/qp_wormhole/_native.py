@@ -149,6 +149,7 @@ def lib():
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),
         "qp_debug_field_op": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, U64P, VP, ctypes.c_uint64, U64P]),
+        "qp_debug_poseidon_op": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, VP, ctypes.c_uint64, VP]),
         "qp_prover_set_host_threads": (ctypes.c_int, [VP, ctypes.c_uint32]),
         "qp_prover_kernel_stats": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_int]),
@@ -338,6 +339,27 @@ def debug_field_op(ctx, op, a, b=None, param=0):
     out = np.zeros(nout, np.uint64)
     ctx.check(lib().qp_debug_field_op(ctx.h, int(op), int(param), a, None if b is None else b.ctypes.data, a.size,
                                       out), "qp_debug_field_op")
+    return out
+
+
+# qp_debug_poseidon_op forms (include/qpgpu.h QP_PFORM_*)
+(PFORM_PERMUTE_NC, PFORM_PERMUTE_CAPZ, PFORM_ROUNDS1_L7, PFORM_COOP_PERMUTE, PFORM_ROW_PERMUTE, PFORM_MDS_BLOCK,
+ PFORM_MDS_K, PFORM_MDS_MADS, PFORM_CAPZ_ROUND0, PFORM_MDS_INIT_SPARSE, PFORM_PARTIAL_GROUP, PFORM_FULL_ROUND_DYN,
+ PFORM_PARTIAL_DYN, PFORM_COOP_MDS, PFORM_ROW_MDS, PFORM_COUNT) = range(16)
+
+
+def debug_poseidon_op(ctx, form, states, param=0):
+    """TEST-ONLY (qp_debug_poseidon_op): the device Poseidon form `form` on
+    states[i] (12 words each); raw u64 results, [nstates][12].  states=None
+    passes a null pointer (with one state claimed)."""
+    if states is None:
+        n, src = 1, None
+    else:
+        s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, 12)
+        n, src = s.shape[0], s.ctypes.data
+    out = np.zeros((n, 12), np.uint64)
+    ctx.check(lib().qp_debug_poseidon_op(ctx.h, int(form), int(param), src, n, out.ctypes.data),
+              "qp_debug_poseidon_op")
     return out
 
 

@@ -38,16 +38,24 @@ S32 = U(32)
 
 HALVES = [0, 1, 2**31, 2**32 - 2, 2**32 - 1]
 EDGE_VALUES = sorted(set(EDGES) | {(h << 32) | lo for h in HALVES for lo in HALVES})
-# the bounded operands of pf::reduce_row (al, ah < 2^42) and pf::sub_small (y < 2^40)
+# the bounded operands of pf::reduce_row (al, ah < 2^60; lt42 is the range of
+# the dense MDS rows, lt60 the guaranteed domain that the sparse partial rounds
+# use up to 2^58.2) and pf::sub_small (y < 2^40)
 EDGES_42 = sorted({v for v in EDGE_VALUES if v < 2**42} |
                   {2**41, 2**42 - 2**32 - 1, 2**42 - 2**32, 2**42 - 2**32 + 1, 2**42 - 2, 2**42 - 1,
                    2**41 + 2**32 - 1, 2**33, 2**41 - 1})
 EDGES_40 = sorted({v for v in EDGE_VALUES if v < 2**40} |
                   {2**39, 2**40 - 2**32 - 1, 2**40 - 2**32, 2**40 - 2, 2**40 - 1, 2**33})
+HALVES_28 = [0, 1, 2**27, 2**28 - 2, 2**28 - 1]
+EDGES_60 = sorted({v for v in EDGE_VALUES if v < 2**60} |
+                  {(h << 32) | lo for h in HALVES_28 for lo in HALVES} |
+                  {2**60 - 2**32 - 1, 2**60 - 2**32, 2**60 - 2**32 + 1, 2**60 - 2, 2**60 - 1,
+                   2**59 - 1, 2**59, 2**59 + 1, 2**59 + 2**32 - 1, ((2**28 - 1) << 32) | 0xFFFFFFFF,
+                   ((2**28 - 1) << 32) | 0xFFFFFFFE, (2**28 - 1) << 32})
 NRAND = 1 << 16
 
 DOMAINS = {"u64": (EDGE_VALUES, 1 << 64), "canon": ([v for v in EDGE_VALUES if v < P], P),
-           "lt42": (EDGES_42, 1 << 42), "lt40": (EDGES_40, 1 << 40)}
+           "lt42": (EDGES_42, 1 << 42), "lt40": (EDGES_40, 1 << 40), "lt60": (EDGES_60, 1 << 60)}
 
 
 def u64(v):
@@ -134,6 +142,20 @@ def m_gfn_reduce(lo, hi):
     cd = bit(l1 + cc > EPS)  # documented: cannot carry out
     l1 = lo32(l1 + cc)
     return l1 << S32 | l0, bo2 | c << U(1) | cb << U(2) | cc << U(3) | cd << U(4)
+
+
+def m_reduce_row(al, ah):
+    """pf::reduce_row / reduce_row_c for al, ah < 2^60: t = al + eps hi32(ah)
+    (< 2^61: cannot wrap); t.hi += lo32(ah) with carry c (worth 2^64 = eps);
+    + c eps (on a carry the new t.hi < 2^29: cannot wrap)."""
+    t = al + hi32(ah) * EPS
+    ct = bit(t < al)
+    t1 = hi32(t) + lo32(ah)
+    c = hi32(t1)
+    tt = lo32(t1) << S32 | lo32(t)
+    r = tt + c * EPS
+    c3 = bit(r < tt)
+    return r, c | ct << U(1) | c3 << U(2)
 
 
 def m_mul(a, b):
@@ -238,7 +260,7 @@ def m_acc3(a, b, K):
     return m_sub(r, top << S32)[0], paths
 
 
-NEVER = {"add": 0b100, "sub": 0b100, "nt_reduce": 0b1010, "gfn_reduce": 0b10000, "mul": 0b10100, "acc3_mac": 0b1000}
+NEVER = {"reduce_row": 0b110, "add": 0b100, "sub": 0b100, "nt_reduce": 0b1010, "gfn_reduce": 0b10000, "mul": 0b10100, "acc3_mac": 0b1000}
 
 
 def never_pow2(E):
@@ -356,6 +378,7 @@ REACHABLE = {
     "gfn_reduce": [0, 1, 3, 4, 5, 12, 13, 15],
     "mul": [0, 1, 2, 3, 8],  # a borrow of t - w3 (8) only without the carries cu and c1
     "acc3_mac": [0, 1, 2, 3, 4, 5, 6, 7],
+    "reduce_row": [0, 1],
 }
 # mul_pow2<E>, the same for every E of a shift regime
 REACHABLE_POW2 = {E: [0] if E == 0 else [0, 4] if E < 32 else [0, 1, 4] if E < 64 else [0, 1] if E < 96 else
@@ -369,6 +392,7 @@ MODELLED = {
     "nt_reduce": (m_nt_reduce, ("u64", "u64")),
     "gfn_reduce": (m_gfn_reduce, ("u64", "u64")),
     "mul": (m_mul, ("u64", "u64")),
+    "reduce_row": (m_reduce_row, ("lt60", "lt60")),
 }
 POW2_E = list(range(0, 192, 6))
 ACC3_K = [1, 2, 16, 123]
@@ -471,7 +495,8 @@ def test_models_agree_with_integers(name):
         model, doms = MODELLED[name]
         a, b = pair_set(*doms)
         ref = {"add": lambda x, y: (x + y) % P, "sub": lambda x, y: (x - y) % P, "mul": lambda x, y: x * y % P,
-               "nt_reduce": lambda x, y: (x + (y << 64)) % P, "gfn_reduce": lambda x, y: (x + (y << 64)) % P}[name]
+               "nt_reduce": lambda x, y: (x + (y << 64)) % P, "gfn_reduce": lambda x, y: (x + (y << 64)) % P,
+               "reduce_row": lambda x, y: (x + (y << 32)) % P}[name]
         assert residues(model(a, b)[0]) == [ref(x, y) for x, y in zip(ints(a), ints(b))]
 
 
@@ -515,6 +540,10 @@ BINARY = {
     "gl_reduce128": (N.FOP_GL_REDUCE128, ("u64", "u64"), lambda a, b: (a + (b << 64)) % P, True, None),
     "pf_reduce_row": (N.FOP_PF_REDUCE_ROW, ("lt42", "lt42"), lambda a, b: (a + (b << 32)) % P, False, None),
     "pf_reduce_row_c": (N.FOP_PF_REDUCE_ROW_C, ("lt42", "lt42"), lambda a, b: (a + (b << 32)) % P, False, None),
+    "pf_reduce_row_60": (N.FOP_PF_REDUCE_ROW, ("lt60", "lt60"), lambda a, b: (a + (b << 32)) % P, False,
+                         "reduce_row"),
+    "pf_reduce_row_c_60": (N.FOP_PF_REDUCE_ROW_C, ("lt60", "lt60"), lambda a, b: (a + (b << 32)) % P, False,
+                           "reduce_row"),
     "pf_sub_small": (N.FOP_PF_SUB_SMALL, ("u64", "lt40"), lambda a, b: (a - b) % P, False, None),
     "pf_mul": (N.FOP_PF_MUL, ("u64", "u64"), lambda a, b: a * b % P, False, "mul"),
     "pf_mul_c": (N.FOP_PF_MUL_C, ("u64", "u64"), lambda a, b: a * b % P, False, "mul"),

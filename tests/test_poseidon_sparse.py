@@ -55,3 +55,95 @@ def test_dot_pieces_bounds():
                 c = A[r][0][j] * (1 << (32 * h)) % g.P
                 assert (c & 0x3FFFFF) < 1 << 22 and ((c >> 22) & 0x3FFFFF) < 1 << 22 and (c >> 44) < 1 << 20
     assert 22 * (2**32 - 1) * (2**22 - 1) + 25 * 2**32 + 2**32 < 2**59
+
+
+# ---- accumulator bounds of the sparse rounds, from the generator's tables ------
+# Worst cases with every 22-bit limb at 2^22 - 1, 2^22 - 1, 2^20 - 1 and every
+# 32-bit half at 2^32 - 1, of every accumulator poseidon_fast.h hands to
+# reduce_row (tested for al, ah < 2^60: test_gpu_field_ops.py "lt60") and to
+# sub_small (y < 2^40: "lt40").
+
+PF_GROUP = 4
+LMAX = (2**22 - 1, 2**22 - 1, 2**20 - 1)
+H32 = 2**32 - 1
+REDUCE_ROW_DOMAIN = 2**60
+SUB_SMALL_DOMAIN = 2**40
+
+
+def _limb_mac_max(g, c):
+    """(al, ah) increments of mac_limbs over one constant's limb halves"""
+    lc = g.limbs_consts(c)
+    return sum(m * l for m, (l, _) in zip(LMAX, lc)), sum(m * h for m, (_, h) in zip(LMAX, lc))
+
+
+def sparse_accumulator_maxima():
+    g = _gen()
+    A, init_rows, init_k, kscalar, c26 = g.derive()
+    gam = g.gammas(A)
+    worst = {"mds_init_sparse": 0, "group_lane0": 0, "S": 0, "group_cols": 0, "sub_small_y": 0, "intermediate": 0}
+
+    def see(name, *vals):
+        worst[name] = max(worst[name], *vals)
+        worst["intermediate"] = max(worst["intermediate"], *vals)
+
+    # mds_init_sparse: row 0 dense on halves, rows 1..11 on the limbs of all lanes
+    assert init_rows[0] == g.M[0]
+    see("mds_init_sparse", sum(g.M[0]) * H32 + (init_k[0] & H32), sum(g.M[0]) * H32 + (init_k[0] >> 32))
+    for i in range(1, 12):
+        macs = [_limb_mac_max(g, init_rows[i][j]) for j in range(12)]
+        see("mds_init_sparse", (init_k[i] & H32) + sum(m[0] for m in macs), (init_k[i] >> 32) + sum(m[1] for m in macs))
+    groups = [(t0, min(PF_GROUP, 22 - t0)) for t0 in range(0, 22, PF_GROUP)]
+    assert groups[-1] == (20, 2) and all(G > 1 for _, G in groups)
+    for t0, G in groups:
+        for m in range(G):
+            t = t0 + m
+            k0 = kscalar[t + 5] if t < 21 else c26[0]
+            # S[k]: the AH2 pieces (weights 1, 2^22, 2^44) times the halves of lanes 1..11
+            pieces = [[c & 0x3FFFFF, (c >> 22) & 0x3FFFFF, c >> 44]
+                      for j in range(11) for h in range(2) for c in [A[t + 4][0][j] * (1 << (32 * h)) % g.P]]
+            S = [sum(p[k] for p in pieces) * H32 for k in range(3)]
+            S[0] += 25 * H32 + (k0 & H32)
+            S[1] += 25600 * H32
+            see("S", *S)
+            # al + 2^32 ah - y as group_lane0 combines them, then the gamma terms
+            gmacs = [_limb_mac_max(g, gam[t][t0 + l]) for l in range(m)]
+            parts_l = [S[0], min(S[1], H32) << 22]
+            parts_h = [k0 >> 32, (S[1] >> 32) << 22, min(S[2], H32) << 12, (S[2] >> 32) << 12]
+            see("intermediate", *parts_l, *parts_h)
+            see("group_lane0", sum(parts_l) + sum(x[0] for x in gmacs), sum(parts_h) + sum(x[1] for x in gmacs))
+            see("sub_small_y", (S[2] >> 32) << 12)
+        last = t0 + G == 22
+        for i in range(1, 12):
+            macs = [_limb_mac_max(g, A[t0 + m + 4][1][i - 1]) for m in range(G)]
+            see("group_cols", H32 + ((c26[i] & H32) if last else 0) + sum(x[0] for x in macs),
+                H32 + ((c26[i] >> 32) if last else 0) + sum(x[1] for x in macs))
+    return worst
+
+
+def test_tested_domains_are_the_field_op_domains():
+    from test_gpu_field_ops import BINARY, DOMAINS
+    assert DOMAINS["lt60"][1] == REDUCE_ROW_DOMAIN and DOMAINS["lt40"][1] == SUB_SMALL_DOMAIN
+    assert BINARY["pf_reduce_row_60"][1] == ("lt60", "lt60") and BINARY["pf_sub_small"][1] == ("u64", "lt40")
+
+
+def test_sparse_accumulators_stay_in_the_tested_domains():
+    """INIT, BV, GAM, K0, KLAST and AH2 keep every accumulator of
+    mds_init_sparse, group_lane0 and group_cols inside the domains reduce_row
+    and sub_small are tested on, and no intermediate reaches 2^64 (reduce_row's
+    own t = al + eps hi32(ah) included).  The maxima are the figures of
+    DESIGN.md "Edge-value tests of the carry chains"."""
+    import math
+    w = sparse_accumulator_maxima()
+    for name in ("mds_init_sparse", "group_lane0", "group_cols"):
+        assert w[name] < REDUCE_ROW_DOMAIN, (name, math.log2(w[name]))
+        assert w[name] + H32 * (w[name] >> 32) < 2**64
+    assert w["S"] < 2**64 and w["intermediate"] < 2**64
+    assert w["sub_small_y"] < SUB_SMALL_DOMAIN
+    # the recorded maxima (log2, rounded up to 0.01): a generator or PF_GROUP
+    # change that moves them shows here
+    for name, bound in SPARSE_MAXIMA_LOG2.items():
+        assert bound - 0.01 <= math.log2(w[name]) < bound, (name, math.log2(w[name]))
+
+
+SPARSE_MAXIMA_LOG2 = {"mds_init_sparse": 58.11, "group_lane0": 58.07, "S": 57.71, "group_cols": 56.76,
+                      "sub_small_y": 35.70}
