@@ -392,6 +392,59 @@ int qp_prover_kernel_stats(qp_prover *p, double *ms, double *units, uint64_t *la
  * inputs (host), [9] device witness generation; reset != 0 clears */
 int qp_prover_stage_times(qp_prover *p, double *ms, uint32_t n, int reset);
 
+/* ---- voter registry (device) ------------------------------------------------
+ * The electorate's Merkle tree of a proposal, built once, and the Merkle paths
+ * the voting circuit walks, by voter index.  The reference has no such object:
+ * its test builds the tree with a host loop (voting/src/lib.rs:285-316), and
+ * that loop is the convention: leaf = hash_no_pad(private key), node =
+ * hash_no_pad(left || right), the last node of an odd-length level moves to
+ * the next level unchanged.  A voter's path holds the siblings of the levels
+ * where its node was hashed, in order from the leaf, one side bit each
+ * (VotePrivateInputs.merkle_siblings / path_indices / actual_merkle_depth,
+ * lib.rs:42-52, as the circuit's walk reads them, :123-180); promoted levels
+ * contribute nothing.  A registry belongs to its context: free it before
+ * qp_ctx_destroy.                                                          */
+typedef struct qp_registry qp_registry;
+/* replaces the leaf and level loops of voting/src/lib.rs:292-316.  keys
+ * [n][4] canonical felts.  QP_ERR_ARG for n == 0, a felt >= p, or n > 2^31 (a
+ * path deeper than 31 does not fit the circuit's 5-bit depth split).  Device
+ * memory: 64 n bytes of digests (every level stays resident).              */
+int qp_registry_new(qp_ctx *ctx, const uint64_t *keys, uint64_t n, qp_registry **out);
+void qp_registry_free(qp_registry *r);
+/* VotePublicInputs.merkle_root (lib.rs:318) */
+int qp_registry_root(const qp_registry *r, uint64_t out[4]);
+/* the voter count and the deepest path, ceil(log2 n) (either may be NULL) */
+int qp_registry_size(const qp_registry *r, uint64_t *n, uint32_t *max_depth);
+/* replaces the hand-picked merkle_siblings / path_indices /
+ * actual_merkle_depth of lib.rs:320-322 for voters idx[0..nidx): siblings
+ * [nidx][32][4] (the zero digest from the depth up, as fill_targets sets
+ * them, lib.rs:254-257), path_bits[b] bit j = path_indices[j] (1: the voter's
+ * node is the right child), depth[b] = actual_merkle_depth.  An index >= n
+ * is QP_ERR_ARG (checked before the launch).                               */
+int qp_registry_paths(qp_registry *r, const uint64_t *idx, uint32_t nidx, uint64_t *siblings, uint32_t *path_bits,
+                      uint32_t *depth);
+/* copies one level's digests [len][4] (level 0 = the leaves, the last = the
+ * root); out == NULL: only *len.  Test/diagnostic entry point.             */
+int qp_registry_level(qp_registry *r, uint32_t level, uint64_t *out, uint64_t *len);
+/* HIP-event times of the build on the context's stream (ms): [0] key upload,
+ * [1] leaf digests (n permutations), [2] the levels (n - 1 permutations).
+ * Diagnostic entry point (tools/registry_bench.py).                        */
+int qp_registry_build_times(const qp_registry *r, double ms[3]);
+/* one voter's ballot: the public inputs the voter chooses (lib.rs:324-326) */
+typedef struct {
+    uint64_t proposal_id[4];
+    uint8_t vote;                      /* 0 = no, 1 = yes */
+    const uint64_t *zk_randomness;     /* as in qp_voting_inputs */
+} qp_vote_ballot;
+/* create_test_inputs + prove (lib.rs:285-343, :346-357) for voters idx[] of
+ * a registry: the private key and the root are the registry's, the path comes
+ * from the device tree, the nullifier is H(leaf || proposal_id) (lib.rs:
+ * 277-283); then qp_prover_prove_voting_inputs on those inputs, so the proofs
+ * are the bytes that call gives for the same inputs.  The prover must be a
+ * voting-circuit prover of the registry's context (QP_ERR_ARG otherwise).  */
+int qp_prover_prove_voters(qp_prover *p, qp_registry *r, const uint64_t *idx, const qp_vote_ballot *ballots,
+                           uint32_t nproofs, uint8_t *out, size_t stride, size_t *lens);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

@@ -10,6 +10,7 @@
 #include "poseidon_coop.h"
 #include <stdlib.h>
 #include "kernels.h"
+#include "merkle_node.h"
 #include "paths.h"
 
 // Leaf digests and the first tree level are separate launches: one kernel
@@ -113,10 +114,7 @@ __global__ void __launch_bounds__(256) k_merkle_levels(uint64_t *__restrict__ di
 #pragma unroll
         for (int j = 0; j < 8; j++) s[j] = sh[t * 8 + j];
       }
-      s[8] = s[9] = s[10] = s[11] = 0;
-      psd::permute_nc_node(s);
-#pragma unroll
-      for (int j = 0; j < 4; j++) s[j] = psd::canon(s[j]);
+      node_digest(s);
       uint64_t *o = digests + (top - ((uint64_t)1 << (log_N - k + 1))) * 4 + (uint64_t)((base >> l) + t) * 4;
 #pragma unroll
       for (int j = 0; j < 4; j++) o[j] = s[j];
@@ -143,6 +141,9 @@ __global__ void __launch_bounds__(256) k_merkle_level(uint64_t *__restrict__ dig
   uint64_t s[12];
 #pragma unroll
   for (int j = 0; j < 8; j++) s[j] = c[j];
+  // node_digest (merkle_node.h) with the canonicalisation at the store: the
+  // form this kernel was measured in (canonicalising before the address is
+  // formed gave other code for the store's addressing)
   s[8] = s[9] = s[10] = s[11] = 0;
   psd::permute_nc_node(s);
   uint64_t *o = digests + (top - ((uint64_t)1 << (log_N - k + 1))) * 4 + (uint64_t)t * 4;

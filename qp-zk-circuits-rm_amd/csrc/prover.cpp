@@ -25,6 +25,7 @@
 #include "host_util.h"
 #include "kernels.h"
 #include "prover_kernels.h"
+#include "registry.h"
 #include "witness_kernels.h"
 #include "paths.h"
 
@@ -1240,6 +1241,50 @@ int qp_prover_prove_voting_inputs(qp_prover *P, const qp_voting_inputs *in, uint
   TRY(hipSetDevice(P->ctx->device));
   try {
     return prove_inputs(P, voting_fill, (const uint8_t *)in, sizeof(qp_voting_inputs), nproofs, out, stride, lens);
+  } catch (const std::bad_alloc &) {
+    return QP_ERR_OOM;
+  }
+}
+
+// voters of a registry: the inputs qp_prover_prove_voting_inputs takes, filled
+// from the device tree's path buffers (k_registry_paths' layout)
+int qp_prover_prove_voters(qp_prover *P, qp_registry *r, const uint64_t *idx, const qp_vote_ballot *ballots,
+                           uint32_t nproofs, uint8_t *out, size_t stride, size_t *lens) {
+  if (!P || !r || !idx || !ballots || !out || !nproofs) return QP_ERR_ARG;
+  if (r->ctx != P->ctx) {
+    P->ctx->err = "the registry belongs to another context than the prover";
+    return QP_ERR_ARG;
+  }
+  if (P->circuit->kind != qp_circuit::VOTING) {
+    P->ctx->err = "prover circuit is not the voting circuit";
+    return QP_ERR_ARG;
+  }
+  try {
+    constexpr uint32_t S = qpk::REG_PATH_SLOTS;
+    std::vector<uint64_t> sib((size_t)nproofs * S * 4), leaf((size_t)nproofs * 4);
+    std::vector<uint32_t> bits(nproofs), depth(nproofs);
+    std::vector<uint8_t> path((size_t)nproofs * S);
+    std::vector<qp_voting_inputs> in(nproofs);
+    int rc = registry_paths_host(r, idx, nproofs, sib.data(), bits.data(), depth.data(), leaf.data());
+    if (rc) return rc;
+    for (uint32_t b = 0; b < nproofs; b++) {
+      qp_voting_inputs &v = in[b];
+      memcpy(v.proposal_id, ballots[b].proposal_id, 32);
+      memcpy(v.merkle_root, r->root, 32);
+      uint64_t h[8];
+      memcpy(h, &leaf[(size_t)b * 4], 32);
+      memcpy(h + 4, ballots[b].proposal_id, 32);
+      qh::hash_no_pad(h, 8, v.nullifier);
+      v.vote = ballots[b].vote != 0;
+      memcpy(v.private_key, &r->keys[idx[b] * 4], 32);
+      for (uint32_t j = 0; j < depth[b]; j++) path[(size_t)b * S + j] = (bits[b] >> j) & 1;
+      v.num_siblings = v.num_path_indices = depth[b];
+      v.siblings = &sib[(size_t)b * S * 4];
+      v.path_indices = &path[(size_t)b * S];
+      v.actual_merkle_depth = depth[b];
+      v.zk_randomness = ballots[b].zk_randomness;
+    }
+    return qp_prover_prove_voting_inputs(P, in.data(), nproofs, out, stride, lens);
   } catch (const std::bad_alloc &) {
     return QP_ERR_OOM;
   }

@@ -1,0 +1,171 @@
+// registry.hip — the voter registry's eligibility tree and Merkle paths
+// (gfx950).  The tree is the reference's (voting/src/lib.rs:285-316): leaf =
+// hash_no_pad(key), node = hash_no_pad(left || right), a lone last node of an
+// odd level moves up unchanged; the paths are the ones the voting circuit
+// walks (:123-180): the siblings of the levels where the voter's node was
+// hashed, compacted, with one side bit each.
+// VALU-bound like merkle.hip: one lane per leaf / parent, one capacity-zero
+// permutation each (merkle_node.h), the state in registers.
+#include "registry_kernels.h"
+#include "merkle_node.h"
+
+namespace qpk {
+
+bool registry_levels(uint64_t n, RegistryLevels &lv) {
+  if (!n) return false;
+  RegistryLevels t;
+  uint64_t o = 0;
+  for (uint64_t len = n;; len = (len + 1) / 2) {
+    if (t.nlevels == REG_MAX_LEVELS) return false;
+    t.off[t.nlevels] = o;
+    t.len[t.nlevels] = len;
+    t.nlevels++;
+    o += len;
+    if (len == 1) break;
+  }
+  lv = t;
+  return true;
+}
+
+// leaf i = hash_no_pad(key i): the four felts of a key are four coalesced
+// column loads (64 lanes x 8 B = 512 contiguous bytes each)
+__global__ void __launch_bounds__(256) k_registry_leaves(const uint64_t *__restrict__ keys, uint64_t n,
+                                                         uint64_t *__restrict__ dig) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint64_t s[12];
+#pragma unroll
+  for (int k = 0; k < 4; k++) s[k] = keys[(uint64_t)k * n + i];
+  s[4] = s[5] = s[6] = s[7] = 0;
+  node_digest(s);
+  uint64_t *o = dig + i * 4;
+#pragma unroll
+  for (int k = 0; k < 4; k++) o[k] = s[k];
+}
+
+// one wide level: lane t hashes nodes 2t, 2t+1 of src into node t of dst.  The
+// lone last node of an odd src is copied by lane 0 once its own hash is
+// stored (a branch around the permutation for that one lane cost every lane
+// registers: 84 and 108 VGPRs in two forms against this form's count)
+__global__ void __launch_bounds__(256) k_registry_level(const uint64_t *__restrict__ src, uint64_t nsrc,
+                                                        uint64_t *__restrict__ dst) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t npair = nsrc / 2;
+  if (t >= npair) return;
+  const uint64_t *c = src + t * 8;
+  uint64_t s[12];
+#pragma unroll
+  for (int j = 0; j < 8; j++) s[j] = c[j];
+  node_digest(s);
+  uint64_t *o = dst + t * 4;
+#pragma unroll
+  for (int j = 0; j < 4; j++) o[j] = s[j];
+  if (t == 0 && (nsrc & 1)) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) dst[npair * 4 + j] = src[(nsrc - 1) * 4 + j];
+  }
+}
+
+// every level above level l0 (at most REG_FOLD_MAX nodes) in one wave: the
+// nodes fold through LDS level by level, every level written out
+__global__ void __launch_bounds__(REG_FOLD_MAX) k_registry_fold(uint64_t *__restrict__ dig, RegistryLevels lv,
+                                                                uint32_t l0) {
+  __shared__ uint64_t sh[REG_FOLD_MAX * 4];
+  const uint32_t t = threadIdx.x;
+  if (t < lv.len[l0]) {
+    const uint64_t *c = dig + (lv.off[l0] + t) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; j++) sh[t * 4 + j] = c[j];
+  }
+  __syncthreads();
+  for (uint32_t l = l0 + 1; l < lv.nlevels; l++) {
+    const uint32_t nsrc = (uint32_t)lv.len[l - 1], ndst = (uint32_t)lv.len[l];
+    uint64_t s[12];
+    if (t < ndst) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) s[j] = sh[t * 8 + j];
+      if (2 * t + 1 < nsrc) {
+#pragma unroll
+        for (int j = 4; j < 8; j++) s[j] = sh[t * 8 + j];
+        node_digest(s);
+      }
+      uint64_t *o = dig + (lv.off[l] + t) * 4;
+#pragma unroll
+      for (int j = 0; j < 4; j++) o[j] = s[j];
+    }
+    __syncthreads();
+    if (t < ndst) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) sh[t * 4 + j] = s[j];
+    }
+    __syncthreads();
+  }
+}
+
+// one lane per (voter of the batch, level): 32 lanes per voter, two voters per
+// wave.  Lane l marks whether the voter's node at level l was hashed (it has a
+// sibling) or promoted; the voter's half of the wave ballot is its level mask,
+// so the slot of lane l's sibling is the count of hashed levels below l.
+// Every one of the voter's 32 sibling slots is written exactly once: slots
+// below the depth by the hashed lanes, slot l >= depth (zero digest) by lane l.
+__global__ void __launch_bounds__(256) k_registry_paths(const uint64_t *__restrict__ dig, RegistryLevels lv,
+                                                        const uint64_t *__restrict__ idx, uint32_t nidx,
+                                                        uint64_t *__restrict__ siblings,
+                                                        uint32_t *__restrict__ path_bits, uint32_t *__restrict__ depth,
+                                                        uint64_t *__restrict__ leaves) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t b = g >> 5, l = g & 31;
+  const bool valid = b < nidx;
+  const uint64_t i = valid ? idx[b] : 0;
+  const uint64_t sib = (i >> l) ^ 1;
+  const bool hashed = valid && l + 1 < lv.nlevels && sib < lv.len[l];
+  const uint32_t m = (uint32_t)(__ballot(hashed) >> (threadIdx.x & 32));
+  if (!valid) return;
+  const uint32_t d = __popc(m);
+  uint64_t *out = siblings + (uint64_t)b * REG_PATH_SLOTS * 4;
+  if (hashed) {
+    const uint64_t *c = dig + (lv.off[l] + sib) * 4;
+    uint64_t *o = out + __popc(m & ((1u << l) - 1)) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = c[j];
+  }
+  if (l >= d) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) out[l * 4 + j] = 0;
+  }
+  if (l == 0) {
+    uint32_t bits = 0, k = 0;
+    for (uint32_t mm = m; mm; mm &= mm - 1, k++) bits |= (uint32_t)((i >> (__ffs(mm) - 1)) & 1) << k;
+    path_bits[b] = bits;
+    depth[b] = d;
+    if (leaves) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) leaves[(uint64_t)b * 4 + j] = dig[i * 4 + j];
+    }
+  }
+}
+
+void registry_leaves(const uint64_t *keys, uint64_t n, uint64_t *dig, hipStream_t s) {
+  k_registry_leaves<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(keys, n, dig);
+}
+
+void registry_tree(uint64_t *dig, const RegistryLevels &lv, hipStream_t s) {
+  for (uint32_t l = 1; l < lv.nlevels; l++) {
+    if (lv.len[l - 1] <= REG_FOLD_MAX) {
+      k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
+      return;
+    }
+    // one lane per pair (len > REG_FOLD_MAX: at least 32 pairs)
+    k_registry_level<<<(unsigned)((lv.len[l - 1] / 2 + 255) / 256), 256, 0, s>>>(dig + lv.off[l - 1] * 4,
+                                                                                   lv.len[l - 1], dig + lv.off[l] * 4);
+  }
+}
+
+void registry_paths(const uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, uint32_t nidx,
+                    uint64_t *siblings, uint32_t *path_bits, uint32_t *depth, uint64_t *leaves, hipStream_t s) {
+  if (!nidx) return;
+  k_registry_paths<<<(unsigned)(((uint64_t)nidx * REG_PATH_SLOTS + 255) / 256), 256, 0, s>>>(
+      dig, lv, idx, nidx, siblings, path_bits, depth, leaves);
+}
+
+}  // namespace qpk
