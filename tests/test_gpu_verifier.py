@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import fri_shapes as fs
 import verifier_cases as vc
 from current_circuit_vd import cap_entry
 from oracle_lib import GOLDEN, P, golden, lib as olib
@@ -121,6 +122,51 @@ def test_device_equals_host_equals_oracle(current):
                                         if not g == h == w]
         assert {0, 3, 4, 5, 6, 7, 9} <= set(got)
     bench.close()
+
+
+@pytest.mark.parametrize("shape", fs.SHAPES, ids=fs.shape_id)
+def test_fri_shapes_device_equals_host_equals_oracle(shape):
+    """k_verify_paths / k_verify_fri at the FRI shapes beyond the fixtures' arity-16 reductions
+    (fri_shapes.SHAPES: arities 2..64 and mixes, 0 and 8 layers, 12 path classes, all-cap layer
+    trees, width-4 layer leaves, cap height 0, 1 / odd / 64 queries): the oracle's proof of the
+    voting circuit under the shape and its whole tamper set in one chunk.  The statuses must
+    cover every stage a byte tamper reaches (fri_shapes.status_floor; 8, the final polynomial,
+    is out of reach: it is observed before PoW and the query indices)."""
+    from qp_wormhole import WormholeVerifier
+    vo, cb, _ = fs.oracle_case(shape)
+    batch = fs.tamper_cases(shape)
+    proofs = [pf for _, pf, _ in batch]
+    dev = device_verifier(vo, cb, max_batch=len(proofs))
+    host = WormholeVerifier.new_from_bytes(vo, cb, device=None, max_batch=len(proofs))
+    got, on_host = dev.verify_batch(proofs), host.verify_batch(proofs)
+    dev.close()
+    host.close()
+    want = [vc.expect(rc) for _, _, rc in batch]
+    assert got == on_host == want, [(lab, g, h, w) for (lab, _, _), g, h, w in zip(batch, got, on_host, want)
+                                    if not g == h == w]
+    assert fs.status_floor(shape) <= set(got), sorted(set(got))
+
+
+@pytest.mark.parametrize("shape", [fs.SHAPES[10], fs.SHAPES[11]], ids=fs.shape_id)
+def test_fri_shapes_odd_lane_chunks(shape):
+    """[4,3] / 63 queries and [2,2,2,2] / 5 queries through a device verifier of max_batch = 3:
+    7 proofs run as chunks of 3, 3, 1, each with an odd lane count (the u32 index arrays end in
+    a padded word), and 3 * 63 lanes * 6 classes cross several 256-lane blocks and class
+    boundaries inside a block.  Statuses equal each proof verified alone and the oracle's; the
+    pick (fri_shapes.chunk_pick) puts a valid and a tampered proof at every chunk
+    position, so a slot reading its neighbour's arrays shows."""
+    vo, cb, _ = fs.oracle_case(shape)
+    proofs, valid = fs.chunk_pick(shape)
+    want = [vc.expect(vc.ora(vo + cb, p)) for p in proofs]
+    assert [w == 0 for w in want] == valid
+    one = device_verifier(vo, cb, max_batch=1)
+    alone = [one.verify_batch([p])[0] for p in proofs]
+    one.close()
+    dev = device_verifier(vo, cb, max_batch=3)
+    assert dev.max_batch == 3
+    got = dev.verify_batch(proofs)
+    dev.close()
+    assert got == alone == want, (got, alone, want)
 
 
 @pytest.mark.parametrize("n", [1, 2, 65, 130])

@@ -92,7 +92,10 @@ def flip(pf, off, bit=0):
 
 
 def tamper_set(vd, cb, pf):
-    """[(label, proof bytes)]: the proof itself first, then the tampered variants."""
+    """[(label, proof bytes)]: the proof itself first, then the tampered variants.
+    Valid for any FRI shape the verifier accepts: the query picks are clamped to
+    nq and deduplicated (nq = 1 has one), and a layer whose tree is all cap has
+    no sibling to change, so another element of its leaf is changed instead."""
     lay = Layout(cb)
     nq = lay.d["nq"]
     qidx = query_indices(vd, pf, lay)
@@ -101,7 +104,7 @@ def tamper_set(vd, cb, pf):
         cases.append((f"{what} opening", flip(pf, lay.openings + 16 * (lay.open_at[what] + k))))
     cases.append(("public input", flip(pf, len(pf) - 100)))
     cases.append(("pow witness", flip(pf, lay.pow + 1)))
-    for q in (0, nq // 2, nq - 1):
+    for q in dict.fromkeys((0, nq // 2, nq - 1)):
         for o in range(4):
             leaf, nsib = lay.tree(q, o)
             cases.append((f"q{q} tree{o} leaf", flip(pf, leaf + 8 * (lay.widths[o] // 2))))
@@ -113,12 +116,15 @@ def tamper_set(vd, cb, pf):
         shift += a
         cases.append((f"layer{l} queried element", flip(pf, ev + 16 * within + 2)))
         cases.append((f"layer{l} other element", flip(pf, ev + 16 * ((within + 3) % (1 << a)) + 10)))
-        cases.append((f"layer{l} sibling", flip(pf, nsib + 1 + 32 * (s - 1) + 17)))
+        if s:
+            cases.append((f"layer{l} sibling", flip(pf, nsib + 1 + 32 * (s - 1) + 17)))
+        else:
+            cases.append((f"layer{l} leaf, no sibling", flip(pf, ev + 16 * ((within + 1) % (1 << a)) + 1)))
     cases.append(("final poly", flip(pf, lay.final_poly + 16 * (lay.final_len // 2))))
     cases.append(("truncated", pf[:-1]))
     cases.append(("extra byte", pf + b"\0"))
-    cases.append(("sibling count", flip(pf, lay.tree(1, 2)[1], 1)))
-    at = lay.tree(2, 1)[0] + 8 * 7
+    cases.append(("sibling count", flip(pf, lay.tree(min(1, nq - 1), 2)[1], 1)))
+    at = lay.tree(min(2, nq - 1), 1)[0] + 8 * 7
     cases.append(("element = p", pf[:at] + struct.pack("<Q", P) + pf[at + 8:]))
     return cases
 
