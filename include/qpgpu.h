@@ -430,6 +430,38 @@ int qp_registry_level(qp_registry *r, uint32_t level, uint64_t *out, uint64_t *l
  * [1] leaf digests (n permutations), [2] the levels (n - 1 permutations).
  * Diagnostic entry point (tools/registry_bench.py).                        */
 int qp_registry_build_times(const qp_registry *r, double ms[3]);
+
+/* ---- a registry from commitments: what an election operator holds ----------
+ * The operator never sees a private key, only each voter's commitment, the
+ * leaf hash_no_pad(key) the voter sends when registering; voters arrive over
+ * time and some are struck off.  A commitment registry keeps no keys, reserves
+ * room to grow in place and is updated on the device: an update recomputes
+ * only the nodes it changes.  The entries above work on it as on a keyed one,
+ * except that on an empty one (n == 0) qp_registry_root, _paths and _level
+ * return QP_ERR_STATE; qp_registry_build_times then gives the last build or
+ * update: [0] upload, [1] 0 (there is no leaf kernel), [2] the levels.
+ * qp_prover_prove_voters on it is QP_ERR_STATE (it holds no keys); the calls
+ * below on a registry made by qp_registry_new are QP_ERR_STATE too (its host
+ * key copy would go stale).  A refused call leaves the registry as it was:
+ * same root, size and epoch.  A path is valid only under the root of the
+ * epoch it was taken in.                                                   */
+/* a registry over registered commitments: leaves[n][4] canonical felts, each the voter's
+ * hash_no_pad(private key), computed by the voter.  n may be 0 (registration opens empty).
+ * capacity >= max(n, 1), <= 2^31: the digest buffer is laid out for `capacity` leaves
+ * (64 * capacity bytes), so the tree can grow in place.  No keys are held anywhere.       */
+int qp_registry_new_commitments(qp_ctx *ctx, const uint64_t *leaves, uint64_t n, uint64_t capacity, qp_registry **out);
+/* registers k more voters at indices [n, n + k); *first (may be NULL) = n before the call.
+ * n + k > capacity: QP_ERR_ARG (call qp_registry_reserve); a felt >= p: QP_ERR_ARG naming
+ * the voter and the felt; k == 0: QP_OK, nothing changes                                  */
+int qp_registry_append(qp_registry *r, const uint64_t *leaves, uint64_t k, uint64_t *first);
+/* replaces the commitments of voters idx[0..k) (each < n, no index twice); a voter is
+ * struck off by replacing the commitment with one nobody holds a key for                  */
+int qp_registry_replace(qp_registry *r, const uint64_t *idx, const uint64_t *leaves, uint32_t k);
+/* moves the tree to a layout for new_capacity >= n leaves (device-to-device, level by level) */
+int qp_registry_reserve(qp_registry *r, uint64_t new_capacity);
+/* capacity, and the number of completed append / replace / reserve calls (either may be NULL);
+ * a keyed registry reports capacity == n and epoch == 0                                   */
+int qp_registry_state(const qp_registry *r, uint64_t *capacity, uint64_t *epoch);
 /* one voter's ballot: the public inputs the voter chooses (lib.rs:324-326) */
 typedef struct {
     uint64_t proposal_id[4];

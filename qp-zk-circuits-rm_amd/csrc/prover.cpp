@@ -1259,6 +1259,11 @@ int qp_prover_prove_voters(qp_prover *P, qp_registry *r, const uint64_t *idx, co
     P->ctx->err = "prover circuit is not the voting circuit";
     return QP_ERR_ARG;
   }
+  if (!r->keyed) {
+    P->ctx->err = "qp_prover_prove_voters: the registry was built from commitments and holds no keys; a voter "
+                  "proves with their own key and the registry's path (qp_prover_prove_voting_inputs)";
+    return QP_ERR_STATE;
+  }
   try {
     constexpr uint32_t S = qpk::REG_PATH_SLOTS;
     std::vector<uint64_t> sib((size_t)nproofs * S * 4), leaf((size_t)nproofs * 4);

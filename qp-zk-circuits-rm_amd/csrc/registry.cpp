@@ -21,6 +21,68 @@ struct Events {
       if (x) (void)hipEventDestroy(x);
   }
 };
+
+// a felt >= p among leaves[k][4]; the voter named is first + its position
+int check_commitments(qp_ctx *c, const char *fn, const uint64_t *leaves, uint64_t k, uint64_t first) {
+  for (uint64_t i = 0; i < k; i++)
+    for (uint32_t f = 0; f < 4; f++)
+      if (leaves[4 * i + f] >= gl::P) {
+        c->err = std::string(fn) + ": commitment " + std::to_string(first + i) + " (position " + std::to_string(i) +
+                 " of the batch) felt " + std::to_string(f) + " is not a canonical field element";
+        return QP_ERR_ARG;
+      }
+  return QP_OK;
+}
+
+int not_for_keyed(const qp_registry *r, const char *fn) {
+  r->ctx->err = std::string(fn) + ": the registry was built from private keys (qp_registry_new) and keeps a host " +
+                "copy of them, which an update would leave stale; use qp_registry_new_commitments";
+  return QP_ERR_STATE;
+}
+
+// the first step of an update on the context's stream: the device, the timing events, the start mark
+int update_begin(qp_registry *r) {
+  qp_ctx *c = r->ctx;
+  QP_HIP_TRY(c, hipSetDevice(c->device));
+  for (hipEvent_t &e : r->ev)
+    if (!e) QP_HIP_TRY(c, hipEventCreate(&e));
+  QP_HIP_TRY(c, hipEventRecord(r->ev[0], c->stream));
+  return QP_OK;
+}
+
+// the last step: the launches' status, the new root, and only then the new size and table
+int update_end(qp_registry *r, const qpk::RegistryLevels &lv, bool count) {
+  qp_ctx *c = r->ctx;
+  hipStream_t s = c->stream;
+  uint64_t root[4];
+  QP_HIP_TRY(c, hipGetLastError());
+  QP_HIP_TRY(c, hipEventRecord(r->ev[2], s));
+  QP_HIP_TRY(c, hipMemcpyAsync(root, r->dig.p + lv.off[lv.nlevels - 1] * 4, 32, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(c, hipStreamSynchronize(s));
+  QP_HIP_TRY(c, hipEventElapsedTime(&r->build_ms[0], r->ev[0], r->ev[1]));
+  QP_HIP_TRY(c, hipEventElapsedTime(&r->build_ms[2], r->ev[1], r->ev[2]));
+  r->build_ms[1] = 0;
+  memcpy(r->root, root, 32);
+  r->lv = lv;
+  r->n = lv.len[0];
+  if (count) r->epoch++;
+  return QP_OK;
+}
+
+// voters [n, n + k) of a commitment registry (the caller checked the batch and the capacity)
+int append_checked(qp_registry *r, const uint64_t *leaves, uint64_t k, bool count) {
+  qp_ctx *c = r->ctx;
+  qpk::RegistryLevels lv;
+  if (!qpk::registry_levels_reserved(r->n + k, r->capacity, lv)) return QP_ERR_ARG;
+  int rc = update_begin(r);
+  if (rc) return rc;
+  hipStream_t s = c->stream;
+  // straight into level 0: slots at or beyond len[0] are scratch until the size moves
+  QP_HIP_TRY(c, hipMemcpyAsync(r->dig.p + (lv.off[0] + r->n) * 4, leaves, k * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(c, hipEventRecord(r->ev[1], s));
+  qpk::registry_append(r->dig.p, lv, r->n, s);
+  return update_end(r, lv, count);
+}
 }  // namespace
 
 int registry_paths_host(qp_registry *r, const uint64_t *idx, uint32_t nidx, uint64_t *siblings, uint32_t *path_bits,
@@ -57,6 +119,12 @@ int registry_paths_host(qp_registry *r, const uint64_t *idx, uint32_t nidx, uint
     done += nb;
   }
   return QP_OK;
+}
+
+// what has no meaning before the first voter registers
+static int empty_registry(const qp_registry *r, const char *fn) {
+  r->ctx->err = std::string(fn) + ": the registry is empty (no voter has registered yet)";
+  return QP_ERR_STATE;
 }
 
 extern "C" {
@@ -116,7 +184,139 @@ int qp_registry_new(qp_ctx *c, const uint64_t *keys, uint64_t n, qp_registry **o
   QP_HIP_TRY(c, hipMemcpyAsync(r->root, r->dig.p + lv.off[lv.nlevels - 1] * 4, 32, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(c, hipStreamSynchronize(s));
   for (int k = 0; k < 3; k++) QP_HIP_TRY(c, hipEventElapsedTime(&r->build_ms[k], ev.e[k], ev.e[k + 1]));
+  r->capacity = n;
   *out = r.release();
+  return QP_OK;
+}
+
+int qp_registry_new_commitments(qp_ctx *c, const uint64_t *leaves, uint64_t n, uint64_t capacity, qp_registry **out) {
+  if (!c || !out) return QP_ERR_ARG;
+  *out = nullptr;
+  if (n && !leaves) {
+    c->err = "qp_registry_new_commitments: null leaves";
+    return QP_ERR_ARG;
+  }
+  if (capacity > qpk::REG_MAX_VOTERS || capacity < std::max<uint64_t>(n, 1)) {
+    c->err = "qp_registry_new_commitments: capacity " + std::to_string(capacity) + " for " + std::to_string(n) +
+             " voters: it must hold them (and at least one) and be at most 2^31, the most voters a path of depth " +
+             std::to_string(qpk::REG_MAX_DEPTH) + " reaches";
+    return QP_ERR_ARG;
+  }
+  int rc = check_commitments(c, "qp_registry_new_commitments", leaves, n, 0);
+  if (rc) return rc;
+  std::unique_ptr<qp_registry> r(new (std::nothrow) qp_registry);
+  if (!r) return QP_ERR_OOM;
+  r->ctx = c;
+  r->keyed = false;
+  r->capacity = capacity;
+  qpk::registry_levels_reserved(0, capacity, r->lv);
+  QP_HIP_TRY(c, hipSetDevice(c->device));
+  QP_HIP_TRY(c, r->dig.alloc(qpk::registry_reserved(capacity) * 4));
+  if (n && (rc = append_checked(r.get(), leaves, n, false))) return rc;
+  *out = r.release();
+  return QP_OK;
+}
+
+int qp_registry_append(qp_registry *r, const uint64_t *leaves, uint64_t k, uint64_t *first) {
+  if (!r) return QP_ERR_ARG;
+  if (r->keyed) return not_for_keyed(r, "qp_registry_append");
+  if (first) *first = r->n;
+  if (!k) return QP_OK;
+  qp_ctx *c = r->ctx;
+  if (!leaves) {
+    c->err = "qp_registry_append: null leaves";
+    return QP_ERR_ARG;
+  }
+  if (k > r->capacity - r->n) {
+    c->err = "qp_registry_append: " + std::to_string(r->n) + " + " + std::to_string(k) + " voters exceed the capacity " +
+             std::to_string(r->capacity) + "; call qp_registry_reserve first";
+    return QP_ERR_ARG;
+  }
+  int rc = check_commitments(c, "qp_registry_append", leaves, k, r->n);
+  if (rc) return rc;
+  return append_checked(r, leaves, k, true);
+}
+
+int qp_registry_replace(qp_registry *r, const uint64_t *idx, const uint64_t *leaves, uint32_t k) {
+  if (!r) return QP_ERR_ARG;
+  if (r->keyed) return not_for_keyed(r, "qp_registry_replace");
+  if (!k) return QP_OK;
+  qp_ctx *c = r->ctx;
+  if (!idx || !leaves) {
+    c->err = "qp_registry_replace: null buffer";
+    return QP_ERR_ARG;
+  }
+  std::vector<uint32_t> order;
+  std::vector<uint64_t> sidx, sleaf;
+  try {
+    uint32_t bad = 0;
+    if (!qpk::registry_replace_order(idx, k, r->n, order, &bad)) {
+      c->err = "qp_registry_replace: voter index " + std::to_string(idx[bad]) + " (position " + std::to_string(bad) +
+               (idx[bad] >= r->n ? ") is outside the " + std::to_string(r->n) + " voters"
+                                 : ") appears twice in the batch");
+      return QP_ERR_ARG;
+    }
+    sidx.resize(k);
+    sleaf.resize((size_t)k * 4);
+  } catch (const std::bad_alloc &) {
+    c->err = "qp_registry_replace: host allocation failed";
+    return QP_ERR_OOM;
+  }
+  for (uint32_t b = 0; b < k; b++)
+    for (uint32_t f = 0; f < 4; f++)
+      if (leaves[4 * (size_t)b + f] >= gl::P) {
+        c->err = "qp_registry_replace: commitment " + std::to_string(idx[b]) + " (position " + std::to_string(b) +
+                 " of the batch) felt " + std::to_string(f) + " is not a canonical field element";
+        return QP_ERR_ARG;
+      }
+  for (uint32_t b = 0; b < k; b++) {
+    sidx[b] = idx[order[b]];
+    memcpy(&sleaf[(size_t)b * 4], leaves + (size_t)order[b] * 4, 32);
+  }
+  int rc = update_begin(r);
+  if (rc) return rc;
+  if (r->d_upd_idx.words < k) {
+    QP_HIP_TRY(c, r->d_upd_idx.alloc(k));
+    QP_HIP_TRY(c, r->d_upd_leaf.alloc((size_t)k * 4));
+  }
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(c, hipMemcpyAsync(r->d_upd_idx.p, sidx.data(), (size_t)k * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(c, hipMemcpyAsync(r->d_upd_leaf.p, sleaf.data(), (size_t)k * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(c, hipEventRecord(r->ev[1], s));
+  qpk::registry_replace(r->dig.p, r->lv, r->d_upd_idx.p, r->d_upd_leaf.p, k, s);
+  return update_end(r, r->lv, true);
+}
+
+int qp_registry_reserve(qp_registry *r, uint64_t new_capacity) {
+  if (!r) return QP_ERR_ARG;
+  if (r->keyed) return not_for_keyed(r, "qp_registry_reserve");
+  qp_ctx *c = r->ctx;
+  qpk::RegistryLevels lv;
+  if (!qpk::registry_levels_reserved(r->n, new_capacity, lv)) {
+    c->err = "qp_registry_reserve: capacity " + std::to_string(new_capacity) + " for " + std::to_string(r->n) +
+             " voters: it must hold them (and at least one) and be at most 2^31";
+    return QP_ERR_ARG;
+  }
+  if (new_capacity == r->capacity) return QP_OK;
+  QP_HIP_TRY(c, hipSetDevice(c->device));
+  DevBuf nd;
+  QP_HIP_TRY(c, nd.alloc(qpk::registry_reserved(new_capacity) * 4));
+  for (uint32_t l = 0; l < lv.nlevels; l++)
+    QP_HIP_TRY(c, hipMemcpyAsync(nd.p + lv.off[l] * 4, r->dig.p + r->lv.off[l] * 4, lv.len[l] * 32,
+                                 hipMemcpyDeviceToDevice, c->stream));
+  QP_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  std::swap(r->dig.p, nd.p);
+  std::swap(r->dig.words, nd.words);
+  r->lv = lv;
+  r->capacity = new_capacity;
+  r->epoch++;
+  return QP_OK;
+}
+
+int qp_registry_state(const qp_registry *r, uint64_t *capacity, uint64_t *epoch) {
+  if (!r) return QP_ERR_ARG;
+  if (capacity) *capacity = r->capacity;
+  if (epoch) *epoch = r->epoch;
   return QP_OK;
 }
 
@@ -128,6 +328,7 @@ void qp_registry_free(qp_registry *r) {
 
 int qp_registry_root(const qp_registry *r, uint64_t out[4]) {
   if (!r || !out) return QP_ERR_ARG;
+  if (!r->n) return empty_registry(r, "qp_registry_root");
   memcpy(out, r->root, 32);
   return QP_OK;
 }
@@ -142,6 +343,7 @@ int qp_registry_size(const qp_registry *r, uint64_t *n, uint32_t *max_depth) {
 int qp_registry_paths(qp_registry *r, const uint64_t *idx, uint32_t nidx, uint64_t *siblings, uint32_t *path_bits,
                       uint32_t *depth) {
   if (!r) return QP_ERR_ARG;
+  if (!r->n) return empty_registry(r, "qp_registry_paths");
   if (!nidx) return QP_OK;
   if (!idx || !siblings || !path_bits || !depth) {
     r->ctx->err = "qp_registry_paths: null buffer";
@@ -158,6 +360,7 @@ int qp_registry_build_times(const qp_registry *r, double ms[3]) {
 
 int qp_registry_level(qp_registry *r, uint32_t level, uint64_t *out, uint64_t *len) {
   if (!r) return QP_ERR_ARG;
+  if (!r->n) return empty_registry(r, "qp_registry_level");
   if (level >= r->lv.nlevels) {
     r->ctx->err = "qp_registry_level: the tree has " + std::to_string(r->lv.nlevels) + " levels";
     return QP_ERR_ARG;

@@ -8,6 +8,8 @@
 // permutation each (merkle_node.h), the state in registers.
 #include "registry_kernels.h"
 #include "merkle_node.h"
+#include "paths.h"
+#include "poseidon_coop.h"
 
 namespace qpk {
 
@@ -145,6 +147,81 @@ __global__ void __launch_bounds__(256) k_registry_paths(const uint64_t *__restri
   }
 }
 
+// ---- updates of a commitment registry (registry_kernels.h).  A node of level
+// l is remade from nodes 2j, 2j + 1 of level l - 1, which the previous launch
+// (or the upload, for the leaves) left final; a node whose right child lies
+// beyond the level's end is a promotion, a copy of the left child.
+
+// the row form of one node: the 16-lane row of lane l16 remakes node j of
+// `level`.  The permutation runs for a promoted node too (on the left child
+// alone) and is dropped at the store, so no lane leaves the DPP broadcasts.
+__device__ __forceinline__ void registry_node_row(uint64_t *__restrict__ dig, const RegistryLevels &lv, uint32_t level,
+                                                  uint64_t j, uint32_t l16) {
+  const uint64_t *c = dig + (lv.off[level - 1] + 2 * j) * 4;
+  const bool pair = 2 * j + 1 < lv.len[level - 1];
+  const uint64_t in = l16 < (pair ? 8u : 4u) ? c[l16] : 0;
+  const uint64_t x = pc::permute_row(in);
+  if (l16 < 4) dig[(lv.off[level] + j) * 4 + l16] = pair ? psd::canon(x) : in;
+}
+
+// append, narrow range: nodes [first, first + count) of `level`, one 16-lane
+// row per node, 16 nodes per block; rows past the range exit together
+__global__ void __launch_bounds__(256) k_registry_range_row(uint64_t *__restrict__ dig, RegistryLevels lv,
+                                                            uint32_t level, uint64_t first, uint32_t count) {
+  const uint32_t r = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (r >= count) return;
+  registry_node_row(dig, lv, level, first + r, threadIdx.x & 15);
+}
+
+// replace, level 0: leaf b of the batch into voter idx[b]'s slot (one lane per felt)
+__global__ void __launch_bounds__(256) k_registry_put(uint64_t *__restrict__ dig, const uint64_t *__restrict__ idx,
+                                                      const uint64_t *__restrict__ leaves, uint32_t k) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (uint64_t)k * 4) return;
+  dig[idx[g >> 2] * 4 + (g & 3)] = leaves[g];
+}
+
+// replace, one level: the dirty nodes are unique(idx >> level), idx ascending.
+// Of the batch entries with the same idx >> level the first owns the node and
+// the others leave at once, so every dirty node is written exactly once; its
+// children are final because the level below was a launch of its own.  One
+// lane per batch entry.
+__global__ void __launch_bounds__(256) k_registry_scatter(uint64_t *__restrict__ dig, RegistryLevels lv,
+                                                          uint32_t level, const uint64_t *__restrict__ idx,
+                                                          uint32_t k) {
+  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= k) return;
+  const uint64_t j = idx[b] >> level;
+  if (b && (idx[b - 1] >> level) == j) return;
+  const uint64_t *c = dig + (lv.off[level - 1] + 2 * j) * 4;
+  const bool pair = 2 * j + 1 < lv.len[level - 1];
+  uint64_t s[12];
+#pragma unroll
+  for (int i = 0; i < 4; i++) s[i] = c[i];
+#pragma unroll
+  for (int i = 4; i < 8; i++) s[i] = pair ? c[i] : 0;
+  node_digest(s);
+  if (!pair) {  // promoted: the left child again, unhashed
+#pragma unroll
+    for (int i = 0; i < 4; i++) s[i] = c[i];
+  }
+  uint64_t *o = dig + (lv.off[level] + j) * 4;
+#pragma unroll
+  for (int i = 0; i < 4; i++) o[i] = s[i];
+}
+
+// the same in the row form: one 16-lane row per batch entry; the rows that do
+// not own their node exit whole (the owner rule of k_registry_scatter)
+__global__ void __launch_bounds__(256) k_registry_scatter_row(uint64_t *__restrict__ dig, RegistryLevels lv,
+                                                              uint32_t level, const uint64_t *__restrict__ idx,
+                                                              uint32_t k) {
+  const uint32_t b = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (b >= k) return;
+  const uint64_t j = idx[b] >> level;
+  if (b && (idx[b - 1] >> level) == j) return;
+  registry_node_row(dig, lv, level, j, threadIdx.x & 15);
+}
+
 void registry_leaves(const uint64_t *keys, uint64_t n, uint64_t *dig, hipStream_t s) {
   k_registry_leaves<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(keys, n, dig);
 }
@@ -166,6 +243,57 @@ void registry_paths(const uint64_t *dig, const RegistryLevels &lv, const uint64_
   if (!nidx) return;
   k_registry_paths<<<(unsigned)(((uint64_t)nidx * REG_PATH_SLOTS + 255) / 256), 256, 0, s>>>(
       dig, lv, idx, nidx, siblings, path_bits, depth, leaves);
+}
+
+// path hook registry_row=N: the row form for dirty ranges below N nodes (read per call)
+static uint64_t registry_row_max() { return (uint64_t)path_opt("registry_row", REG_ROW_MAX); }
+
+// nodes [a, e) of level l (a even-aligned source: pairs from 2a) from level
+// l - 1; true when k_registry_fold finished the tree from level l - 1 up
+static bool registry_range(uint64_t *dig, const RegistryLevels &lv, uint32_t l, uint64_t a, uint64_t e,
+                           uint64_t row_max, hipStream_t s) {
+  const uint64_t count = e - a;
+  if (count < row_max) {
+    k_registry_range_row<<<(unsigned)((count + 15) / 16), 256, 0, s>>>(dig, lv, l, a, (uint32_t)count);
+    return false;
+  }
+  if (lv.len[l - 1] <= REG_FOLD_MAX) {
+    k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
+    return true;
+  }
+  const uint64_t *src = dig + (lv.off[l - 1] + 2 * a) * 4;
+  uint64_t *dst = dig + (lv.off[l] + a) * 4;
+  const uint64_t nsrc = lv.len[l - 1] - 2 * a;
+  if (nsrc == 1)  // the range is one promoted node: no pair for k_registry_level's lane 0
+    (void)hipMemcpyAsync(dst, src, 32, hipMemcpyDeviceToDevice, s);
+  else
+    k_registry_level<<<(unsigned)((nsrc / 2 + 255) / 256), 256, 0, s>>>(src, nsrc, dst);
+  return false;
+}
+
+void registry_append(uint64_t *dig, const RegistryLevels &lv, uint64_t n_old, hipStream_t s) {
+  const uint64_t row_max = registry_row_max();
+  for (uint32_t l = 1; l < lv.nlevels; l++)
+    if (registry_range(dig, lv, l, n_old >> l, lv.len[l], row_max, s)) return;
+}
+
+void registry_replace(uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, const uint64_t *leaves, uint32_t k,
+                      hipStream_t s) {
+  if (!k) return;
+  const uint64_t row_max = registry_row_max();
+  k_registry_put<<<(unsigned)(((uint64_t)k * 4 + 255) / 256), 256, 0, s>>>(dig, idx, leaves, k);
+  for (uint32_t l = 1; l < lv.nlevels; l++) {
+    if (k >= lv.len[l]) {  // no fewer entries than nodes: the whole level, as a range
+      if (registry_range(dig, lv, l, 0, lv.len[l], row_max, s)) return;
+    } else if (k < row_max) {
+      k_registry_scatter_row<<<(k + 15) / 16, 256, 0, s>>>(dig, lv, l, idx, k);
+    } else if (lv.len[l - 1] <= REG_FOLD_MAX) {
+      k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
+      return;
+    } else {
+      k_registry_scatter<<<(k + 255) / 256, 256, 0, s>>>(dig, lv, l, idx, k);
+    }
+  }
 }
 
 }  // namespace qpk

@@ -10,22 +10,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "registry_layout.h"
 
 namespace qpk {
 
-// the circuit has MAX_MERKLE_DEPTH = 32 sibling slots and a 5-bit depth split:
-// the deepest path a registry may hold is 31 (N <= 2^31)
-constexpr uint32_t REG_PATH_SLOTS = 32, REG_MAX_DEPTH = 31, REG_MAX_LEVELS = REG_MAX_DEPTH + 1;
-// from a level of at most this many nodes up, the rest of the tree is one launch
-constexpr uint32_t REG_FOLD_MAX = 64;
-
-// level offsets (in digests) and lengths, leaves first; the root is level nlevels - 1
-struct RegistryLevels {
-  uint32_t nlevels = 0;
-  uint64_t off[REG_MAX_LEVELS] = {0}, len[REG_MAX_LEVELS] = {0};
-  uint64_t total() const { return nlevels ? off[nlevels - 1] + len[nlevels - 1] : 0; }
-  uint32_t max_depth() const { return nlevels - 1; }
-};
 // the table for n voters; false (table untouched) for n = 0 or a path deeper than REG_MAX_DEPTH
 bool registry_levels(uint64_t n, RegistryLevels &lv);
 
@@ -47,5 +35,33 @@ void registry_tree(uint64_t *dig, const RegistryLevels &lv, hipStream_t s);
 // leaves (may be null) [nidx][4] = the voters' leaf digests
 void registry_paths(const uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, uint32_t nidx,
                     uint64_t *siblings, uint32_t *path_bits, uint32_t *depth, uint64_t *leaves, hipStream_t s);
+
+// ---- updates of a commitment registry (a reserved layout: off[] from the
+// capacity, len[] / nlevels from the current n; registry_layout.h).  Level 0
+// is already written when these run; each recomputes the nodes above it that
+// the update changes, level by level in launch order, every loop bound from
+// the host's table.
+// Dirty ranges narrower than this run in the row form (16 lanes per node,
+// pc::permute_row) at every level up to the root: measured against the
+// one-lane form it wins or ties at every range width up to this one, the
+// widest measured (DESIGN §12 has the A/B).  Wider ranges go through
+// k_registry_level on the level's suffix and, from a level of at most
+// REG_FOLD_MAX nodes, k_registry_fold.  Path hook registry_row=N overrides
+// the bound (0 = never the row form).
+constexpr long REG_ROW_MAX = 32768;
+
+__global__ void k_registry_range_row(uint64_t *dig, RegistryLevels lv, uint32_t level, uint64_t first, uint32_t count);
+__global__ void k_registry_put(uint64_t *dig, const uint64_t *idx, const uint64_t *leaves, uint32_t k);
+__global__ void k_registry_scatter(uint64_t *dig, RegistryLevels lv, uint32_t level, const uint64_t *idx, uint32_t k);
+__global__ void k_registry_scatter_row(uint64_t *dig, RegistryLevels lv, uint32_t level, const uint64_t *idx,
+                                       uint32_t k);
+
+// the levels above the leaves after voters [n_old, lv.len[0]) were written into
+// level 0 (lv: the table of the new size); n_old = 0 builds the whole tree
+void registry_append(uint64_t *dig, const RegistryLevels &lv, uint64_t n_old, hipStream_t s);
+// leaves[b][4] into level 0 at idx[b], then the levels above; idx (device):
+// k >= 1 voter indices < lv.len[0], ascending, no index twice (the caller checks)
+void registry_replace(uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, const uint64_t *leaves, uint32_t k,
+                      hipStream_t s);
 
 }  // namespace qpk

@@ -152,6 +152,11 @@ def lib():
         "qp_registry_paths": (ctypes.c_int, [VP, U64P, ctypes.c_uint32, U64P, U32P, U32P]),
         "qp_registry_level": (ctypes.c_int, [VP, ctypes.c_uint32, VP, ctypes.POINTER(ctypes.c_uint64)]),
         "qp_registry_build_times": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double)]),
+        "qp_registry_new_commitments": (ctypes.c_int, [VP, VP, ctypes.c_uint64, ctypes.c_uint64, PP]),
+        "qp_registry_append": (ctypes.c_int, [VP, VP, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_registry_replace": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint32]),
+        "qp_registry_reserve": (ctypes.c_int, [VP, ctypes.c_uint64]),
+        "qp_registry_state": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "qp_prover_prove_voters": (ctypes.c_int, [VP, VP, U64P, VP, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                                   ctypes.POINTER(ctypes.c_size_t)]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
