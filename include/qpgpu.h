@@ -477,6 +477,84 @@ typedef struct {
 int qp_prover_prove_voters(qp_prover *p, qp_registry *r, const uint64_t *idx, const qp_vote_ballot *ballots,
                            uint32_t nproofs, uint8_t *out, size_t stride, size_t *lens);
 
+/* ---- ballot box: count voting proofs once per nullifier ----------------------
+ * The counter's side of an election.  A verified voting proof says only that
+ * some registered voter voted `vote` on `proposal_id` under `merkle_root`, with
+ * this `nullifier` ("the nullifier to prevent double voting", voting/src/
+ * lib.rs:33-34); the reference has no object that uses it.  A box is opened for
+ * one proposal with the Merkle roots the operator published (1 to 64; a
+ * registry's root changes with every epoch) and a capacity of admitted
+ * ballots.  Every ballot cast gets a number: its position in the stream of all
+ * ballots cast into the box, rejected ones included, from 0.  The 13 public
+ * inputs are proposal[0:4] root[4:8] vote[8] nullifier[9:13] (lib.rs:55-62);
+ * a ballot's status is the first of these checks that fails, in this order:  */
+typedef enum {
+    QP_BALLOT_COUNTED = 0,        /* admitted and counted; first = its own number */
+    QP_BALLOT_PROOF_REJECTED = 1, /* the verifier's verdict is not QP_VERIFY_OK (it is in verify_status) */
+    QP_BALLOT_MALFORMED = 2,      /* a public input >= p (reachable only through qp_ballot_box_cast_public) */
+    QP_BALLOT_WRONG_PROPOSAL = 3, /* proposal differs from the box's */
+    QP_BALLOT_UNKNOWN_ROOT = 4,   /* root is not among the accepted roots */
+    QP_BALLOT_BAD_VOTE = 5,       /* vote is neither 0 nor 1 (a sound proof cannot carry that; screened anyway) */
+    QP_BALLOT_DOUBLE_VOTE = 6     /* an earlier ballot with the same nullifier was counted; first = its number */
+} qp_ballot_status;
+/* A ballot that passes the first five checks is admitted and takes one of the
+ * capacity's entries; the sixth decides between counted and double vote.  The
+ * lowest number wins: of the admitted ballots with one nullifier the counted
+ * one is the one with the lowest number, inside a batch and across batches.
+ * Statuses, `first` and the tally are a function of the ballot stream alone:
+ * not of how it is cut into batches, of the path (device or host) or of the
+ * device's scheduling.  Nothing is ever removed from a box.
+ *
+ * With a context the admitted ballots' log (nullifier, number, flags) and the
+ * nullifier table live on the device and the box uses the context's stream
+ * (free it before qp_ctx_destroy); ctx == NULL runs the same semantics on the
+ * host.  Every call is all or nothing: what it can refuse is checked before
+ * anything is enqueued, and a refused call leaves the cast and admitted
+ * counts, the tally and the log as they were (out[] is then unspecified).   */
+typedef struct qp_ballot_box qp_ballot_box;
+struct qp_verifier;
+typedef struct {
+    uint32_t status;         /* qp_ballot_status */
+    uint32_t verify_status;  /* qp_verify_status of the proof (cast_public: verdicts[i]) */
+    uint64_t number;         /* the ballot's number */
+    uint64_t first;          /* counted: number; double vote: the counted ballot's number; else number */
+} qp_ballot_result;
+/* proposal_id: 4 canonical felts; roots [nroots][4] canonical, 1 <= nroots <= 64 (a root given
+ * twice counts once); 1 <= capacity <= 2^31 admitted ballots.  Device memory: 41 bytes per
+ * entry of capacity and 4 per table slot (the power of two >= 2 capacity slots).           */
+int qp_ballot_box_new(qp_ctx *ctx /* NULL: host */, const uint64_t proposal_id[4], const uint64_t *roots,
+                      uint32_t nroots, uint64_t capacity, qp_ballot_box **out);
+void qp_ballot_box_free(qp_ballot_box *b);
+/* the reason of the box's last refused call; b == NULL: of this thread's last refused qp_ballot_box_new */
+const char *qp_ballot_box_last_error(const qp_ballot_box *b);
+/* one more accepted root (a new epoch's); a root the box already accepts: QP_OK, held once; a 65th: QP_ERR_ARG */
+int qp_ballot_box_accept_root(qp_ballot_box *b, const uint64_t root[4]);
+/* verifies proofs[0..n) with v, a verifier of the voting circuit's data (13 public inputs, else
+ * QP_ERR_ARG), then casts them: out[n].  More admitted ballots than the capacity has room for:
+ * QP_ERR_ARG (call qp_ballot_box_reserve); n == 0: QP_OK                                   */
+int qp_ballot_box_cast(qp_ballot_box *b, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens,
+                       uint32_t n, qp_ballot_result *out);
+/* the routine-level seam: public inputs pis[n][13] of proofs verified elsewhere (verdicts[i] != 0
+ * marks a rejected one; NULL = all verified); also the small-shape test surface of the kernels */
+int qp_ballot_box_cast_public(qp_ballot_box *b, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                              qp_ballot_result *out);
+/* moves the box to a log and table for new_capacity >= admitted (and >= 1, <= 2^31); statuses
+ * already handed out stay true                                                             */
+int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity);
+/* counted yes and no votes (either may be NULL) */
+int qp_ballot_box_tally(const qp_ballot_box *b, uint64_t *yes, uint64_t *no);
+/* ballots cast, admitted, capacity (each may be NULL) */
+int qp_ballot_box_state(const qp_ballot_box *b, uint64_t *cast, uint64_t *admitted, uint64_t *capacity);
+/* the log, for publication and audit: entries [first, first + k) in admission order: nullifiers
+ * [k][4], numbers [k], flags [k] (bit 0 the vote, bit 1 counted); each may be NULL          */
+int qp_ballot_box_entries(qp_ballot_box *b, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
+                          uint8_t *flags);
+/* the audit: yes, no, counted, admitted recomputed from the log's flags alone */
+int qp_ballot_box_recount(qp_ballot_box *b, uint64_t out[4]);
+/* HIP-event times of the last device cast that admitted a ballot (ms): [0] the log upload, [1]
+ * insert + resolve.  Diagnostic entry point (tools/ballot_bench.py); 0 on the host path.    */
+int qp_ballot_box_cast_times(const qp_ballot_box *b, double ms[2]);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

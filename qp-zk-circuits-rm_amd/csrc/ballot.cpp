@@ -1,0 +1,403 @@
+// ballot.cpp — the qp_ballot_box_* entry points (qpgpu.h): voting proofs
+// verified through the batch verifier, their public inputs screened on the
+// host (ballot_table.h), each nullifier admitted once.  With a context the
+// nullifier set and the tally live on the device (ballot.hip); without one the
+// same semantics run on the host (qb::HostBox).
+#include "../../include/qpgpu.h"
+#include <string.h>
+#include <memory>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+#include "ballot_kernels.h"
+#include "ballot_table.h"
+#include "ctx.h"
+#include "verifier.h"
+
+static_assert(sizeof(qp_ballot_result) == sizeof(qb::Result) && sizeof(qb::Result) == 24, "qp_ballot_result layout");
+static_assert(QP_BALLOT_COUNTED == qb::COUNTED && QP_BALLOT_PROOF_REJECTED == qb::PROOF_REJECTED &&
+                  QP_BALLOT_MALFORMED == qb::MALFORMED && QP_BALLOT_WRONG_PROPOSAL == qb::WRONG_PROPOSAL &&
+                  QP_BALLOT_UNKNOWN_ROOT == qb::UNKNOWN_ROOT && QP_BALLOT_BAD_VOTE == qb::BAD_VOTE &&
+                  QP_BALLOT_DOUBLE_VOTE == qb::DOUBLE_VOTE,
+              "qp_ballot_status and ballot_table.h differ");
+
+namespace {
+// the device half of a box for one capacity: the log, the table
+struct DeviceTables {
+  DevBuf nul, num, flags, slot;
+  uint64_t mask = 0;
+  qpk::BallotDev dev() const {
+    return qpk::BallotDev{nul.p, num.p, flags.as<uint8_t>(), slot.as<uint32_t>(), mask};
+  }
+};
+}  // namespace
+
+struct qp_ballot_box {
+  qp_ctx *ctx = nullptr;  // null: the host path
+  std::string err;
+  bool dead = false;  // a device step failed part-way, or the defensive error word was set: no further casts
+  qb::Screen screen;
+  uint64_t cast = 0;
+  qb::Packed pk;  // the batch in flight
+  qb::HostBox host;
+  // ---- device path
+  uint64_t capacity = 0, count = 0, yes = 0, no = 0;  // yes / no: the device counters as of the last cast
+  DeviceTables t;
+  DevBuf d_stay, d_first, d_ctr, d_audit;  // per batch: slot stayed at [k] (u32), first [k]; counters; recount's four
+  std::vector<uint64_t> h_first;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // upload start, upload end, resolve end of the last cast
+  float ms[2] = {0, 0};
+  ~qp_ballot_box() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  uint64_t admitted() const { return ctx ? count : host.count(); }
+  uint64_t cap() const { return ctx ? capacity : host.capacity; }
+};
+
+namespace {
+thread_local std::string g_new_err;  // why the last qp_ballot_box_new on this thread was refused
+
+int refuse_new(qp_ctx *c, const std::string &why) {
+  g_new_err = "qp_ballot_box_new: " + why;
+  if (c) c->err = g_new_err;
+  return QP_ERR_ARG;
+}
+
+int alloc_tables(qp_ballot_box *b, uint64_t capacity, DeviceTables &t) {
+  const uint64_t S = qb::table_slots(capacity);
+  QP_HIP_TRY(b, t.nul.alloc(capacity * 4));
+  QP_HIP_TRY(b, t.num.alloc(capacity));
+  QP_HIP_TRY(b, t.flags.alloc((capacity + 7) / 8));
+  QP_HIP_TRY(b, t.slot.alloc(S / 2));
+  t.mask = S - 1;
+  QP_HIP_TRY(b, hipMemsetAsync(t.slot.p, 0xFF, S * 4, b->ctx->stream));
+  return QP_OK;
+}
+
+int dead_box(qp_ballot_box *b, const char *fn) {
+  b->err = std::string(fn) + ": an earlier call on this box failed on the device part-way; its state is not known";
+  return QP_ERR_STATE;
+}
+
+// the device steps of one batch: the packed ballots into log [count, count + k), insert, resolve
+int cast_device(qp_ballot_box *b, qb::Result *out) {
+  qp_ctx *c = b->ctx;
+  const qb::Packed &pk = b->pk;
+  const uint32_t k = (uint32_t)pk.size();
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  for (hipEvent_t &e : b->ev)
+    if (!e) QP_HIP_TRY(b, hipEventCreate(&e));
+  if (b->d_first.words < k) {
+    QP_HIP_TRY(b, b->d_stay.alloc(((size_t)k + 1) / 2));
+    QP_HIP_TRY(b, b->d_first.alloc(k));
+  }
+  b->h_first.resize(k);
+  const qpk::BallotDev d = b->t.dev();
+  qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
+  qpk::BallotCounters now;
+  QP_HIP_TRY(b, hipEventRecord(b->ev[0], s));
+  QP_HIP_TRY(b, hipMemcpyAsync(d.nullifier + b->count * 4, pk.nullifier.data(), (size_t)k * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(b, hipMemcpyAsync(d.number + b->count, pk.number.data(), (size_t)k * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(b, hipMemcpyAsync(d.flags + b->count, pk.flags.data(), k, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(b, hipEventRecord(b->ev[1], s));
+  qpk::ballot_insert(d, (uint32_t)b->count, k, b->d_stay.as<uint32_t>(), ctr, s);
+  QP_HIP_TRY(b, hipGetLastError());
+  qpk::ballot_resolve(d, (uint32_t)b->count, k, b->d_stay.as<uint32_t>(), b->d_first.p, ctr, s);
+  QP_HIP_TRY(b, hipGetLastError());
+  QP_HIP_TRY(b, hipEventRecord(b->ev[2], s));
+  QP_HIP_TRY(b, hipMemcpyAsync(b->h_first.data(), b->d_first.p, (size_t)k * 8, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipStreamSynchronize(s));
+  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[0], b->ev[0], b->ev[1]));
+  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[1], b->ev[1], b->ev[2]));
+  if (now.err) {
+    b->err = "qp_ballot_box_cast: the nullifier table's probe found no slot (an internal invariant broke)";
+    return QP_ERR_STATE;
+  }
+  for (uint32_t j = 0; j < k; j++) {
+    qb::Result &r = out[pk.pos[j]];
+    r.first = b->h_first[j];
+    if (r.first != r.number) r.status = qb::DOUBLE_VOTE;
+  }
+  b->count += k;
+  b->yes = now.yes;
+  b->no = now.no;
+  return QP_OK;
+}
+
+// pis [n][13], verdicts (may be null): screen, pack, refuse an overflow, count
+int cast_screened(qp_ballot_box *b, const char *fn, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                  qb::Result *out) {
+  qb::screen_and_pack(b->screen, pis, verdicts, n, b->cast, out, b->pk);
+  const uint64_t k = b->pk.size();
+  if (k > b->cap() - b->admitted()) {
+    b->err = std::string(fn) + ": " + std::to_string(b->admitted()) + " + " + std::to_string(k) +
+             " admitted ballots exceed the capacity " + std::to_string(b->cap()) + "; call qp_ballot_box_reserve first";
+    return QP_ERR_ARG;
+  }
+  if (!b->ctx) {
+    b->host.admit_packed(b->pk, out);
+  } else if (k) {
+    const int rc = cast_device(b, out);
+    if (rc) {
+      b->dead = true;
+      return rc;
+    }
+  }
+  b->cast += n;
+  return QP_OK;
+}
+
+int bad_alloc(qp_ballot_box *b, const char *fn) {
+  b->err = std::string(fn) + ": out of host memory";
+  return QP_ERR_OOM;
+}
+}  // namespace
+
+extern "C" {
+
+int qp_ballot_box_new(qp_ctx *c, const uint64_t proposal_id[4], const uint64_t *roots, uint32_t nroots,
+                      uint64_t capacity, qp_ballot_box **out) {
+  if (!out) return QP_ERR_ARG;
+  *out = nullptr;
+  if (!proposal_id || !roots) return refuse_new(c, "null proposal_id or roots");
+  if (!qb::canonical(proposal_id, 4)) return refuse_new(c, "proposal_id is not four canonical field elements");
+  if (!nroots || nroots > qb::MAX_ROOTS)
+    return refuse_new(c, std::to_string(nroots) + " accepted roots: a box needs 1 to " + std::to_string(qb::MAX_ROOTS));
+  if (!qb::canonical(roots, nroots * 4)) return refuse_new(c, "a root is not four canonical field elements");
+  if (!capacity || capacity > qb::MAX_CAPACITY)
+    return refuse_new(c, "capacity " + std::to_string(capacity) + ": it must be 1 to 2^31 admitted ballots");
+  std::unique_ptr<qp_ballot_box> b(new (std::nothrow) qp_ballot_box);
+  if (!b) return QP_ERR_OOM;
+  b->ctx = c;
+  memcpy(b->screen.proposal, proposal_id, 32);
+  try {
+    for (uint32_t i = 0; i < nroots; i++)
+      if (!b->screen.has_root(roots + 4 * i)) b->screen.roots.insert(b->screen.roots.end(), roots + 4 * i, roots + 4 * i + 4);
+    if (!c) {
+      b->host.open(capacity);
+      *out = b.release();
+      return QP_OK;
+    }
+  } catch (const std::bad_alloc &) {
+    g_new_err = "qp_ballot_box_new: out of host memory";
+    return QP_ERR_OOM;
+  }
+  int rc = QP_OK;
+  auto device_open = [&]() -> int {
+    QP_HIP_TRY(b, hipSetDevice(c->device));
+    if ((rc = alloc_tables(b.get(), capacity, b->t))) return rc;
+    QP_HIP_TRY(b, b->d_ctr.alloc((sizeof(qpk::BallotCounters) + 7) / 8));
+    QP_HIP_TRY(b, b->d_audit.alloc(4));
+    QP_HIP_TRY(b, hipMemsetAsync(b->d_ctr.p, 0, sizeof(qpk::BallotCounters), c->stream));
+    QP_HIP_TRY(b, hipStreamSynchronize(c->stream));
+    return QP_OK;
+  };
+  if ((rc = device_open())) {
+    g_new_err = c->err = "qp_ballot_box_new: " + b->err;
+    return rc;
+  }
+  b->capacity = capacity;
+  *out = b.release();
+  return QP_OK;
+}
+
+void qp_ballot_box_free(qp_ballot_box *b) {
+  if (!b) return;
+  if (b->ctx) (void)hipSetDevice(b->ctx->device);
+  delete b;
+}
+
+const char *qp_ballot_box_last_error(const qp_ballot_box *b) { return b ? b->err.c_str() : g_new_err.c_str(); }
+
+int qp_ballot_box_accept_root(qp_ballot_box *b, const uint64_t root[4]) {
+  if (!b) return QP_ERR_ARG;
+  if (!root || !qb::canonical(root, 4)) {
+    b->err = "qp_ballot_box_accept_root: the root must be four canonical field elements";
+    return QP_ERR_ARG;
+  }
+  if (b->screen.has_root(root)) return QP_OK;
+  if (b->screen.roots.size() / 4 >= qb::MAX_ROOTS) {
+    b->err = "qp_ballot_box_accept_root: the box already accepts " + std::to_string(qb::MAX_ROOTS) + " roots, the most";
+    return QP_ERR_ARG;
+  }
+  try {
+    b->screen.roots.insert(b->screen.roots.end(), root, root + 4);
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_accept_root");
+  }
+  return QP_OK;
+}
+
+int qp_ballot_box_cast_public(qp_ballot_box *b, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                              qp_ballot_result *out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_cast_public");
+  if (!n) return QP_OK;
+  if (!pis || !out) {
+    b->err = "qp_ballot_box_cast_public: null buffer";
+    return QP_ERR_ARG;
+  }
+  try {
+    return cast_screened(b, "qp_ballot_box_cast_public", pis, verdicts, n, reinterpret_cast<qb::Result *>(out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_cast_public");
+  }
+}
+
+int qp_ballot_box_cast(qp_ballot_box *b, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens,
+                       uint32_t n, qp_ballot_result *out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_cast");
+  const uint32_t npi = qv::public_input_count(v);
+  if (npi != qb::NPI) {
+    b->err = !v ? "qp_ballot_box_cast: null verifier"
+                : !npi ? "qp_ballot_box_cast: the verifier is not usable"
+                       : "qp_ballot_box_cast: the verifier's circuit has " + std::to_string(npi) +
+                             " public inputs; a voting circuit's has " + std::to_string(qb::NPI);
+    return QP_ERR_ARG;
+  }
+  if (!n) return QP_OK;
+  if (!proofs || !lens || !out) {
+    b->err = "qp_ballot_box_cast: null buffer";
+    return QP_ERR_ARG;
+  }
+  try {
+    std::vector<uint32_t> verdicts(n);
+    const int rc = qp_verifier_verify(v, proofs, lens, n, verdicts.data());
+    if (rc) {
+      b->err = std::string("qp_ballot_box_cast: qp_verifier_verify: ") + qp_verifier_last_error(v);
+      return rc;
+    }
+    std::vector<uint64_t> pis((size_t)n * qb::NPI, 0);
+    for (uint32_t i = 0; i < n; i++)
+      if (verdicts[i] == QP_VERIFY_OK) memcpy(&pis[(size_t)i * qb::NPI], qv::public_inputs(v, proofs[i]), qb::NPI * 8);
+    return cast_screened(b, "qp_ballot_box_cast", pis.data(), verdicts.data(), n, reinterpret_cast<qb::Result *>(out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_cast");
+  }
+}
+
+int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_reserve");
+  if (new_capacity > qb::MAX_CAPACITY || new_capacity < b->admitted() || !new_capacity) {
+    b->err = "qp_ballot_box_reserve: capacity " + std::to_string(new_capacity) + " for " + std::to_string(b->admitted()) +
+             " admitted ballots: it must hold them (and at least one) and be at most 2^31";
+    return QP_ERR_ARG;
+  }
+  if (new_capacity == b->cap()) return QP_OK;
+  if (!b->ctx) {
+    try {
+      b->host.reserve(new_capacity);
+    } catch (const std::bad_alloc &) {
+      return bad_alloc(b, "qp_ballot_box_reserve");
+    }
+    return QP_OK;
+  }
+  // a new log and table beside the old; the box moves over only once all of it succeeded
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  DeviceTables nt;
+  qpk::BallotCounters now;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  const int rc = alloc_tables(b, new_capacity, nt);
+  if (rc) return rc;
+  const qpk::BallotDev od = b->t.dev(), nd = nt.dev();
+  qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
+  if (b->count) {
+    QP_HIP_TRY(b, hipMemcpyAsync(nd.nullifier, od.nullifier, b->count * 32, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(b, hipMemcpyAsync(nd.number, od.number, b->count * 8, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(b, hipMemcpyAsync(nd.flags, od.flags, b->count, hipMemcpyDeviceToDevice, s));
+    qpk::ballot_rebuild(nd, (uint32_t)b->count, ctr, s);
+    QP_HIP_TRY(b, hipGetLastError());
+  }
+  QP_HIP_TRY(b, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipStreamSynchronize(s));
+  if (now.err) {
+    b->dead = true;
+    b->err = "qp_ballot_box_reserve: the nullifier table's probe found no slot (an internal invariant broke)";
+    return QP_ERR_STATE;
+  }
+  std::swap(b->t.nul.p, nt.nul.p);
+  std::swap(b->t.nul.words, nt.nul.words);
+  std::swap(b->t.num.p, nt.num.p);
+  std::swap(b->t.num.words, nt.num.words);
+  std::swap(b->t.flags.p, nt.flags.p);
+  std::swap(b->t.flags.words, nt.flags.words);
+  std::swap(b->t.slot.p, nt.slot.p);
+  std::swap(b->t.slot.words, nt.slot.words);
+  b->t.mask = nt.mask;
+  b->capacity = new_capacity;
+  return QP_OK;
+}
+
+int qp_ballot_box_tally(const qp_ballot_box *b, uint64_t *yes, uint64_t *no) {
+  if (!b) return QP_ERR_ARG;
+  if (yes) *yes = b->ctx ? b->yes : b->host.yes;
+  if (no) *no = b->ctx ? b->no : b->host.no;
+  return QP_OK;
+}
+
+int qp_ballot_box_state(const qp_ballot_box *b, uint64_t *cast, uint64_t *admitted, uint64_t *capacity) {
+  if (!b) return QP_ERR_ARG;
+  if (cast) *cast = b->cast;
+  if (admitted) *admitted = b->admitted();
+  if (capacity) *capacity = b->cap();
+  return QP_OK;
+}
+
+int qp_ballot_box_entries(qp_ballot_box *b, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
+                          uint8_t *flags) {
+  if (!b) return QP_ERR_ARG;
+  if (first > b->admitted() || k > b->admitted() - first) {
+    b->err = "qp_ballot_box_entries: entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
+             std::to_string(k) + ") are outside the log's " + std::to_string(b->admitted());
+    return QP_ERR_ARG;
+  }
+  if (!k) return QP_OK;
+  if (!b->ctx) {
+    if (nullifiers) memcpy(nullifiers, &b->host.nullifier[first * 4], k * 32);
+    if (numbers) memcpy(numbers, &b->host.number[first], k * 8);
+    if (flags) memcpy(flags, &b->host.flags[first], k);
+    return QP_OK;
+  }
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  const qpk::BallotDev d = b->t.dev();
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  if (nullifiers) QP_HIP_TRY(b, hipMemcpyAsync(nullifiers, d.nullifier + first * 4, k * 32, hipMemcpyDeviceToHost, s));
+  if (numbers) QP_HIP_TRY(b, hipMemcpyAsync(numbers, d.number + first, k * 8, hipMemcpyDeviceToHost, s));
+  if (flags) QP_HIP_TRY(b, hipMemcpyAsync(flags, d.flags + first, k, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_ballot_box_recount(qp_ballot_box *b, uint64_t out[4]) {
+  if (!b || !out) return QP_ERR_ARG;
+  if (!b->ctx) {
+    b->host.recount(out);
+    return QP_OK;
+  }
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  QP_HIP_TRY(b, hipMemsetAsync(b->d_audit.p, 0, 32, s));
+  qpk::ballot_recount(b->t.flags.as<uint8_t>(), (uint32_t)b->count, b->d_audit.as<unsigned long long>(), s);
+  QP_HIP_TRY(b, hipGetLastError());
+  QP_HIP_TRY(b, hipMemcpyAsync(out, b->d_audit.p, 32, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_ballot_box_cast_times(const qp_ballot_box *b, double ms[2]) {
+  if (!b || !ms) return QP_ERR_ARG;
+  ms[0] = b->ms[0];
+  ms[1] = b->ms[1];
+  return QP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,54 @@
+// ballot_kernels.h — argument layouts and launchers of ballot.hip: the ballot
+// box's nullifier table and tally on the device.  One launcher per step; the
+// launcher owns the grid and block sizes.
+//
+// The log (dense, indexed by admission sequence seq, written by the host's
+// upload before any launch that reads it):
+//   nullifier[C][4]   number[C]   flags[C] (bit 0 the vote, bit 1 counted)
+// The table: S = the power of two >= 2 C slots of uint32_t, a seq or
+// 0xFFFFFFFF (empty); open addressing, linear probing, wrapping.
+//   HOME SLOT = nullifier[0] & (S - 1)
+// (ballot_table.h states the same rule for the host path; the tests craft
+// colliding nullifiers from it.)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace qpk {
+
+struct BallotDev {
+  uint64_t *nullifier;  // [C][4]
+  uint64_t *number;     // [C]
+  uint8_t *flags;       // [C]
+  uint32_t *slot;       // [mask + 1]
+  uint64_t mask;        // S - 1
+};
+
+// the box's device counters: the running tally and the defensive error word
+struct BallotCounters {
+  unsigned long long yes, no;
+  uint32_t err, pad;
+};
+
+__global__ void k_ballot_insert(BallotDev d, uint32_t first_seq, uint32_t k, uint32_t *stay, uint32_t *err);
+__global__ void k_ballot_resolve(BallotDev d, uint32_t first_seq, uint32_t k, const uint32_t *stay, uint64_t *first_out,
+                                 BallotCounters *ctr);
+__global__ void k_ballot_rebuild(BallotDev d, uint32_t count, uint32_t *err);
+__global__ void k_ballot_recount(const uint8_t *flags, uint32_t count, unsigned long long *out);
+
+// log entries [first_seq, first_seq + k) (already uploaded) into the table;
+// stay[i] = the slot entry first_seq + i stopped at.  The caller keeps
+// first_seq + k <= C.
+void ballot_insert(const BallotDev &d, uint32_t first_seq, uint32_t k, uint32_t *stay, BallotCounters *ctr,
+                   hipStream_t s);
+// after ballot_insert, a launch of its own: first_out[i] = the number of the
+// entry that owns stay[i]'s slot (entry i's own: counted, its flag set and its
+// vote added to ctr)
+void ballot_resolve(const BallotDev &d, uint32_t first_seq, uint32_t k, const uint32_t *stay, uint64_t *first_out,
+                    BallotCounters *ctr, hipStream_t s);
+// the counted entries of log [0, count) into a fresh (all-empty) table
+void ballot_rebuild(const BallotDev &d, uint32_t count, BallotCounters *ctr, hipStream_t s);
+// out[4] (zeroed by the caller) += yes, no, counted, admitted of flags [0, count)
+void ballot_recount(const uint8_t *flags, uint32_t count, unsigned long long *out, hipStream_t s);
+
+}  // namespace qpk

@@ -147,6 +147,11 @@ struct qp_verifier {
   std::vector<uint32_t> early;  // per proof of the chunk: status of the host checks
 };
 
+namespace qv {
+uint32_t public_input_count(const qp_verifier *v) { return v && v->usable ? v->c.num_public_inputs : 0; }
+const uint8_t *public_inputs(const qp_verifier *v, const uint8_t *proof) { return proof + v->d.fixed_len; }
+}  // namespace qv
+
 namespace {
 
 std::string check_supported(const InnerCommon &c, Dims &d) {

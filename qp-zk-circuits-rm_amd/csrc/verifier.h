@@ -6,7 +6,17 @@
 #include <hip/hip_runtime.h>
 #include "verifier_rounds.h"
 
+struct qp_verifier;
+
 namespace qv {
+
+// what the ballot box (ballot.cpp) reads of a verifier: the circuit's public-input
+// count (0: the handle is not usable) and its last error
+uint32_t public_input_count(const qp_verifier *v);
+// the public inputs [public_input_count] inside a proof's bytes: valid for a
+// proof on which this verifier's verdict was QP_VERIFY_OK (its length and
+// every felt were checked then); 8-byte little-endian words, not aligned
+const uint8_t *public_inputs(const qp_verifier *v, const uint8_t *proof);
 
 // one lane per (proof, query, tree): leaf digest, climb, cap comparison.
 // The job's pointers are device pointers.

@@ -159,6 +159,20 @@ def lib():
         "qp_registry_state": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
         "qp_prover_prove_voters": (ctypes.c_int, [VP, VP, U64P, VP, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                                   ctypes.POINTER(ctypes.c_size_t)]),
+        "qp_ballot_box_new": (ctypes.c_int, [VP, U64P, U64P, ctypes.c_uint32, ctypes.c_uint64, PP]),
+        "qp_ballot_box_free": (None, [VP]),
+        "qp_ballot_box_last_error": (ctypes.c_char_p, [VP]),
+        "qp_ballot_box_accept_root": (ctypes.c_int, [VP, U64P]),
+        "qp_ballot_box_cast": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t),
+                                              ctypes.c_uint32, VP]),
+        "qp_ballot_box_cast_public": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint32, VP]),
+        "qp_ballot_box_reserve": (ctypes.c_int, [VP, ctypes.c_uint64]),
+        "qp_ballot_box_tally": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_state": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                               ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_entries": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP]),
+        "qp_ballot_box_recount": (ctypes.c_int, [VP, U64P]),
+        "qp_ballot_box_cast_times": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double)]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

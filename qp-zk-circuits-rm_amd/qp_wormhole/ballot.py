@@ -1,0 +1,213 @@
+"""BallotBox: the counter's side of an election (include/qpgpu.h qp_ballot_box_*).
+
+A verified voting proof says only that some registered voter voted `vote` on
+`proposal_id` under `merkle_root`, with this `nullifier`.  A box is opened for
+one proposal with the roots the operator published; it verifies batches of
+voting proofs through a WormholeVerifier of the voting circuit's data, screens
+their 13 public inputs (proposal[0:4] root[4:8] vote[8] nullifier[9:13]) and
+counts each nullifier once.  Every ballot cast gets a number, its position in
+the stream of all ballots cast into the box, and a status, the first check it
+fails (BALLOT_STATUS_TEXT, in the checks' order after "counted").  Of the
+ballots with one nullifier the one with the lowest number is counted; the
+others are double votes whose `first` names it.  Statuses and the tally depend
+on the ballot stream alone, not on how it is cut into batches.
+
+With a Context (or a device number) the nullifier set, the log of admitted
+ballots and the tally live on the device (csrc/ballot.hip); with None the same
+semantics run on the host.
+"""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+
+from ._native import Context, QpError, lib
+
+P = 0xFFFFFFFF00000001
+NPI = 13
+MAX_ROOTS = 64
+MAX_CAPACITY = 1 << 31
+DEFAULT_CAPACITY = 1024
+
+# qp_ballot_status
+COUNTED, PROOF_REJECTED, MALFORMED, WRONG_PROPOSAL, UNKNOWN_ROOT, BAD_VOTE, DOUBLE_VOTE = range(7)
+BALLOT_STATUS_TEXT = ("counted", "proof rejected", "malformed public inputs", "wrong proposal", "unknown root",
+                      "bad vote", "double vote")
+FLAG_VOTE, FLAG_COUNTED = 1, 2
+
+BallotResult = namedtuple("BallotResult", "status verify_status number first")
+# qp_ballot_result
+RESULT_DTYPE = np.dtype([("status", np.uint32), ("verify_status", np.uint32), ("number", np.uint64),
+                         ("first", np.uint64)])
+
+
+def _digest(v, what):
+    d = [int(x) for x in v]
+    if len(d) != 4 or any(not 0 <= x < P for x in d):
+        raise ValueError(f"{what} must be 4 canonical field elements")
+    return np.array(d, dtype=np.uint64)
+
+
+class BallotBox:
+    def __init__(self, ctx_or_device, proposal_id, roots, verifier=None, capacity=None):
+        """proposal_id: 4 canonical felts.  roots: the accepted Merkle roots, 1 to 64
+        digests (a registry's `root` of every epoch ballots may refer to).  verifier:
+        a WormholeVerifier of the voting circuit's data, needed by `cast` only.
+        capacity: admitted ballots the box has room for (default 1024; `cast` grows
+        it).  ctx_or_device: a Context, a device number (an own Context), or None
+        for the host path."""
+        prop = _digest(proposal_id, "proposal_id")
+        roots = list(roots)
+        if not 1 <= len(roots) <= MAX_ROOTS:
+            raise ValueError(f"{len(roots)} accepted roots: a ballot box needs 1 to {MAX_ROOTS}")
+        r = np.concatenate([_digest(x, "a root") for x in roots])
+        capacity = DEFAULT_CAPACITY if capacity is None else int(capacity)
+        if not 1 <= capacity <= MAX_CAPACITY:
+            raise ValueError(f"capacity {capacity}: it must be 1 to 2^31 admitted ballots")
+        self.verifier = verifier
+        self.h = self._own_ctx = None
+        if ctx_or_device is None or isinstance(ctx_or_device, Context):
+            self.ctx = ctx_or_device
+        else:
+            self.ctx = self._own_ctx = Context(int(ctx_or_device))
+        h = ctypes.c_void_p()
+        rc = lib().qp_ballot_box_new(None if self.ctx is None else self.ctx.h, prop, r, len(roots), capacity,
+                                     ctypes.byref(h))
+        if rc:
+            raise QpError(rc, lib().qp_ballot_box_last_error(None).decode())
+        self.h = h
+
+    def _check(self, rc):
+        if rc:
+            raise QpError(rc, lib().qp_ballot_box_last_error(self.h).decode())
+
+    # ---- state
+    def _state(self):
+        c, a, cap = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib().qp_ballot_box_state(self.h, ctypes.byref(c), ctypes.byref(a), ctypes.byref(cap)))
+        return c.value, a.value, cap.value
+
+    @property
+    def cast_count(self):
+        """ballots cast so far, rejected ones included: the next ballot's number"""
+        return self._state()[0]
+
+    @property
+    def admitted(self):
+        """ballots that passed the screen: counted ones and double votes (the log's length)"""
+        return self._state()[1]
+
+    @property
+    def capacity(self):
+        return self._state()[2]
+
+    @property
+    def tally(self):
+        """(yes, no) of the counted ballots"""
+        y, n = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib().qp_ballot_box_tally(self.h, ctypes.byref(y), ctypes.byref(n)))
+        return y.value, n.value
+
+    def accept_root(self, root):
+        """One more accepted root (a new epoch's); a root already accepted is held once."""
+        self._check(lib().qp_ballot_box_accept_root(self.h, _digest(root, "a root")))
+
+    def reserve(self, capacity):
+        """Moves the box to a log and table for `capacity` >= admitted ballots."""
+        self._check(lib().qp_ballot_box_reserve(self.h, int(capacity)))
+
+    def _make_room(self, n):
+        """room for n more admitted ballots: double the capacity, or what the batch needs"""
+        _, adm, cap = self._state()
+        if adm + n > cap:
+            if adm + n > MAX_CAPACITY:
+                raise ValueError(f"{adm} + {n} ballots are more than 2^31, the most a box holds")
+            self.reserve(min(max(2 * cap, adm + n), MAX_CAPACITY))
+
+    @staticmethod
+    def _results(out, raw):
+        if raw:
+            return out
+        return [BallotResult(int(r["status"]), int(r["verify_status"]), int(r["number"]), int(r["first"])) for r in out]
+
+    # ---- casting
+    def cast(self, proofs, reserve=True, raw=False):
+        """Verifies the voting proofs (bytes or ProofWithPublicInputs) and casts them:
+        one BallotResult each (raw=True: a RESULT_DTYPE array).  A batch the capacity
+        may not hold first reserves double (or what the batch needs); with
+        reserve=False it is refused, as qp_ballot_box_cast does."""
+        if self.verifier is None or self.verifier.h is None:
+            raise ValueError("cast needs the box's verifier=: a WormholeVerifier of the voting circuit's data")
+        datas = [bytes(p) if isinstance(p, (bytes, bytearray, memoryview)) else p.to_bytes() for p in proofs]
+        n = len(datas)
+        if n and reserve:
+            self._make_room(n)
+        ptrs = (ctypes.c_char_p * max(n, 1))(*datas)
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(d) for d in datas])
+        out = np.zeros(n, RESULT_DTYPE)
+        self._check(lib().qp_ballot_box_cast(self.h, self.verifier.h, ptrs, lens, n, out.ctypes.data))
+        return self._results(out, raw)
+
+    def cast_public(self, pis, verdicts=None, reserve=True, raw=False):
+        """Casts ballots whose proofs were verified elsewhere, by their public inputs:
+        pis [n][13] (a uint64 array, or rows of ints), verdicts [n] (non-zero marks a
+        rejected proof; None: all verified).  A row that does not hold 13 values
+        that fit 64 bits is cast as malformed."""
+        if isinstance(pis, np.ndarray) and pis.dtype == np.uint64 and pis.ndim == 2 and pis.shape[1] == NPI:
+            a = np.ascontiguousarray(pis)
+        else:
+            rows = [list(r) for r in pis]
+            a = np.full((len(rows), NPI), np.uint64(2**64 - 1), np.uint64)  # not canonical: malformed
+            for i, r in enumerate(rows):
+                if len(r) == NPI and all(0 <= int(x) < 2**64 for x in r):
+                    a[i] = [int(x) for x in r]
+        n = a.shape[0]
+        v = None
+        if verdicts is not None:
+            v = np.ascontiguousarray(verdicts, dtype=np.uint32)
+            if v.shape != (n,):
+                raise ValueError(f"{v.size} verdicts for {n} ballots")
+        if n and reserve:
+            self._make_room(n)
+        out = np.zeros(n, RESULT_DTYPE)
+        self._check(lib().qp_ballot_box_cast_public(self.h, a.ctypes.data, None if v is None else v.ctypes.data, n,
+                                                    out.ctypes.data))
+        return self._results(out, raw)
+
+    # ---- publication and audit
+    def entries(self, first=0, k=None):
+        """The log, entries [first, first + k) in admission order (k=None: to the end):
+        (nullifiers [k][4], numbers [k], counted [k] bool, votes [k] bool)."""
+        first = int(first)
+        k = max(self.admitted - first, 0) if k is None else int(k)
+        nul = np.zeros((k, 4), np.uint64)
+        num = np.zeros(k, np.uint64)
+        fl = np.zeros(k, np.uint8)
+        self._check(lib().qp_ballot_box_entries(self.h, first, k, nul.ctypes.data, num.ctypes.data, fl.ctypes.data))
+        return nul, num, (fl & FLAG_COUNTED) != 0, (fl & FLAG_VOTE) != 0
+
+    def recount(self):
+        """(yes, no, counted, admitted) recomputed from the log's flags alone."""
+        out = np.zeros(4, np.uint64)
+        self._check(lib().qp_ballot_box_recount(self.h, out))
+        return tuple(int(x) for x in out)
+
+    def cast_times(self):
+        """Device times of the last cast that admitted a ballot (ms): log upload, insert + resolve."""
+        ms = (ctypes.c_double * 2)()
+        self._check(lib().qp_ballot_box_cast_times(self.h, ms))
+        return {"upload_ms": ms[0], "insert_resolve_ms": ms[1]}
+
+    def free(self):
+        if self.h:
+            lib().qp_ballot_box_free(self.h)
+            self.h = None
+        if self._own_ctx is not None:
+            self._own_ctx.close()
+            self._own_ctx = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -1,0 +1,174 @@
+"""Times the ballot box: N = 2^20 synthetic ballots cast through cast_public into
+a box of capacity 2 N, in batches of 1024, 65536 and N, all distinct and with a
+quarter of them double votes; reserve 2 N -> 4 N on the full log; recount.
+Per figure the wall time (a host clock around the calls; each ends in a stream
+synchronise) and, on the device, the HIP-event times of the log upload and of
+insert + resolve (qp_ballot_box_cast_times), medians of --reps runs.
+
+The yardstick is the host path of the same library (ctx None: the sequential
+table of csrc/ballot_table.h) on the same stream in the same process; there is
+no earlier device counter to compare with.  The results of the two paths are
+compared as well.
+
+Last, `cast` of 1024 real voting proofs beside `verify_batch` alone on the same
+proofs: what the box adds to verification.
+
+Writes one JSON object (default profiles/ballot_bench.json) stamped with the
+library hash (tools/libhash.py).  Needs an MI355X: without a device it fails.
+
+  python tools/ballot_bench.py [--log-n 20] [--reps 7] [--proofs 1024] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "qp-zk-circuits-rm_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+P = 0xFFFFFFFF00000001
+PROPOSAL = [0x2A2A2A2A2A2A2A2A] * 4
+ROOT_DIGEST = [5, 6, 7, 8]
+
+
+def _stats(v):
+    return {"median": statistics.median(v), "min": min(v), "max": max(v), "runs": len(v)}
+
+
+def make_stream(rng, n, doubles):
+    """pis [n][13]: n - doubles distinct nullifiers, then `doubles` copies of earlier ones, shuffled"""
+    pis = np.zeros((n, 13), np.uint64)
+    pis[:, 0:4] = PROPOSAL
+    pis[:, 4:8] = ROOT_DIGEST
+    pis[:, 8] = rng.integers(0, 2, n, dtype=np.uint64)
+    fresh = n - doubles
+    pis[:fresh, 9:13] = rng.integers(0, P, size=(fresh, 4), dtype=np.uint64)
+    pis[fresh:, 9:13] = pis[rng.integers(0, fresh, doubles), 9:13]
+    return np.ascontiguousarray(pis[rng.permutation(n)])
+
+
+def cast_stream(BallotBox, ctx, pis, capacity, batch, reps):
+    """reps fresh boxes, the stream in batches of `batch`: wall of all the casts, summed event times"""
+    n = len(pis)
+    wall, up, ir, last = [], [], [], None
+    for _ in range(reps + 1):  # the first run is the warm-up
+        box = BallotBox(ctx, PROPOSAL, [ROOT_DIGEST], capacity=capacity)
+        res, u, k = [], 0.0, 0.0
+        t0 = time.perf_counter()
+        for at in range(0, n, batch):
+            res.append(box.cast_public(pis[at:at + batch], reserve=False, raw=True))
+            if ctx is not None:
+                ms = box.cast_times()
+                u, k = u + ms["upload_ms"], k + ms["insert_resolve_ms"]
+        wall.append(time.perf_counter() - t0)
+        up.append(u), ir.append(k)
+        last = (np.concatenate(res), box.tally, box.recount())
+        box.free()
+    rec = {"batch": batch, "calls": (n + batch - 1) // batch, "wall_s": _stats(wall[1:]),
+           "ballots_per_s_wall": n / statistics.median(wall[1:])}
+    if ctx is not None:
+        rec["upload_ms"] = _stats(up[1:])
+        rec["insert_resolve_ms"] = _stats(ir[1:])
+    return rec, last
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log-n", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--proofs", type=int, default=1024, help="real voting proofs of the cast / verify_batch pair (0 = skip)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ballot_bench.json"))
+    args = ap.parse_args()
+
+    import qp_wormhole
+    from qp_wormhole import BallotBox
+    from qp_wormhole._native import LIB_PATH
+    from libhash import lib_sha16
+
+    n = 1 << args.log_n
+    cap = 2 * n
+    rng = np.random.default_rng(1)
+    ctx = qp_wormhole.Context(0)
+    out = {"lib_sha16": lib_sha16(LIB_PATH), "ballots": n, "capacity": cap, "reps": args.reps,
+           "what": "wall: perf_counter around the cast_public calls of the whole stream, fresh box per run, one warm-up "
+                   "run dropped; *_ms: HIP events summed over the stream's calls; host: the same library with ctx None",
+           "streams": []}
+    for name, doubles in (("distinct", 0), ("quarter_doubles", n // 4)):
+        pis = make_stream(rng, n, doubles)
+        rows = []
+        for batch in (1024, 65536, n):
+            dev, dlast = cast_stream(BallotBox, ctx, pis, cap, batch, args.reps)
+            host, hlast = cast_stream(BallotBox, None, pis, cap, batch, args.reps)
+            same = bool((dlast[0] == hlast[0]).all()) and dlast[1:] == hlast[1:]
+            assert same, "device and host paths disagree"
+            rows.append({"batch": batch, "device": dev, "host": host, "results_equal": same,
+                         "device_wall_over_host_wall": dev["wall_s"]["median"] / host["wall_s"]["median"]})
+        out["streams"].append({"name": name, "doubles": doubles, "tally": list(dlast[1]), "batches": rows})
+
+    # reserve 2 N -> 4 N and recount on a box holding the N-ballot distinct stream
+    pis = make_stream(rng, n, 0)
+    for label, c in (("device", ctx), ("host", None)):
+        rs, rc = [], []
+        for _ in range(args.reps):
+            box = BallotBox(c, PROPOSAL, [ROOT_DIGEST], capacity=cap)
+            box.cast_public(pis, reserve=False, raw=True)
+            t0 = time.perf_counter()
+            box.reserve(2 * cap)
+            rs.append(time.perf_counter() - t0)
+            t0 = time.perf_counter()
+            got = box.recount()
+            rc.append(time.perf_counter() - t0)
+            assert got[:2] == box.tally and got[2:] == (n, n)
+            box.free()
+        out["reserve_" + label] = {"from": cap, "to": 2 * cap, "admitted": n, "wall_s": _stats(rs)}
+        out["recount_" + label] = {"admitted": n, "wall_s": _stats(rc)}
+
+    out["real_proofs"] = "not measured"
+    if args.proofs:
+        from qp_wormhole import VoterRegistry, WormholeVerifier
+        from qp_wormhole.prover import _verifier_only
+        k = args.proofs
+        keys = rng.integers(0, P, size=(k, 4), dtype=np.uint64)
+        circ = qp_wormhole.Circuit.voting()
+        prover = qp_wormhole.Prover(ctx, circ, k)
+        reg = VoterRegistry(ctx, keys)
+        proofs = reg.prove(prover, range(k), PROPOSAL, [bool(i & 1) for i in range(k)])
+        ver = WormholeVerifier(circuit_data=(_verifier_only(circ, prover), circ.common_data()), max_batch=256)
+        assert ver.verify_batch(proofs) == [0] * k  # warm-up
+        vt, ct = {"device": [], "host": []}, {"device": [], "host": []}
+        for _ in range(args.reps):
+            for label, c in (("device", ctx), ("host", None)):
+                t0 = time.perf_counter()
+                ver.verify_batch(proofs)
+                vt[label].append(time.perf_counter() - t0)
+                box = BallotBox(c, PROPOSAL, [reg.root], verifier=ver, capacity=k)
+                t0 = time.perf_counter()
+                res = box.cast(proofs, raw=True)
+                ct[label].append(time.perf_counter() - t0)
+                assert (res["status"] == 0).all() and box.tally == (k // 2, k - k // 2)
+                box.free()
+        out["real_proofs"] = {
+            "proofs": k, "verifier": "device query rounds, max_batch 256",
+            "verify_batch_wall_s": _stats(vt["device"] + vt["host"]),
+            "cast_device_box_wall_s": _stats(ct["device"]), "cast_host_box_wall_s": _stats(ct["host"]),
+            "box_adds_s_device": statistics.median(ct["device"]) - statistics.median(vt["device"]),
+            "box_adds_s_host": statistics.median(ct["host"]) - statistics.median(vt["host"])}
+        ver.close()
+        reg.free()
+        prover.free()
+        circ.free()
+    ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
