@@ -90,12 +90,6 @@ void leaf_hash(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint
 // parent levels down to the cap (two_to_one), appended after the N leaf digests
 void merkle_tree(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t d_bstride,
                  hipStream_t s);
-// leaf digests; returns the first level merkle_tree_from still builds (1)
-uint32_t leaf_hash_first(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint64_t *salt, uint32_t nsalt,
-                         uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t c_bstride,
-                         uint64_t s_bstride, uint64_t d_bstride, hipStream_t s);
-void merkle_tree_from(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t d_bstride,
-                      uint32_t first_level, hipStream_t s);
 // leaf digests + the whole tree
 void leaf_hash_tree(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint64_t *salt, uint32_t nsalt,
                     uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t c_bstride,

@@ -224,14 +224,14 @@ void leaf_hash(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint
   k_leaf_hash<<<grid, 256, 0, s>>>(cols, stride, ncols, salt, nsalt, digests, N, c_bstride, s_bstride, d_bstride);
 }
 
-void merkle_tree_from(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t d_bstride,
-                      uint32_t first_level, hipStream_t s) {
+void merkle_tree(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t d_bstride,
+                 hipStream_t s) {
   const uint32_t K = log_N - cap_h;  // levels above the leaves
   const bool row = merkle_row();
   const uint64_t coop_max = merkle_coop_max(row);
   // the batch size up to which the cooperative forms apply (path hook merkle_nbat)
   const uint64_t coop_nbat = (uint64_t)path_opt("merkle_nbat", MERKLE_COOP_NBAT);
-  for (uint32_t k0 = first_level; k0 <= K;) {
+  for (uint32_t k0 = 1; k0 <= K;) {
     const uint32_t lc = log_N - k0;  // log2(nodes at level k0)
     if (nbat <= coop_nbat && ((uint64_t)nbat << lc) <= coop_max) {
       if (row)
@@ -255,25 +255,11 @@ void merkle_tree_from(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_
   }
 }
 
-void merkle_tree(uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t d_bstride,
-                 hipStream_t s) {
-  merkle_tree_from(digests, log_N, cap_h, nbat, d_bstride, 1, s);
-}
-
-uint32_t leaf_hash_first(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint64_t *salt, uint32_t nsalt,
-                         uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t c_bstride,
-                         uint64_t s_bstride, uint64_t d_bstride, hipStream_t s) {
-  (void)cap_h;
-  leaf_hash(cols, stride, ncols, salt, nsalt, digests, 1u << log_N, nbat, c_bstride, s_bstride, d_bstride, s);
-  return 1;
-}
-
 void leaf_hash_tree(const uint64_t *cols, uint64_t stride, uint32_t ncols, const uint64_t *salt, uint32_t nsalt,
                     uint64_t *digests, uint32_t log_N, uint32_t cap_h, uint32_t nbat, uint64_t c_bstride,
                     uint64_t s_bstride, uint64_t d_bstride, hipStream_t s) {
-  const uint32_t first = leaf_hash_first(cols, stride, ncols, salt, nsalt, digests, log_N, cap_h, nbat, c_bstride,
-                                         s_bstride, d_bstride, s);
-  merkle_tree_from(digests, log_N, cap_h, nbat, d_bstride, first, s);
+  leaf_hash(cols, stride, ncols, salt, nsalt, digests, 1u << log_N, nbat, c_bstride, s_bstride, d_bstride, s);
+  merkle_tree(digests, log_N, cap_h, nbat, d_bstride, s);
 }
 
 __global__ void __launch_bounds__(256) k_permute(uint64_t *states, uint64_t n) {

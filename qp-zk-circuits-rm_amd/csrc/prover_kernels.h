@@ -1,8 +1,10 @@
-// prover_kernels.h — argument layouts and launchers of prover_kernels.hip.
-// Every stage of prove() has one launcher, declared next to the kernels it
-// launches: it owns the kernel choice and the grid, block and LDS sizes, and
-// both callers go through it: prove_batch (prover.cpp: nb proofs, per-proof
-// strides) and the seams (seams.cpp, capi.cpp: one proof, strides 0).
+// prover_kernels.h — argument layouts and launchers of the prover's stage
+// files (pp_z.hip, quotient.hip, openings.hip, fri.hip, pow.hip).  Every stage
+// of prove() has one launcher, defined next to the kernels it launches: it
+// owns the kernel choice and the grid, block and LDS sizes, and both callers
+// go through it: prove_batch (prover.cpp: nb proofs, per-proof strides) and
+// the seams (seams.cpp, capi.cpp: one proof, strides 0).  The kernels
+// themselves are declared nowhere outside their file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,6 +44,18 @@ void alpha_powers(uint64_t *apow, uint64_t alpha, uint32_t nterms);
 constexpr uint32_t OPEN_STRIDE = 520;  // 257 ext openings per proof (+pad)
 constexpr uint32_t APOW_STRIDE = 256;  // alpha_c^i, i < #vanishing terms (per challenge)
 
+// ---- pp_z.hip
+// wires_permutation_partial_products_and_zs for nb proofs: the chunk products
+// of every row (prods: scratch of nc * ceil(R / qdf) * n words per proof; the
+// compile-time kernel for the leaf circuits' shape), then their running
+// product into zs [nc * ceil(R / qdf)][n] per proof (rows staged in LDS up to
+// n = 2^LDS_LOG_MAX, read from HBM above)
+void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t w_bstride, const uint64_t *sigmas,
+                             const uint64_t *k_is, const uint64_t *chal, uint64_t *prods, uint64_t *zs,
+                             uint64_t z_bstride, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint32_t nb,
+                             hipStream_t s);
+
+// ---- quotient.hip
 using namespace qg;  // gate kinds (gates.h)
 // RandomAccessGate width k_quotient_1r evaluates (the recursive verifier's
 // RandomAccessGate::new_from_config shape); other widths take the per-gate
@@ -90,47 +104,6 @@ struct QuotientArgs {
 // zh[k] = Z_H on coset k of the LDE domain (x^n - 1 at x = g w_N^k) and its inverse
 void quotient_zh(QuotientArgs &a, uint32_t log_n, uint32_t rate_bits);
 
-struct FriComposeArgs {
-  const uint64_t *coeffs[4];
-  uint64_t bstride[4];
-  uint32_t npolys[4];
-  uint32_t noracles, nnext, log_n;
-  const uint64_t *chal;
-  uint64_t *comp;
-};
-
-__global__ void k_pp_rows(const uint64_t *wires, const uint64_t *sigmas, const uint64_t *k_is, const uint64_t *chal,
-                          uint64_t *prods, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint64_t w_bstride,
-                          uint64_t p_bstride, const uint64_t *tw);
-template <int R, int QDF>
-__global__ void k_pp_rows_t(const uint64_t *wires, const uint64_t *sigmas, const uint64_t *k_is, const uint64_t *chal,
-                            uint64_t *prods, uint32_t log_n, uint64_t w_bstride, uint64_t p_bstride,
-                            const uint64_t *tw);
-template <bool STAGE>
-__global__ void k_z_scan(const uint64_t *prods, uint64_t *zs, uint32_t log_n, uint32_t nc, uint32_t nchunks,
-                         uint64_t p_bstride, uint64_t z_bstride);
-// wires_permutation_partial_products_and_zs for nb proofs: the chunk products
-// of every row (prods: scratch of nc * ceil(R / qdf) * n words per proof; the
-// compile-time kernel for the leaf circuits' shape), then their running
-// product into zs [nc * ceil(R / qdf)][n] per proof (rows staged in LDS up to
-// n = 2^LDS_LOG_MAX, read from HBM above)
-void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t w_bstride, const uint64_t *sigmas,
-                             const uint64_t *k_is, const uint64_t *chal, uint64_t *prods, uint64_t *zs,
-                             uint64_t z_bstride, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint32_t nb,
-                             hipStream_t s);
-__global__ void k_quotient_1r(QuotientArgs a);
-template <int PART>
-__global__ void k_quotient_part(QuotientArgs a, uint32_t gi, uint32_t last);
-// the permutation terms + the gates of gmask that read routed wires only, one pass
-template <int QDF>
-__global__ void k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last);
-__global__ void k_qintt_gather_big(const uint64_t *vals, uint64_t *out, uint32_t log_n, uint32_t rate_bits,
-                                   uint64_t v_bstride, uint64_t o_bstride);
-__global__ void k_qintt_blocks(const uint64_t *vals, uint64_t *out, uint32_t log_n, uint32_t rate_bits,
-                               uint64_t v_bstride, uint64_t o_bstride, const uint64_t *tw, const uint64_t *pt_inv,
-                               uint64_t n_inv, uint64_t ginv);
-__global__ void k_qintt_radix(const uint64_t *cbuf, uint64_t *coeffs, uint32_t log_n, uint32_t rate_bits,
-                              uint64_t c_bstride, uint64_t o_bstride, uint64_t winv_r, uint64_t r_inv, uint64_t gninv);
 // compute_quotient_polys (plonk/prover.rs) as launches, shared by the prover's
 // stage 3 and the qp_quotient seam: the vanishing-polynomial values at every
 // LDE point of nb proofs with the chosen kernel(s) ...
@@ -151,9 +124,8 @@ void quotient_values(const QuotientArgs &a, QuotientKernel k, uint32_t nb, hipSt
 void quotient_coeffs(const Twiddles &tw, const uint64_t *qvals, uint64_t *cbuf, uint64_t *coeffs, uint32_t log_n,
                      uint32_t rate_bits, uint32_t nc, uint32_t nb, uint64_t v_bstride, uint64_t c_bstride,
                      uint64_t o_bstride, hipStream_t s);
-constexpr int OPEN_PB = 8;  // polys per k_openings block
-__global__ void k_openings(const uint64_t *coeffs, uint64_t c_bstride, uint32_t npolys, uint32_t log_n,
-                           const uint64_t *pts, uint32_t pt_off, uint64_t *out, uint32_t out_off);
+
+// ---- openings.hip
 // every opening batch of a proof (OpeningSet::new's zeta and g*zeta
 // evaluations) in one launch (+ a reduction when the coefficient range is
 // split over S slices); out[b][OPEN_STRIDE] as k_openings writes it
@@ -169,23 +141,23 @@ struct OpeningsArgs {
   const uint64_t *pts = nullptr;
   uint64_t *out = nullptr, *part = nullptr;  // part: nb * OPEN_MAX_SLICES * OPEN_STRIDE words
 };
-__global__ void k_openings_seg(OpeningsArgs a);
-__global__ void k_openings_reduce(const uint64_t *part, uint64_t *out, uint32_t ntot, uint32_t S);
 void openings(OpeningsArgs a, uint32_t nb, hipStream_t s);
-__global__ void k_fri_compose(FriComposeArgs a);
-template <int MAXPER>
-__global__ void k_fri_divide(const uint64_t *comp, uint64_t *fin, uint32_t log_n, const uint64_t *chal,
-                             uint64_t f_bstride, uint64_t f_cstride);
+
+// ---- fri.hip
+struct FriComposeArgs {
+  const uint64_t *coeffs[4];
+  uint64_t bstride[4];
+  uint32_t npolys[4];
+  uint32_t noracles, nnext, log_n;
+  const uint64_t *chal;
+  uint64_t *comp;
+};
 // the polynomial FRI starts from (PolynomialBatch::prove_openings) for nb
 // proofs: a.comp (4 n words per proof) = the alpha-reduced oracles, then
 // fin [2][f_cstride] per proof = alpha^nc comp / (X - zeta) + comp_next / (X - g zeta),
 // n coefficients each; 2^6 <= n <= 2^16
 void fri_initial_poly(const FriComposeArgs &a, uint64_t *fin, uint64_t f_bstride, uint64_t f_cstride, uint32_t nb,
                       hipStream_t s);
-__global__ void k_fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
-                           uint64_t d_bstride);
-__global__ void k_fri_leaf_row(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
-                               uint64_t d_bstride);
 // the leaf digests of a FRI layer for nb proofs (row or one-lane form by size)
 void fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
               uint64_t d_bstride, uint32_t nb, hipStream_t s);
@@ -196,25 +168,10 @@ void fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab
 void fri_layer_tree(const Twiddles &tw, const uint64_t *coef, uint64_t coef_cstride, uint64_t coef_bstride,
                     uint32_t coef_log, uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint32_t cap_h,
                     uint64_t shift, uint32_t nb, hipStream_t s);
-__global__ void k_fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer,
-                       const uint64_t *chal, uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz);
 // one FRI fold of nb proofs with beta = the layer's CH_FRI_BETA pair: cin
 // [2][2^log_len] -> cout [2][2^(log_len - ab)]; 2^log_nz: the possibly nonzero prefix of cin
 void fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer, const uint64_t *chal,
           uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz, uint32_t nb, hipStream_t s);
-__global__ void k_pow_scan(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
-                           uint32_t bits, uint64_t limit);
-// fri_proof_of_work's minimal witness per proof in one launch: found[b] = the
-// least witness below 2^min(bits + 20, 62), all ones if none (found and the
-// claim counters next are reset here)
-hipError_t pow_search(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
-                      uint32_t bits, hipStream_t s);
-__global__ void k_gather_rows_b(const uint64_t *cols, uint64_t stride, uint64_t bstride, uint32_t ncols,
-                                const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
-__global__ void k_gather_paths_b(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, uint32_t cap_h,
-                                 const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
-__global__ void k_gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab,
-                                  const uint32_t *idx, uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride);
 // query openings of nb proofs at leaves idx[b][q] >> shift: rows of an LDE
 // matrix (out[b][q][ncols]), Merkle paths (out[b][q][depth][4], depth =
 // log_leaves - cap_h) and FRI layer leaves (out[b][q][2 << ab]).  Nothing is
@@ -225,5 +182,12 @@ void gather_paths(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, 
                   uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s);
 void gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab, const uint32_t *idx,
                      uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s);
+
+// ---- pow.hip
+// fri_proof_of_work's minimal witness per proof in one launch: found[b] = the
+// least witness below 2^min(bits + 20, 62), all ones if none (found and the
+// claim counters next are reset here)
+hipError_t pow_search(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
+                      uint32_t bits, hipStream_t s);
 
 }  // namespace qpk

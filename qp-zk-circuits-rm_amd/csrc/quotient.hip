@@ -1,251 +1,25 @@
-// prover_kernels.hip — gfx950 kernels for the proof stages after the
-// commitments, batched over
-// proofs of one circuit (blockIdx.y / .z = proof index, per-proof strides).
+// quotient.hip — compute_quotient_polys on
+// gfx950, batched over proofs of one circuit (per-proof strides):
 //
-//   k_pp_rows / k_z_scan   wires_permutation_partial_products_and_zs (a9)
-//   k_quotient             compute_quotient_polys: vanishing poly at every
-//                          LDE point, alpha-reduced, / Z_H (a8)
-//   k_qintt_blocks/_radix  coset_ifft of size N as 2^r size-n LDS iNTTs + a
-//                          radix-2^r cross-block pass (a8, second half)
-//   k_openings             OpeningSet::new: Horner at zeta / g*zeta (a10)
-//   k_fri_compose/_divide  prove_openings: alpha-reduce + divide by (X - z) (a11)
-//   k_fri_leaf, k_fold     fri_committed_trees: leaves of 2^a ext, folding (a11)
-//   k_pow_scan             fri_proof_of_work: minimal witness (a12)
-//   k_gather_*             query-round openings (a11)
-#include "field.h"
-#include "poseidon.h"
-#include "poseidon_dev.h"
-#include "poseidon_coop.h"
-#include "prover_kernels.h"
-#include "paths.h"
-#include <stdlib.h>
-#include <algorithm>
-#include "ntt16.h"
-
-namespace qpk {
-
-using gl::ext;
-
-static inline unsigned cdiv(uint64_t a, unsigned b) { return (unsigned)((a + b - 1) / b); }
-
-__device__ __forceinline__ uint64_t wpow_N(const uint64_t *__restrict__ tw, uint32_t j, uint32_t logN) {
-  // w_N^j from the half table of w_{2^TW_LOG}: w_N^j = w_T^{j << (TW_LOG-logN)}
-  return tw_get(tw, j << (TW_LOG - logN));
-}
-
-// ---------------------------------------------------------------- a9
-
-// per row: P_j = prod_{k<=j} num_k/den_k over chunks of qdf routed wires
-__global__ void __launch_bounds__(256) k_pp_rows(const uint64_t *__restrict__ wires, const uint64_t *__restrict__ sigmas,
-                                                 const uint64_t *__restrict__ k_is, const uint64_t *__restrict__ chal,
-                                                 uint64_t *__restrict__ prods, uint32_t log_n, uint32_t R, uint32_t qdf,
-                                                 uint32_t nc, uint64_t w_bstride, uint64_t p_bstride,
-                                                 const uint64_t *__restrict__ tw) {
-  const uint32_t n = 1u << log_n;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t b = blockIdx.y;
-  wires += b * w_bstride;
-  prods += b * p_bstride;
-  const uint64_t *ch = chal + b * CHAL_STRIDE;
-  const uint64_t x = wpow_N(tw, i, log_n);
-  const uint32_t nchunks = (R + qdf - 1) / qdf;
-  for (uint32_t c = 0; c < nc; c++) {
-    const uint64_t beta = ch[CH_BETA + c], gamma = ch[CH_GAMMA + c];
-    uint64_t num[16], den[16];
-    for (uint32_t k = 0; k < nchunks; k++) {
-      uint64_t nn = 1, dd = 1;
-      for (uint32_t j = k * qdf; j < (k + 1) * qdf && j < R; j++) {
-        uint64_t wv = wires[(uint64_t)j * n + i];
-        nn = gl::mul(nn, gl::add(gl::add(wv, gl::mul(beta, gl::mul(k_is[j], x))), gamma));
-        dd = gl::mul(dd, gl::add(gl::add(wv, gl::mul(beta, sigmas[(uint64_t)j * n + i])), gamma));
-      }
-      num[k] = nn;
-      den[k] = dd;
-    }
-    // batch inversion of den[0..nchunks)
-    uint64_t pre[16], acc = 1;
-    for (uint32_t k = 0; k < nchunks; k++) {
-      pre[k] = acc;
-      acc = gl::mul(acc, den[k]);
-    }
-    uint64_t inv = gl::inv(acc);
-    for (uint32_t k = nchunks; k-- > 0;) {
-      uint64_t t = gl::mul(inv, pre[k]);
-      inv = gl::mul(inv, den[k]);
-      den[k] = t;
-    }
-    uint64_t run = 1;
-    for (uint32_t k = 0; k < nchunks; k++) {
-      run = gl::mul(run, gl::mul(num[k], den[k]));
-      prods[((uint64_t)c * nchunks + k) * n + i] = run;
-    }
-  }
-}
-
-// a^(p-2) by the addition chain of p - 2 = (2^32 - 2) 2^32 + (2^32 - 1):
-// 63 squarings + 8 products (the generic gl::inv runs a 64-step
-// square-and-multiply loop with a product per set bit: 125 products)
-__device__ __forceinline__ uint64_t inv_chain(uint64_t x) {
-  auto sq = [](uint64_t v, int k) {
-#pragma unroll
-    for (int i = 0; i < k; i++) v = gfn::mul(v, v);
-    return v;
-  };
-  const uint64_t t1 = x;
-  const uint64_t t2 = gfn::mul(sq(t1, 1), t1);   // x^(2^2-1)
-  const uint64_t t3 = gfn::mul(sq(t2, 1), t1);   // x^(2^3-1)
-  const uint64_t t6 = gfn::mul(sq(t3, 3), t3);   // x^(2^6-1)
-  const uint64_t t12 = gfn::mul(sq(t6, 6), t6);  // x^(2^12-1)
-  const uint64_t t24 = gfn::mul(sq(t12, 12), t12);
-  const uint64_t t30 = gfn::mul(sq(t24, 6), t6);
-  const uint64_t t31 = gfn::mul(sq(t30, 1), t1);  // x^(2^31-1)
-  const uint64_t t32 = gfn::mul(sq(t31, 1), t1);  // x^(2^32-1)
-  // x^(2^32-2) = (x^(2^31-1))^2; then shift up 32 and add 2^32-1
-  return gfn::mul(sq(sq(t31, 1), 32), t32);
-}
-
-// k_pp_rows for the leaf circuits' shape (R routed wires in chunks of QDF,
-// 2 challenges), compile-time so the per-row chunk values stay in registers:
-// the numerator term is w + gamma + k_j (beta x) (beta x once per row), and
-// the running quotient is kept as a fraction N_k / D_k (prefix products of
-// the chunk numerators and denominators), so one inversion of D_last per
-// challenge gives every D_k^-1 walking back (D_(k-1)^-1 = D_k^-1 den_k).
-// Non-canonical arithmetic inside (field_nc.h), canonical products out.  Same
-// values as k_pp_rows (plonky2 wires_permutation_partial_products_and_zs).
-template <int R, int QDF>
-__global__ void __launch_bounds__(256) k_pp_rows_t(const uint64_t *__restrict__ wires,
-                                                   const uint64_t *__restrict__ sigmas,
-                                                   const uint64_t *__restrict__ k_is,
-                                                   const uint64_t *__restrict__ chal, uint64_t *__restrict__ prods,
-                                                   uint32_t log_n, uint64_t w_bstride, uint64_t p_bstride,
-                                                   const uint64_t *__restrict__ tw) {
-  constexpr int NCH = (R + QDF - 1) / QDF;
-  const uint32_t n = 1u << log_n;
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t b = blockIdx.y;
-  wires += b * w_bstride;
-  prods += b * p_bstride;
-  const uint64_t *ch = chal + b * CHAL_STRIDE;
-  const uint64_t x = wpow_N(tw, i, log_n);
-#pragma unroll 1
-  for (int c = 0; c < 2; c++) {
-    const uint64_t beta = ch[CH_BETA + c], gamma = ch[CH_GAMMA + c];
-    const uint64_t bx = gfn::mul(beta, x);
-    uint64_t N[NCH], den[NCH], D = 1;
-#pragma unroll
-    for (int k = 0; k < NCH; k++) {
-      uint64_t nn = 1, dd = 1;
-#pragma unroll
-      for (int jj = 0; jj < QDF; jj++) {
-        const int j = k * QDF + jj;
-        if (j < R) {
-          const uint64_t wg = gfn::add(wires[(uint64_t)j * n + i], gamma);
-          const uint64_t nj = gfn::add(wg, gfn::mul(k_is[j], bx));
-          const uint64_t dj = gfn::add(wg, gfn::mul(beta, sigmas[(uint64_t)j * n + i]));
-          nn = jj ? gfn::mul(nn, nj) : nj;
-          dd = jj ? gfn::mul(dd, dj) : dj;
-        }
-      }
-      N[k] = k ? gfn::mul(N[k - 1], nn) : nn;
-      den[k] = dd;
-      D = k ? gfn::mul(D, dd) : dd;
-    }
-    uint64_t dinv = inv_chain(D);
-    uint64_t *out = prods + (uint64_t)c * NCH * n + i;
-#pragma unroll
-    for (int k = NCH - 1; k >= 0; k--) {
-      out[(uint64_t)k * n] = gfn::canon(gfn::mul(N[k], dinv));
-      if (k) dinv = gfn::mul(dinv, den[k]);
-    }
-  }
-}
-template __global__ void k_pp_rows_t<80, 8>(const uint64_t *, const uint64_t *, const uint64_t *, const uint64_t *,
-                                            uint64_t *, uint32_t, uint64_t, uint64_t, const uint64_t *);
-
-// exclusive prefix product of the full-row products -> Z; pp_j = Z * P_j.
-// The row products go through LDS (coalesced in, each thread's contiguous
-// chunk scanned from LDS, Z written back over them), so every HBM access is a
-// coalesced row sweep: n reads of the full products, (npp) reads of the
-// partial products, (1 + npp) n writes per challenge.
-// STAGE = true: the row products are staged in LDS (n <= 2^14); false: read
-// from HBM (the degree-2^15/2^16 top aggregation circuits), Z written there
-template <bool STAGE>
-__global__ void __launch_bounds__(1024) k_z_scan(const uint64_t *__restrict__ prods, uint64_t *__restrict__ zs,
-                                                 uint32_t log_n, uint32_t nc, uint32_t nchunks, uint64_t p_bstride,
-                                                 uint64_t z_bstride) {
-  extern __shared__ __attribute__((aligned(16))) uint64_t zbuf[];  // [lp(n)] rows (STAGE), then [T] partials
-  const uint32_t n = 1u << log_n;
-  const uint32_t c = blockIdx.x, b = blockIdx.y;
-  prods += b * p_bstride + (uint64_t)c * nchunks * n;
-  zs += b * z_bstride;
-  const uint64_t *full = prods + (uint64_t)(nchunks - 1) * n;
-  const uint32_t T = blockDim.x, t = threadIdx.x, per = (n + T - 1) / T;
-  uint64_t *part = STAGE ? zbuf + nt::lp(n) : zbuf;
-  // staged: row i at zbuf[lp(i)]; unstaged: Z itself is built in zs column c
-  uint64_t *zc = zs + (uint64_t)c * n;
-  auto row = [&](uint32_t i) -> uint64_t { return STAGE ? zbuf[nt::lp(i)] : full[i]; };
-  if constexpr (STAGE) {
-    for (uint32_t i = t; i < n; i += T) zbuf[nt::lp(i)] = full[i];
-    __syncthreads();
-  }
-  const uint32_t lo = min(t * per, n), hi = min(lo + per, n);
-  uint64_t local = 1;
-  for (uint32_t i = lo; i < hi; i++) local = gl::mul(local, row(i));
-  part[t] = local;
-  __syncthreads();
-  // inclusive Hillis-Steele scan over T partial products
-  for (uint32_t off = 1; off < T; off <<= 1) {
-    uint64_t v = t >= off ? part[t - off] : 1;
-    __syncthreads();
-    part[t] = gl::mul(part[t], v);
-    __syncthreads();
-  }
-  uint64_t z = t ? part[t - 1] : 1;
-  for (uint32_t i = lo; i < hi; i++) {
-    const uint64_t f = row(i);
-    if constexpr (STAGE) zbuf[nt::lp(i)] = z;
-    else zc[i] = z;
-    z = gl::mul(z, f);
-  }
-  __syncthreads();
-  const uint32_t npp = nchunks - 1;
-  for (uint32_t i = t; i < n; i += T) {
-    const uint64_t zi = STAGE ? zbuf[nt::lp(i)] : zc[i];
-    if constexpr (STAGE) zc[i] = zi;
-    for (uint32_t j = 0; j < npp; j++) zs[((uint64_t)nc + c * npp + j) * n + i] = gl::mul(zi, prods[(uint64_t)j * n + i]);
-  }
-}
-template __global__ void k_z_scan<true>(const uint64_t *, uint64_t *, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t);
-template __global__ void k_z_scan<false>(const uint64_t *, uint64_t *, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t);
-
-void partial_products_and_zs(const Twiddles &tw, const uint64_t *wires, uint64_t w_bstride, const uint64_t *sigmas,
-                             const uint64_t *k_is, const uint64_t *chal, uint64_t *prods, uint64_t *zs,
-                             uint64_t z_bstride, uint32_t log_n, uint32_t R, uint32_t qdf, uint32_t nc, uint32_t nb,
-                             hipStream_t s) {
-  const uint32_t n = 1u << log_n, nchunks = (R + qdf - 1) / qdf;
-  const uint64_t pbs = (uint64_t)nc * nchunks * n;
-  const dim3 rows(cdiv(n, 256), nb);
-  // the leaf circuits' shape takes the compile-time kernel
-  if (R == 80 && qdf == 8 && nc == 2)
-    k_pp_rows_t<80, 8><<<rows, 256, 0, s>>>(wires, sigmas, k_is, chal, prods, log_n, w_bstride, pbs, tw.fwd);
-  else
-    k_pp_rows<<<rows, 256, 0, s>>>(wires, sigmas, k_is, chal, prods, log_n, R, qdf, nc, w_bstride, pbs, tw.fwd);
-  // LDS: the T = 1024 partial products, after the staged rows
-  if (log_n <= LDS_LOG_MAX)
-    k_z_scan<true><<<dim3(nc, nb), 1024, 8u * (ntt_lds_words(n) + 1024), s>>>(prods, zs, log_n, nc, nchunks, pbs,
-                                                                               z_bstride);
-  else
-    k_z_scan<false><<<dim3(nc, nb), 1024, 8u * 1024, s>>>(prods, zs, log_n, nc, nchunks, pbs, z_bstride);
-}
-
-// ---------------------------------------------------------------- a8
+//   k_quotient_1r / _part / _prefix   the vanishing polynomial at every LDE
+//                                     point, alpha-reduced, / Z_H
+//   k_qintt_blocks / _radix           coset_ifft of size N as 2^r size-n LDS
+//                                     iNTTs + a radix-2^r cross-block pass
 //
 // One lane per LDE point.  Terms are alpha-reduced as sum_i t_i alpha_c^i
 // with per-proof power tables (apow, uniform across the workgroup -> scalar
 // loads); a gate's constraints are summed first and multiplied by the gate's
 // selector filter once.  Arithmetic is non-canonical (field_nc.h).
+#include "field.h"
+#include "field_nc.h"
+#include "poseidon.h"
+#include "poseidon_fast.h"
+#include "ntt16.h"
+#include "paths.h"
+#include "prover_kernels.h"
+#include "prover_dev.h"
+
+namespace qpk {
 
 #define WV(j) wl[(uint64_t)(j) * N]
 
@@ -1148,11 +922,6 @@ k_quotient_prefix(QuotientArgs a, uint32_t gmask, uint32_t last) {
   }
   quotient_store(a, q, N, t, jn, acc0, acc1, last);
 }
-template __global__ void k_quotient_prefix<8>(QuotientArgs, uint32_t, uint32_t);
-
-template __global__ void k_quotient_part<0>(QuotientArgs, uint32_t, uint32_t);
-template __global__ void k_quotient_part<1>(QuotientArgs, uint32_t, uint32_t);
-template __global__ void k_quotient_part<2>(QuotientArgs, uint32_t, uint32_t);
 
 #undef WV
 
@@ -1310,482 +1079,6 @@ void quotient_coeffs(const Twiddles &tw, const uint64_t *qvals, uint64_t *cbuf, 
   k_qintt_radix<<<dim3((unsigned)((n + 255) / 256), nc, nb), 256, 0, s>>>(
       cbuf, coeffs, log_n, rate_bits, c_bstride, o_bstride, gl::inv(gl::root_of_unity(rate_bits)), gl::inv(B),
       gl::inv(gl::pow(gl::GEN, n)));
-}
-
-// ---------------------------------------------------------------- a10
-
-// value of each coefficient column at an extension point: out[b][poly].
-// A block evaluates OPEN_PB polys of one proof: thread t walks k = t + jT with
-// one running power z^k shared by the OPEN_PB columns (2 base products per
-// coefficient instead of 6), then a tree reduction per poly.  blockDim = T
-// (host: 256, or n/4 >= 64 for small circuits so z^t's pow stays amortised).
-__global__ void __launch_bounds__(256) k_openings(const uint64_t *__restrict__ coeffs, uint64_t c_bstride,
-                                                  uint32_t npolys, uint32_t log_n, const uint64_t *__restrict__ pts,
-                                                  uint32_t pt_off, uint64_t *__restrict__ out, uint32_t out_off) {
-  __shared__ ext red[OPEN_PB][256];
-  const uint32_t n = 1u << log_n, T = blockDim.x, t = threadIdx.x;
-  const uint32_t p0 = blockIdx.x * OPEN_PB, b = blockIdx.y;
-  const uint32_t np = min((uint32_t)OPEN_PB, npolys - p0);
-  const uint64_t *cf = coeffs + b * c_bstride + (uint64_t)p0 * n;
-  const ext z = ext{pts[b * CHAL_STRIDE + pt_off], pts[b * CHAL_STRIDE + pt_off + 1]};
-  ext zp = gl::ext_pow(z, t);
-  const ext zs = gl::ext_pow(z, T);
-  ext acc[OPEN_PB];
-#pragma unroll
-  for (int j = 0; j < OPEN_PB; j++) acc[j] = ext{0, 0};
-  for (uint32_t k = t; k < n; k += T) {
-#pragma unroll
-    for (int j = 0; j < OPEN_PB; j++)
-      if ((uint32_t)j < np) acc[j] = gl::ext_add(acc[j], gl::ext_scale(zp, cf[(uint64_t)j * n + k]));
-    zp = gl::ext_mul(zp, zs);
-  }
-#pragma unroll
-  for (int j = 0; j < OPEN_PB; j++) red[j][t] = acc[j];
-  __syncthreads();
-  for (uint32_t o = T / 2; o; o >>= 1) {
-    if (t < o)
-      for (uint32_t j = 0; j < np; j++) red[j][t] = gl::ext_add(red[j][t], red[j][t + o]);
-    __syncthreads();
-  }
-  if (t < np) {
-    uint64_t *dst = out + b * OPEN_STRIDE + 2 * (out_off + p0 + t);
-    dst[0] = red[t][0].c0;
-    dst[1] = red[t][0].c1;
-  }
-}
-
-// all of a proof's opening batches in one launch: segment j's polys form
-// groups of OPEN_PB from group g0; each group's coefficient range splits into
-// S slices of n / S (a small batch otherwise leaves most CUs idle: one proof
-// has ~33 groups), whose partial sums k_openings_reduce adds (S > 1)
-__global__ void __launch_bounds__(256) k_openings_seg(OpeningsArgs a) {
-  __shared__ ext red[OPEN_PB][256];
-  const uint32_t n = 1u << a.log_n, T = blockDim.x, t = threadIdx.x;
-  const uint32_t g = blockIdx.x / a.S, slice = blockIdx.x % a.S, b = blockIdx.y;
-  uint32_t j = 0;
-  while (j + 1 < a.nseg && g >= a.seg[j + 1].g0) j++;
-  const OpenSeg sg = a.seg[j];
-  const uint32_t p0 = (g - sg.g0) * OPEN_PB;
-  const uint32_t np = min((uint32_t)OPEN_PB, sg.npolys - p0);
-  const uint32_t len = n / a.S, lo = slice * len;
-  const uint64_t *cf = sg.coeffs + b * sg.c_bstride + (uint64_t)p0 * n;
-  const ext z = ext{a.pts[b * CHAL_STRIDE + sg.pt_off], a.pts[b * CHAL_STRIDE + sg.pt_off + 1]};
-  ext zp = gl::ext_pow(z, lo + t);
-  const ext zs = gl::ext_pow(z, T);
-  ext acc[OPEN_PB];
-#pragma unroll
-  for (int q = 0; q < OPEN_PB; q++) acc[q] = ext{0, 0};
-  for (uint32_t k = lo + t; k < lo + len; k += T) {
-#pragma unroll
-    for (int q = 0; q < OPEN_PB; q++)
-      if ((uint32_t)q < np) acc[q] = gl::ext_add(acc[q], gl::ext_scale(zp, cf[(uint64_t)q * n + k]));
-    zp = gl::ext_mul(zp, zs);
-  }
-#pragma unroll
-  for (int q = 0; q < OPEN_PB; q++) red[q][t] = acc[q];
-  __syncthreads();
-  for (uint32_t o = T / 2; o; o >>= 1) {
-    if (t < o)
-      for (uint32_t q = 0; q < np; q++) red[q][t] = gl::ext_add(red[q][t], red[q][t + o]);
-    __syncthreads();
-  }
-  if (t < np) {
-    const uint32_t idx = sg.out_off + p0 + t;
-    uint64_t *dst = a.S == 1 ? a.out + b * OPEN_STRIDE + 2 * idx
-                             : a.part + ((uint64_t)(b * a.S + slice) * OPEN_STRIDE + 2 * idx);
-    dst[0] = red[t][0].c0;
-    dst[1] = red[t][0].c1;
-  }
-}
-
-__global__ void __launch_bounds__(256) k_openings_reduce(const uint64_t *__restrict__ part, uint64_t *__restrict__ out,
-                                                         uint32_t ntot, uint32_t S) {
-  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (idx >= ntot) return;
-  ext acc{0, 0};
-  for (uint32_t sl = 0; sl < S; sl++) {
-    const uint64_t *p = part + (uint64_t)(b * S + sl) * OPEN_STRIDE + 2 * idx;
-    acc = gl::ext_add(acc, ext{p[0], p[1]});
-  }
-  out[b * OPEN_STRIDE + 2 * idx] = acc.c0;
-  out[b * OPEN_STRIDE + 2 * idx + 1] = acc.c1;
-}
-
-void openings(OpeningsArgs a, uint32_t nb, hipStream_t s) {
-  const uint32_t n = 1u << a.log_n;
-  const unsigned T = (unsigned)std::min<uint32_t>(256, std::max<uint32_t>(64, n / 4));
-  a.ngroups = 0;
-  a.ntot = 0;
-  for (uint32_t j = 0; j < a.nseg; j++) {
-    a.seg[j].g0 = a.ngroups;
-    a.ngroups += (a.seg[j].npolys + OPEN_PB - 1) / OPEN_PB;
-    a.ntot = std::max(a.ntot, a.seg[j].out_off + a.seg[j].npolys);
-  }
-  // path hook open_slices=1: one block per group (the shape of the large batches)
-  const uint32_t smax = (uint32_t)std::min<long>(std::max<long>(path_opt("open_slices", OPEN_MAX_SLICES), 1),
-                                                 OPEN_MAX_SLICES);
-  a.S = 1;
-  while (a.S * 2 <= smax && a.S * 2 * T * 8 <= n && (uint64_t)a.ngroups * nb * a.S < 1024) a.S *= 2;
-  k_openings_seg<<<dim3(a.ngroups * a.S, nb), T, 0, s>>>(a);
-  if (a.S > 1) k_openings_reduce<<<dim3((a.ntot + 255) / 256, nb), 256, 0, s>>>(a.part, a.out, a.ntot, a.S);
-}
-
-// ---------------------------------------------------------------- a11
-
-// comp[k] = sum_j alpha^j c_j[k] over the listed oracles (Horner, reverse order)
-__global__ void __launch_bounds__(256) k_fri_compose(FriComposeArgs a) {
-  const uint32_t n = 1u << a.log_n;
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint32_t b = blockIdx.y;
-  const uint64_t *ch = a.chal + b * CHAL_STRIDE;
-  const ext al{ch[CH_FRI_ALPHA], ch[CH_FRI_ALPHA + 1]};
-  ext acc{0, 0};
-  for (int o = (int)a.noracles - 1; o >= 0; o--) {
-    const uint64_t *base = a.coeffs[o] + b * a.bstride[o] + k;
-    for (uint32_t p = a.npolys[o]; p-- > 0;) acc = gl::ext_add(gl::ext_mul(acc, al), ext{base[(uint64_t)p * n], 0});
-  }
-  ext acc2{0, 0};
-  const uint64_t *zb = a.coeffs[2] + b * a.bstride[2] + k;
-  for (uint32_t p = a.nnext; p-- > 0;) acc2 = gl::ext_add(gl::ext_mul(acc2, al), ext{zb[(uint64_t)p * n], 0});
-  uint64_t *o1 = a.comp + b * (4ull * n);
-  o1[k] = acc.c0;
-  o1[n + k] = acc.c1;
-  o1[2 * n + k] = acc2.c0;
-  o1[3 * n + k] = acc2.c1;
-}
-
-// suffix-scan form of divide_by_linear: q_{k-1} = sum_{i>=k} c_i z^{i-k}
-//   = z^{-k} S_k with S_k = sum_{i>=k} c_i z^i; final = alpha^nc Q1 + Q2
-// MAXPER: n / blockDim.x values per thread (16 up to n = 2^14; 64 for the
-// degree-2^15/2^16 top aggregation circuits, whose arrays live in scratch)
-template <int MAXPER>
-__global__ void __launch_bounds__(1024) k_fri_divide(const uint64_t *__restrict__ comp, uint64_t *__restrict__ fin,
-                                                     uint32_t log_n, const uint64_t *__restrict__ chal,
-                                                     uint64_t f_bstride, uint64_t f_cstride) {
-  __shared__ ext sh[1024];
-  const uint32_t n = 1u << log_n, b = blockIdx.x;
-  const uint64_t *ch = chal + b * CHAL_STRIDE;
-  const uint32_t T = blockDim.x, per = n / T;
-  const uint32_t lo = threadIdx.x * per;
-  ext res[MAXPER];
-  for (int pass = 0; pass < 2; pass++) {
-    const uint64_t *cc = comp + b * (4ull * n) + (uint64_t)pass * 2 * n;
-    const ext z{ch[pass ? CH_ZETA_NEXT : CH_ZETA], ch[(pass ? CH_ZETA_NEXT : CH_ZETA) + 1]};
-    const ext zi{ch[pass ? CH_ZETA_NEXT_INV : CH_ZETA_INV], ch[(pass ? CH_ZETA_NEXT_INV : CH_ZETA_INV) + 1]};
-    // local suffix sums within [lo, lo+per) of d_i = c_i z^i
-    ext zp = gl::ext_pow(z, lo);
-    ext d[MAXPER];
-    for (uint32_t i = 0; i < per; i++) {
-      d[i] = gl::ext_mul(ext{cc[lo + i], cc[n + lo + i]}, zp);
-      zp = gl::ext_mul(zp, z);
-    }
-    ext tot{0, 0};
-    for (uint32_t i = per; i-- > 0;) {
-      tot = gl::ext_add(tot, d[i]);
-      d[i] = tot;
-    }
-    sh[threadIdx.x] = tot;
-    __syncthreads();
-    // inclusive suffix scan across threads
-    for (uint32_t off = 1; off < T; off <<= 1) {
-      ext v = threadIdx.x + off < T ? sh[threadIdx.x + off] : ext{0, 0};
-      __syncthreads();
-      sh[threadIdx.x] = gl::ext_add(sh[threadIdx.x], v);
-      __syncthreads();
-    }
-    const ext after = threadIdx.x + 1 < T ? sh[threadIdx.x + 1] : ext{0, 0};
-    __syncthreads();
-    // q_{k-1} = z^{-k} (S_k) for k >= 1; output index m = k-1; q_{n-1} = 0 (padding)
-    ext zk = gl::ext_pow(zi, lo);
-    for (uint32_t i = 0; i < per; i++) {
-      const uint32_t k = lo + i;
-      ext q = gl::ext_mul(gl::ext_add(d[i], after), zk);  // S_k z^-k = q_{k-1}
-      zk = gl::ext_mul(zk, zi);
-      if (pass == 0) {
-        res[i] = q;
-      } else {
-        res[i] = gl::ext_add(res[i], q);
-      }
-      (void)k;
-    }
-    if (pass == 0) {
-      const ext ap{ch[CH_ALPHA_POW_NC], ch[CH_ALPHA_POW_NC + 1]};
-      for (uint32_t i = 0; i < per; i++) res[i] = gl::ext_mul(res[i], ap);
-    }
-  }
-  // res[i] at k = lo+i holds q_{k-1}; shift down by one, q_{n-1} = 0
-  uint64_t *o = fin + b * f_bstride;
-  for (uint32_t i = 0; i < per; i++) {
-    const uint32_t k = lo + i;
-    if (k == 0) continue;
-    o[k - 1] = res[i].c0;
-    o[f_cstride + k - 1] = res[i].c1;
-  }
-  if (threadIdx.x == T - 1) {
-    o[n - 1] = 0;
-    o[f_cstride + n - 1] = 0;
-  }
-}
-template __global__ void k_fri_divide<16>(const uint64_t *, uint64_t *, uint32_t, const uint64_t *, uint64_t, uint64_t);
-template __global__ void k_fri_divide<64>(const uint64_t *, uint64_t *, uint32_t, const uint64_t *, uint64_t, uint64_t);
-
-void fri_initial_poly(const FriComposeArgs &a, uint64_t *fin, uint64_t f_bstride, uint64_t f_cstride, uint32_t nb,
-                      hipStream_t s) {
-  const uint64_t n = 1ull << a.log_n;
-  k_fri_compose<<<dim3(cdiv(n, 256), nb), 256, 0, s>>>(a);
-  // k_fri_divide: n / 8 threads up to 1024, n / threads values each (n >= 2^6: at least 8 threads;
-  // <16> holds 16 per thread, n <= 2^14; <64> holds 64, n <= 2^16)
-  const unsigned T = (unsigned)std::min<uint64_t>(1024, n / 8);
-  if (n / T <= 16)
-    k_fri_divide<16><<<nb, T, 0, s>>>(a.comp, fin, a.log_n, a.chal, f_bstride, f_cstride);
-  else
-    k_fri_divide<64><<<nb, 1024, 0, s>>>(a.comp, fin, a.log_n, a.chal, f_bstride, f_cstride);
-}
-
-// FRI layer leaves: leaf i = 2^ab consecutive leaf-order ext values, interleaved c0,c1
-__global__ void __launch_bounds__(256) k_fri_leaf(const uint64_t *__restrict__ vals, uint64_t *__restrict__ dig,
-                                                  uint32_t log_len, uint32_t ab, uint64_t v_bstride, uint64_t d_bstride) {
-  const uint32_t nleaves = 1u << (log_len - ab);
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nleaves) return;
-  const uint32_t b = blockIdx.y;
-  const uint64_t L = 1ull << log_len;
-  const uint64_t *c0 = vals + b * v_bstride + ((uint64_t)i << ab);
-  const uint64_t *c1 = c0 + L;
-  const uint32_t W = 2u << ab;
-  uint64_t *o = dig + b * d_bstride + (uint64_t)i * 4;
-  if (W <= 4) {  // hash_or_noop: a leaf of <= 4 elements is its own digest (arity 2)
-    o[0] = psd::canon(c0[0]); o[1] = psd::canon(c1[0]); o[2] = psd::canon(c0[1]); o[3] = psd::canon(c1[1]);
-    return;
-  }
-  uint64_t s[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint32_t off = 0; off < W; off += 8) {
-#pragma unroll
-    for (uint32_t k = 0; k < 8; k += 2) {
-      const uint32_t e = (off + k) >> 1;
-      if (off + k < W) {
-        s[k] = c0[e];
-        s[k + 1] = c1[e];
-      }
-    }
-    psd::permute_nc(s);
-  }
-  o[0] = psd::canon(s[0]); o[1] = psd::canon(s[1]); o[2] = psd::canon(s[2]); o[3] = psd::canon(s[3]);
-}
-
-// k_fri_leaf with one 16-lane row per leaf (pc::permute_row): a layer of few
-// leaves (small batches, the upper FRI layers) otherwise costs a one-lane
-// permutation's latency per absorbed chunk whatever its width
-__global__ void __launch_bounds__(256) k_fri_leaf_row(const uint64_t *__restrict__ vals, uint64_t *__restrict__ dig,
-                                                      uint32_t log_len, uint32_t ab, uint64_t v_bstride,
-                                                      uint64_t d_bstride) {
-  const uint32_t i = blockIdx.x * 16 + (threadIdx.x >> 4), l16 = threadIdx.x & 15;
-  if (i >= (1u << (log_len - ab))) return;
-  const uint32_t b = blockIdx.y;
-  const uint64_t L = 1ull << log_len;
-  const uint64_t *c0 = vals + b * v_bstride + ((uint64_t)i << ab);
-  const uint32_t W = 2u << ab;  // > 4 (the launcher sends arity 2 to k_fri_leaf)
-  uint64_t x = 0;
-  for (uint32_t off = 0; off < W; off += 8) {
-    const uint32_t e = off + l16;  // element e: c0/c1 of value e >> 1
-    if (l16 < 8 && e < W) x = (e & 1 ? c0 + L : c0)[e >> 1];
-    x = pc::permute_row(x);
-  }
-  if (l16 < 4) dig[b * d_bstride + (uint64_t)i * 4 + l16] = psd::canon(x);
-}
-
-// leaves of a FRI layer: the row form up to FRI_ROW_MAX leaves over the
-// batch (path hook fri_row), the one-lane form above
-constexpr long FRI_ROW_MAX = 16384;
-void fri_leaf(const uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint64_t v_bstride,
-              uint64_t d_bstride, uint32_t nb, hipStream_t s) {
-  const uint64_t lim = (uint64_t)path_opt("fri_row", FRI_ROW_MAX);
-  const uint64_t nl = 1ull << (log_len - ab);
-  if ((2u << ab) > 4 && nl * nb <= lim)
-    k_fri_leaf_row<<<dim3((unsigned)((nl + 15) / 16), nb), 256, 0, s>>>(vals, dig, log_len, ab, v_bstride, d_bstride);
-  else
-    k_fri_leaf<<<dim3((unsigned)((nl + 255) / 256), nb), 256, 0, s>>>(vals, dig, log_len, ab, v_bstride, d_bstride);
-}
-
-void fri_layer_tree(const Twiddles &tw, const uint64_t *coef, uint64_t coef_cstride, uint64_t coef_bstride,
-                    uint32_t coef_log, uint64_t *vals, uint64_t *dig, uint32_t log_len, uint32_t ab, uint32_t cap_h,
-                    uint64_t shift, uint32_t nb, hipStream_t s) {
-  const uint64_t dbs = tree_digest_count(log_len - ab, cap_h) * 4;
-  lde(tw, coef, coef_cstride, vals, 1ull << log_len, 2, coef_log, log_len - coef_log, shift, nb, coef_bstride,
-      2ull << log_len, s);
-  fri_leaf(vals, dig, log_len, ab, 2ull << log_len, dbs, nb, s);
-  merkle_tree(dig, log_len - ab, cap_h, nb, dbs, s);
-}
-
-// fold: out[k] = sum_{i<2^ab} beta^i c[2^ab k + i]  (coefficients, ext as 2 columns).
-// Only the first 2^log_nz input coefficients can be nonzero (the layer-0
-// polynomial has degree < n in a length-N buffer): outputs past them are
-// written as zeros without reading the zero tail.
-__global__ void __launch_bounds__(256) k_fold(const uint64_t *__restrict__ cin, uint64_t *__restrict__ cout,
-                                              uint32_t log_len, uint32_t ab, uint32_t layer,
-                                              const uint64_t *__restrict__ chal, uint64_t i_bstride,
-                                              uint64_t o_bstride, uint32_t log_nz) {
-  const uint32_t nout = 1u << (log_len - ab);
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= nout) return;
-  const uint32_t b = blockIdx.y;
-  uint64_t *o = cout + b * o_bstride;
-  if (((uint64_t)k << ab) >= (1ull << log_nz)) {
-    o[k] = 0;
-    o[nout + k] = 0;
-    return;
-  }
-  const uint64_t *ch = chal + b * CHAL_STRIDE;
-  const ext beta{ch[CH_FRI_BETA + 2 * layer], ch[CH_FRI_BETA + 2 * layer + 1]};
-  const uint64_t L = 1ull << log_len;
-  const uint64_t *c0 = cin + b * i_bstride, *c1 = c0 + L;
-  ext acc{0, 0};
-  for (uint32_t i = 1u << ab; i-- > 0;) {
-    const uint64_t idx = ((uint64_t)k << ab) + i;
-    acc = gl::ext_add(gl::ext_mul(acc, beta), ext{c0[idx], c1[idx]});
-  }
-  o[k] = acc.c0;
-  o[nout + k] = acc.c1;
-}
-
-void fold(const uint64_t *cin, uint64_t *cout, uint32_t log_len, uint32_t ab, uint32_t layer, const uint64_t *chal,
-          uint64_t i_bstride, uint64_t o_bstride, uint32_t log_nz, uint32_t nb, hipStream_t s) {
-  k_fold<<<dim3(cdiv(1ull << (log_len - ab), 256), nb), 256, 0, s>>>(cin, cout, log_len, ab, layer, chal, i_bstride,
-                                                                     o_bstride, log_nz);
-}
-
-// ---------------------------------------------------------------- a12
-
-// Minimal witness, one launch for all proofs.  Candidates of proof b are
-// claimed in blocks of 256 from a per-proof counter (next[b], increasing), so
-// every block below the best hit is claimed while that hit is still unknown
-// and gets tested: the final found[b] is the minimal witness.  A workgroup
-// keeps claiming blocks of one proof until the claimed block starts at or
-// above found[b] (or at limit), then moves to the next proof, so the stragglers
-// of the geometric search get every workgroup of the grid.  limit bounds every
-// loop (16 PoW bits: no hit below 2^36 has probability exp(-2^20)).
-__device__ __forceinline__ bool pow_hit(const uint64_t *__restrict__ pre, uint32_t pos, uint64_t cand, uint32_t bits) {
-  const uint64_t y = pf::sbox(pf::add_c(cand, ps::RC_DEV[pos]));
-  const uint32_t y0 = pf::lo32(y), y1 = pf::hi32(y);
-  uint64_t s[12];
-#pragma unroll
-  for (int r = 0; r < 12; r++) {
-    const uint32_t c = (uint32_t)pre[12 + r];
-    s[r] = pf::reduce_row((uint64_t)y0 * c + (pre[r] & pf::EPS), (uint64_t)y1 * c + (pre[r] >> 32));
-  }
-  pf::rounds<1, 0x80u>(s);  // only lane 7 is read
-  return (psd::canon(s[7]) >> (64 - bits)) == 0;
-}
-
-// one candidate per thread per claimed block of 256 (2 or 4 per thread and
-// per-wave claims measured no better: profiles/r05_ab_pow_cpt.log,
-// r05_ab_pow_wave.log)
-__global__ void __launch_bounds__(256) k_pow_scan(const uint64_t *__restrict__ states, const uint32_t *__restrict__ pos,
-                                                  uint64_t *__restrict__ found, uint64_t *__restrict__ next, uint32_t nb,
-                                                  uint32_t bits, uint64_t limit) {
-  constexpr uint64_t BLK = 256;
-  __shared__ uint64_t blk;
-  __shared__ uint32_t done;
-  for (uint32_t i = 0; i < nb; i++) {
-    const uint32_t b = (blockIdx.x + i) % nb;
-    const uint64_t *pre = states + b * 24;
-    for (;;) {
-      if (threadIdx.x == 0) {
-        const uint64_t k = atomicAdd((unsigned long long *)(next + b), 1ull);
-        blk = k;
-        done = k * BLK >= limit || k * BLK >= *(const volatile uint64_t *)(found + b);
-      }
-      __syncthreads();
-      const uint64_t k = blk;
-      const uint32_t d = done;
-      __syncthreads();  // every lane has read blk / done before lane 0 rewrites them
-      if (d) break;
-      const uint64_t cand = k * BLK + threadIdx.x;
-      if (pow_hit(pre, pos[b], cand, bits)) atomicMin((unsigned long long *)(found + b), (unsigned long long)cand);
-    }
-  }
-}
-
-// 2048 workgroups claim 256-candidate blocks from per-proof counters, moving
-// on to the next proof once theirs has a hit below the claimed block (per-wave
-// claims and 2-4 candidates per thread measured no better:
-// profiles/r05_ab_pow_wave.log, r05_ab_pow_cpt.log; a windowed loop with a
-// host check per window was the round-1 form)
-hipError_t pow_search(const uint64_t *states, const uint32_t *pos, uint64_t *found, uint64_t *next, uint32_t nb,
-                      uint32_t bits, hipStream_t s) {
-  hipError_t e = hipMemsetAsync(found, 0xFF, (size_t)nb * 8, s);
-  if (!e) e = hipMemsetAsync(next, 0, (size_t)nb * 8, s);
-  if (e) return e;
-  const uint64_t limit = 1ull << std::min<uint32_t>(bits + 20, 62);
-  k_pow_scan<<<2048, 256, 0, s>>>(states, pos, found, next, nb, bits, limit);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------- gathers
-
-// out[b][q][c] = cols[b*bstride + c*stride + idx[b][q] >> shift]
-__global__ void k_gather_rows_b(const uint64_t *__restrict__ cols, uint64_t stride, uint64_t bstride, uint32_t ncols,
-                                const uint32_t *__restrict__ idx, uint32_t nq, uint32_t shift,
-                                uint64_t *__restrict__ out, uint64_t o_bstride) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t b = blockIdx.y;
-  if (t >= ncols * nq) return;
-  const uint32_t q = t / ncols, c = t % ncols;
-  out[b * o_bstride + t] = cols[b * bstride + (uint64_t)c * stride + (idx[b * nq + q] >> shift)];
-}
-
-// out[b][q][k][4] = sibling digest at level k of leaf idx[b][q] >> shift
-__global__ void k_gather_paths_b(const uint64_t *__restrict__ dig, uint64_t d_bstride, uint32_t log_leaves,
-                                 uint32_t cap_h, const uint32_t *__restrict__ idx, uint32_t nq, uint32_t shift,
-                                 uint64_t *__restrict__ out, uint64_t o_bstride) {
-  const uint32_t depth = log_leaves - cap_h;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t b = blockIdx.y;
-  if (t >= nq * depth * 4) return;
-  const uint32_t q = t / (depth * 4), r = t % (depth * 4), k = r / 4, e = r % 4;
-  uint64_t off = 0;
-  for (uint32_t j = 0; j < k; j++) off += (uint64_t)1 << (log_leaves - j);
-  const uint64_t leaf = idx[b * nq + q] >> shift;
-  const uint64_t sib = (leaf >> k) ^ 1u;
-  out[b * o_bstride + t] = dig[b * d_bstride + (off + sib) * 4 + e];
-}
-
-// FRI layer leaves for queries: out[b][q][2*arity] interleaved from 2 columns
-__global__ void k_gather_fri_leaf(const uint64_t *__restrict__ vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab,
-                                  const uint32_t *__restrict__ idx, uint32_t nq, uint32_t shift,
-                                  uint64_t *__restrict__ out, uint64_t o_bstride) {
-  const uint32_t W = 2u << ab;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t b = blockIdx.y;
-  if (t >= nq * W) return;
-  const uint32_t q = t / W, e = t % W;
-  const uint64_t leaf = idx[b * nq + q] >> shift;
-  const uint64_t L = 1ull << log_len;
-  out[b * o_bstride + t] = vals[b * v_bstride + (e & 1) * L + (leaf << ab) + (e >> 1)];
-}
-
-void gather_rows(const uint64_t *cols, uint64_t stride, uint64_t bstride, uint32_t ncols, const uint32_t *idx,
-                 uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
-  const uint64_t tot = (uint64_t)ncols * nq;
-  if (!tot) return;
-  k_gather_rows_b<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(cols, stride, bstride, ncols, idx, nq, shift, out, o_bstride);
-}
-
-void gather_paths(const uint64_t *dig, uint64_t d_bstride, uint32_t log_leaves, uint32_t cap_h, const uint32_t *idx,
-                  uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
-  const uint64_t tot = (uint64_t)nq * (log_leaves - cap_h) * 4;
-  if (!tot) return;
-  k_gather_paths_b<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(dig, d_bstride, log_leaves, cap_h, idx, nq, shift, out,
-                                                            o_bstride);
-}
-
-void gather_fri_leaf(const uint64_t *vals, uint64_t v_bstride, uint32_t log_len, uint32_t ab, const uint32_t *idx,
-                     uint32_t nq, uint32_t shift, uint64_t *out, uint64_t o_bstride, uint32_t nb, hipStream_t s) {
-  const uint64_t tot = (uint64_t)nq * (2u << ab);
-  if (!tot) return;
-  k_gather_fri_leaf<<<dim3(cdiv(tot, 256), nb), 256, 0, s>>>(vals, v_bstride, log_len, ab, idx, nq, shift, out,
-                                                             o_bstride);
 }
 
 }  // namespace qpk

@@ -3,10 +3,10 @@ the launchers' dispatch, and the case tables of test_gpu_merkle_forms.py (test
 infrastructure).
 
 The five thresholds (MERKLE_ROW_MAX, MERKLE_COOP_MAX, MERKLE_COOP_NBAT,
-MERKLE_FUSE_LOG in csrc/merkle.hip, FRI_ROW_MAX in csrc/prover_kernels.hip) and
+MERKLE_FUSE_LOG in csrc/merkle.hip, FRI_ROW_MAX in csrc/fri.hip) and
 the widths of the fixed-width leaf kernel are read out of the sources by regular
 expression; one that is not found is an error, so the numbers cannot drift.
-The control flow is restated by hand: level_plan must follow merkle_tree_from,
+The control flow is restated by hand: level_plan must follow merkle_tree,
 leaf_form must follow leaf_hash and fri_leaf_form must follow fri_leaf, line by
 line.  Whoever changes one of those launchers changes its model here.
 
@@ -25,7 +25,7 @@ CSRC = os.path.join(ROOT, "qp-zk-circuits-rm_amd", "csrc")
 G = 0xC65C18B67785D900
 
 CONSTANT_SOURCES = {"MERKLE_ROW_MAX": "merkle.hip", "MERKLE_COOP_MAX": "merkle.hip", "MERKLE_COOP_NBAT": "merkle.hip",
-                    "MERKLE_FUSE_LOG": "merkle.hip", "FRI_ROW_MAX": "prover_kernels.hip"}
+                    "MERKLE_FUSE_LOG": "merkle.hip", "FRI_ROW_MAX": "fri.hip"}
 
 
 def read_constant(name, text):
@@ -66,7 +66,7 @@ def parse_hooks(hooks):
 
 
 def level_plan(log_N, cap_h, nbat, hooks="", first_level=1):
-    """The launches of merkle_tree_from: [(kernel, first level, levels in the
+    """The launches of merkle_tree: [(kernel, first level, levels in the
     launch, blocks per tree (grid.x), threads per block)]."""
     c, h = constants(), parse_hooks(hooks)
     K = log_N - cap_h

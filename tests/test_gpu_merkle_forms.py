@@ -4,7 +4,7 @@ with the device).
 
 csrc/merkle.hip has four level kernels (k_merkle_level, k_merkle_levels,
 k_merkle_level_coop, k_merkle_level_row) and two leaf kernels (k_leaf_hash,
-k_leaf_hash_t<135|20|16>); csrc/prover_kernels.hip has k_fri_leaf and
+k_leaf_hash_t<135|20|16>); csrc/fri.hip has k_fri_leaf and
 k_fri_leaf_row.  The launchers choose by nodes x batch, and at batch 1 every
 small tree takes the row form, so the path hooks of csrc/paths.h force the
 others.  merkle_forms.py models that choice; the tests without a gpu mark check
