@@ -378,6 +378,7 @@ enum {
     QP_PFORM_PARTIAL_DYN,      /* pf::sbox on lane 0, then mds_rows_block_dyn folding RC[param], 1..29 */
     QP_PFORM_COOP_MDS,         /* pc::wave_mds_row with pc::mds_coef, one state per wave    */
     QP_PFORM_ROW_MDS,          /* pc::row_mds with pc::mds_coef, one state per 16-lane row  */
+    QP_PFORM_DENSE_GROUP,      /* pf::dense_group<param, pfd::GLEN[param]>, param a group start: 0, 3, .., 15, 18, 20 */
     QP_PFORM_COUNT
 };
 int qp_debug_poseidon_op(qp_ctx *ctx, uint32_t form, uint32_t param, const uint64_t *states, uint64_t nstates,

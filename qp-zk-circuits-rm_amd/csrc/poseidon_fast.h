@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include "field_nc.h"
 #include "poseidon.h"
+#include "poseidon_dense_consts.h"
 #include "poseidon_partial_consts.h"
 
 namespace pf {
@@ -281,7 +282,9 @@ __device__ __forceinline__ void full_round_dyn(uint64_t s[12], const uint64_t *_
 // dot product for lane 0 and 11 scalar multiply-adds.  Dense constants act on
 // 22-bit limbs (x = l0 + 2^22 l1 + 2^44 l2) through precomputed c 2^(22k) mod
 // p halves, so every accumulator stays < 2^60 and reduces in 4 instructions.
-// Same permutation as the plain rounds.
+// Same permutation as the plain rounds.  The quotient's Poseidon gate runs its
+// partial rounds this way (its wire checks hook each round's S-box input); the
+// hashing permutation runs dense_group below.
 
 __device__ __forceinline__ void limbs22(uint64_t x, uint32_t l[3]) {
   const uint32_t lo = lo32(x), hi = hi32(x);
@@ -447,19 +450,107 @@ __device__ __forceinline__ void partial_group(uint64_t s[12], const HK &hook = H
   s[0] = s0;
 }
 
+// ---- dense groups of G <= 3 partial rounds (tools/gen_poseidon_dense.py): a
+// partial round is v <- M (Z v + e_0 v_0^7) + c with Z zeroing lane 0, so G of
+// them are rows of (MZ)^m over the group-start lanes 1..11 plus columns
+// (MZ)^k M e_0 for the group's S-box outputs x_l, all exact small integers
+// (< 2^22, row sums < 2^23.85).  Every term is one mad per 32-bit half, as in
+// the dense MDS rows, where the sparse form pays six for a full-width
+// constant; al, ah stay below 2^56 (tests/test_poseidon_dense.py) and reduce
+// with reduce_row.  The hashing permutation runs the partial rounds this way.
+
+// al += lo * C, ah += hi * C: one constant for the pair of mads (inline up to
+// 64, else an SGPR), the dead carry-outs sunk into VCC as in mac_limbs
+template <uint32_t C>
+__device__ __forceinline__ void mac_pair(uint64_t &al, uint64_t &ah, uint32_t lo, uint32_t hi) {
+  static_assert(C != 0, "the integer rows have no zero entry");
+  if constexpr (C <= 64)
+    asm("v_mad_u64_u32 %0, vcc, %2, %4, %0\n\tv_mad_u64_u32 %1, vcc, %3, %4, %1"
+        : "+v"(al), "+v"(ah) : "v"(lo), "v"(hi), "i"(C) : "vcc");
+  else
+    asm("v_mad_u64_u32 %0, vcc, %2, %4, %0\n\tv_mad_u64_u32 %1, vcc, %3, %4, %1"
+        : "+v"(al), "+v"(ah) : "v"(lo), "v"(hi), "s"(C) : "vcc");
+}
+
+// row I of step M (1..G) of the group starting at partial round T0:
+//   K[T0+M-1][I] + sum_(l<M) COL[M-1-l][I] x_l + sum_(j=1..11) POW[M][I][j] v_j
+// The newest x's column is M's column 0 (inline constants): its pair of mads
+// opens the row with the halves of K as addends (an SGPR addend leaves the
+// constant bus no room for an SGPR factor).
+template <int M, int I, int J = 1>
+__device__ __forceinline__ void dg_lane_terms(uint64_t &al, uint64_t &ah, const uint32_t lo[12], const uint32_t hi[12]) {
+  if constexpr (J < 12) {
+    mac_pair<pfd::POW[((M - 1) * 12 + I) * 11 + J - 1]>(al, ah, lo[J], hi[J]);
+    dg_lane_terms<M, I, J + 1>(al, ah, lo, hi);
+  }
+}
+template <int M, int I, int L>
+__device__ __forceinline__ void dg_x_terms(uint64_t &al, uint64_t &ah, const uint32_t *xl, const uint32_t *xh) {
+  if constexpr (L >= 0) {
+    mac_pair<pfd::COL[(M - 1 - L) * 12 + I]>(al, ah, xl[L], xh[L]);
+    dg_x_terms<M, I, L - 1>(al, ah, xl, xh);
+  }
+}
+template <int T0, int M, int I>
+__device__ __forceinline__ uint64_t dg_row(const uint32_t lo[12], const uint32_t hi[12], const uint32_t *xl,
+                                           const uint32_t *xh) {
+  constexpr uint32_t C0 = pfd::COL[I];
+  static_assert(C0 <= 64, "M's column 0 is inline");
+  constexpr uint64_t kl = pfd::K[((T0 + M - 1) * 12 + I) * 2], kh = pfd::K[((T0 + M - 1) * 12 + I) * 2 + 1];
+  uint64_t al, ah;
+  asm("v_mad_u64_u32 %0, vcc, %2, %4, %5\n\tv_mad_u64_u32 %1, vcc, %3, %4, %6"
+      : "=&v"(al), "=&v"(ah) : "v"(xl[M - 1]), "v"(xh[M - 1]), "i"(C0), "s"(kl), "s"(kh) : "vcc");
+  dg_x_terms<M, I, M - 2>(al, ah, xl, xh);
+  dg_lane_terms<M, I>(al, ah, lo, hi);
+  return reduce_row(al, ah);
+}
+
+// x_0 = v_0^7, then y_M (row 0 of step M) and x_M = y_M^7 for M = 1..G-1
+template <int T0, int G, int M = 1>
+__device__ __forceinline__ void dg_lane0(const uint32_t lo[12], const uint32_t hi[12], uint32_t *xl, uint32_t *xh) {
+  if constexpr (M < G) {
+    const uint64_t x = sbox(dg_row<T0, M, 0>(lo, hi, xl, xh));
+    xl[M] = lo32(x);
+    xh[M] = hi32(x);
+    dg_lane0<T0, G, M + 1>(lo, hi, xl, xh);
+  }
+}
+template <int T0, int G, int I = 0>
+__device__ __forceinline__ void dg_out(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12], const uint32_t *xl,
+                                       const uint32_t *xh) {
+  if constexpr (I < 12) {
+    s[I] = dg_row<T0, G, I>(lo, hi, xl, xh);
+    dg_out<T0, G, I + 1>(s, lo, hi, xl, xh);
+  }
+}
+
+// partial rounds T0..T0+G-1 on the state entering round 4 + T0 (its constants
+// added); leaves the state entering round 4 + T0 + G
+template <int T0, int G>
+__device__ __forceinline__ void dense_group(uint64_t s[12]) {
+  static_assert(G >= 1 && G <= 3 && T0 >= 0 && T0 + G <= 22, "the tables hold (MZ)^1..3");
+  uint32_t lo[12], hi[12], xl[G], xh[G];
+#pragma unroll
+  for (int j = 1; j < 12; j++) {
+    lo[j] = lo32(s[j]);
+    hi[j] = hi32(s[j]);
+  }
+  const uint64_t x0 = sbox(s[0]);
+  xl[0] = lo32(x0);
+  xh[0] = hi32(x0);
+  dg_lane0<T0, G>(lo, hi, xl, xh);
+  dg_out<T0, G>(s, lo, hi, xl, xh);
+}
+
 // rounds R..29.  OUT: bit mask of the output lanes the caller reads (the last
 // MDS computes only those rows; digests need lanes 0..3, the PoW lane 7)
 template <int R, uint32_t OUT = 0xFFFu>
 __device__ __forceinline__ void rounds(uint64_t s[12]) {
-  if constexpr (R == 3) {
-    // the last full round before the partial rounds: its MDS merged with D_4
-    sbox12(s);
-    mds_init_sparse(s);
-    rounds<4, OUT>(s);
-  } else if constexpr (R >= 4 && R < 26) {
-    constexpr int T0 = R - 4, G = (22 - T0) < PF_GROUP ? (22 - T0) : PF_GROUP;
-    static_assert(G > 1, "22 partial rounds in groups of PF_GROUP leave no single round");
-    partial_group<T0, G>(s);
+  if constexpr (R >= 4 && R < 26) {
+    // the partial rounds, in the groups of pfd::GLEN
+    constexpr int T0 = R - 4, G = pfd::GLEN[T0];
+    static_assert(G > 0, "partial rounds are entered at a group start");
+    dense_group<T0, G>(s);
     rounds<R + G, OUT>(s);
   } else if constexpr (R < 30) {
     sbox12(s);

@@ -373,7 +373,7 @@ def debug_field_op(ctx, op, a, b=None, param=0):
 # qp_debug_poseidon_op forms (include/qpgpu.h QP_PFORM_*)
 (PFORM_PERMUTE_NC, PFORM_PERMUTE_CAPZ, PFORM_ROUNDS1_L7, PFORM_COOP_PERMUTE, PFORM_ROW_PERMUTE, PFORM_MDS_BLOCK,
  PFORM_MDS_K, PFORM_MDS_MADS, PFORM_CAPZ_ROUND0, PFORM_MDS_INIT_SPARSE, PFORM_PARTIAL_GROUP, PFORM_FULL_ROUND_DYN,
- PFORM_PARTIAL_DYN, PFORM_COOP_MDS, PFORM_ROW_MDS, PFORM_COUNT) = range(16)
+ PFORM_PARTIAL_DYN, PFORM_COOP_MDS, PFORM_ROW_MDS, PFORM_DENSE_GROUP, PFORM_COUNT) = range(17)
 
 
 def debug_poseidon_op(ctx, form, states, param=0):
