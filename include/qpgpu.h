@@ -556,6 +556,57 @@ int qp_ballot_box_recount(qp_ballot_box *b, uint64_t out[4]);
  * insert + resolve.  Diagnostic entry point (tools/ballot_bench.py); 0 on the host path.    */
 int qp_ballot_box_cast_times(const qp_ballot_box *b, double ms[2]);
 
+/* ---- the log commitment: what the operator publishes, and a voter's receipt --
+ * The log is append-only and final: an entry never changes once its cast
+ * returned.  Its commitment is (root, n), n = the admitted count:
+ *   log leaf of entry seq = hash_no_pad([nullifier[0..4], number, flags]), six
+ *     felts, flags the log's byte (bit 0 the vote, bit 1 counted);
+ *   the tree over leaves [0, n) in the registry's convention: node =
+ *     hash_no_pad(left || right), the last node of an odd level moves up
+ *     unchanged.
+ * The operator publishes (root, n, tally).  A receipt ties one entry to that
+ * pair: the entry, its siblings compacted as qp_registry_paths compacts them,
+ * the side bits and the depth.  A receipt is valid only under the (root, n) it
+ * was made under: every later cast that admits a ballot changes both.  The
+ * checker takes the tree's shape from (seq, n) alone (at level l the node
+ * seq >> l has a sibling iff ((seq >> l) ^ 1) < ceil(n / 2^l)) and rejects a
+ * receipt whose depth or side bits say otherwise, so a node cannot be offered
+ * as a leaf.  The tree (64 bytes per entry of capacity on the device) is
+ * allocated by the first commit and brought up to date on demand only; reserve
+ * drops it, and the next commit rebuilds it to the same root.  A device step
+ * that fails is QP_ERR_HIP and leaves the box dead, as in qp_ballot_box_cast. */
+/* seq_out[i] = the log index of the *counted* entry with nullifiers[i][4] (a double vote's
+ * nullifier gives the counted entry, not its own), UINT64_MAX if that nullifier was never
+ * admitted.  A felt >= p: QP_ERR_ARG naming the position.  k == 0: QP_OK, nothing launched */
+int qp_ballot_box_find(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out);
+/* hashes the leaves the tree does not hold yet and the nodes above them; root_out, *n_out (either
+ * may be NULL) = the commitment.  Nothing admitted: QP_ERR_STATE "empty log"; nothing new since
+ * the last commit: the same pair, nothing launched                                          */
+int qp_ballot_box_commit_log(qp_ballot_box *b, uint64_t root_out[4], uint64_t *n_out);
+/* commits, then the paths of entries seqs[0..k) (each < admitted, else QP_ERR_ARG before anything
+ * is enqueued): siblings [k][32][4] (the zero digest from the depth up), path_bits[i] bit j = side
+ * of sibling j (1: the entry's node is the right child), depth[i], leaves [k][4] (may be NULL) =
+ * the entries' log leaves; root_out, *n_out (either may be NULL) = the commitment they hold under */
+int qp_ballot_box_receipts(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
+                           uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out);
+/* the log entries seqs[0..k) (each < admitted, any order): nullifiers [k][4], numbers [k], flags [k]
+ * as qp_ballot_box_entries gives them; each may be NULL.  What a receipt carries beside its path */
+int qp_ballot_box_entries_at(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers,
+                             uint64_t *numbers, uint8_t *flags);
+typedef enum {
+    QP_RECEIPT_OK = 0,
+    QP_RECEIPT_SHAPE = 1,         /* seq >= n, n outside 1..2^31, depth or path_bits not the shape of (seq, n),
+                                     or a non-zero sibling slot above the depth */
+    QP_RECEIPT_ROOT = 2,          /* the walk from the entry's leaf does not end at root */
+    QP_RECEIPT_NON_CANONICAL = 3, /* a felt >= p in root, nullifier, number or siblings, or flags > 3 */
+    QP_RECEIPT_NULL = 4           /* a null pointer */
+} qp_receipt_status;
+/* checks a receipt against a published (root, n); needs no box and no device.  siblings [32][4].
+ * Returns a qp_receipt_status: the first reason found, in the order non-canonical, shape, root  */
+int qp_ballot_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],
+                            uint64_t number, uint8_t flags, const uint64_t *siblings, uint32_t path_bits,
+                            uint32_t depth);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

@@ -2,20 +2,29 @@
 // verified through the batch verifier, their public inputs screened on the
 // host (ballot_table.h), each nullifier admitted once.  With a context the
 // nullifier set and the tally live on the device (ballot.hip); without one the
-// same semantics run on the host (qb::HostBox).
+// same semantics run on the host (qb::HostBox).  The log commitment (find,
+// commit_log, receipts and the receipt check: ballot_log.h) is brought up to
+// date on demand; a cast does not touch it.
 #include "../../include/qpgpu.h"
 #include <string.h>
+#include <algorithm>
 #include <memory>
 #include <new>
 #include <string>
 #include <utility>
 #include <vector>
 #include "ballot_kernels.h"
+#include "ballot_log.h"
 #include "ballot_table.h"
 #include "ctx.h"
+#include "registry_kernels.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_ballot_result) == sizeof(qb::Result) && sizeof(qb::Result) == 24, "qp_ballot_result layout");
+static_assert(QP_RECEIPT_OK == qb::RECEIPT_OK && QP_RECEIPT_SHAPE == qb::RECEIPT_SHAPE &&
+                  QP_RECEIPT_ROOT == qb::RECEIPT_ROOT && QP_RECEIPT_NON_CANONICAL == qb::RECEIPT_NON_CANONICAL &&
+                  QP_RECEIPT_NULL == qb::RECEIPT_NULL,
+              "qp_receipt_status and ballot_log.h differ");
 static_assert(QP_BALLOT_COUNTED == qb::COUNTED && QP_BALLOT_PROOF_REJECTED == qb::PROOF_REJECTED &&
                   QP_BALLOT_MALFORMED == qb::MALFORMED && QP_BALLOT_WRONG_PROPOSAL == qb::WRONG_PROPOSAL &&
                   QP_BALLOT_UNKNOWN_ROOT == qb::UNKNOWN_ROOT && QP_BALLOT_BAD_VOTE == qb::BAD_VOTE &&
@@ -48,6 +57,13 @@ struct qp_ballot_box {
   std::vector<uint64_t> h_first;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
+  // ---- the log commitment, both paths: built by the first commit, dropped by reserve
+  qb::HostLog hlog;
+  DevBuf d_dig;                // the log tree, registry_reserved(capacity) digests
+  qpk::RegistryLevels lv;      // its table at `committed` leaves
+  uint64_t committed = 0;      // leaves of the tree = the n of (log_root, n)
+  uint64_t log_root[4] = {0, 0, 0, 0};
+  DevBuf d_q, d_seq, d_sib, d_bits, d_depth, d_leaf, d_flag;  // per find / receipts batch (LOG_BATCH entries)
   ~qp_ballot_box() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -154,6 +170,164 @@ int cast_screened(qp_ballot_box *b, const char *fn, const uint64_t *pis, const u
 int bad_alloc(qp_ballot_box *b, const char *fn) {
   b->err = std::string(fn) + ": out of host memory";
   return QP_ERR_OOM;
+}
+
+// entries per k_ballot_find / k_registry_paths / k_ballot_gather launch (the batch buffers hold this
+// many: 8 MB of siblings)
+constexpr uint32_t LOG_BATCH = 8192;
+
+int log_batch_buffers(qp_ballot_box *b) {
+  if (b->d_q.p) return QP_OK;
+  QP_HIP_TRY(b, b->d_seq.alloc(LOG_BATCH));
+  QP_HIP_TRY(b, b->d_sib.alloc((size_t)LOG_BATCH * qpk::REG_PATH_SLOTS * 4));
+  QP_HIP_TRY(b, b->d_bits.alloc(LOG_BATCH / 2));
+  QP_HIP_TRY(b, b->d_depth.alloc(LOG_BATCH / 2));
+  QP_HIP_TRY(b, b->d_leaf.alloc((size_t)LOG_BATCH * 4));
+  QP_HIP_TRY(b, b->d_flag.alloc(LOG_BATCH / 8));
+  QP_HIP_TRY(b, b->d_q.alloc((size_t)LOG_BATCH * 4));
+  return QP_OK;
+}
+
+// the defensive error word after a launch of the log's kernels (copied by the caller, stream synchronised)
+int log_error_word(qp_ballot_box *b, const char *fn, uint32_t err) {
+  if (!err) return QP_OK;
+  b->err = std::string(fn) + (err & 4 ? ": a ballot number in the log is not a field element"
+                                      : ": a slot of the nullifier table holds no log entry") +
+           " (an internal invariant broke)";
+  return QP_ERR_STATE;
+}
+
+int find_device(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  int rc = log_batch_buffers(b);
+  if (rc) return rc;
+  qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
+  std::vector<uint32_t> h(std::min(k, LOG_BATCH));
+  uint32_t err = 0;
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(LOG_BATCH, k - done);
+    QP_HIP_TRY(b, hipMemcpyAsync(b->d_q.p, nullifiers + (size_t)done * 4, (size_t)nb * 32, hipMemcpyHostToDevice, s));
+    qpk::ballot_find(b->t.dev(), (uint32_t)b->count, b->d_q.p, nb, b->d_seq.as<uint32_t>(), ctr, s);
+    QP_HIP_TRY(b, hipGetLastError());
+    QP_HIP_TRY(b, hipMemcpyAsync(h.data(), b->d_seq.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipStreamSynchronize(s));
+    if ((rc = log_error_word(b, "qp_ballot_box_find", err))) return rc;
+    for (uint32_t i = 0; i < nb; i++) seq_out[done + i] = h[i] == qb::EMPTY ? qb::NOT_FOUND : h[i];
+    done += nb;
+  }
+  return QP_OK;
+}
+
+// the log tree up to the admitted count (> 0; the caller checks): leaves [committed, count), the
+// levels above them, the root
+int commit_device(qp_ballot_box *b) {
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  if (b->committed == b->count) return QP_OK;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  if (!b->d_dig.p) QP_HIP_TRY(b, b->d_dig.alloc((size_t)qpk::registry_reserved(b->capacity) * 4));
+  qpk::RegistryLevels lv;
+  if (!qpk::registry_levels_reserved(b->count, b->capacity, lv)) {
+    b->err = "qp_ballot_box_commit_log: the log does not fit its capacity (an internal invariant broke)";
+    return QP_ERR_STATE;
+  }
+  qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
+  uint64_t root[4];
+  uint32_t err = 0;
+  qpk::ballot_leaves(b->t.dev(), (uint32_t)b->committed, (uint32_t)b->count, b->d_dig.p, ctr, s);
+  QP_HIP_TRY(b, hipGetLastError());
+  qpk::registry_append(b->d_dig.p, lv, b->committed, s);
+  QP_HIP_TRY(b, hipGetLastError());
+  QP_HIP_TRY(b, hipMemcpyAsync(root, b->d_dig.p + lv.off[lv.nlevels - 1] * 4, 32, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipStreamSynchronize(s));
+  const int rc = log_error_word(b, "qp_ballot_box_commit_log", err);
+  if (rc) return rc;
+  memcpy(b->log_root, root, 32);
+  b->lv = lv;
+  b->committed = b->count;
+  return QP_OK;
+}
+
+// commit on either path; the caller checked that the log is not empty
+int commit_log(qp_ballot_box *b) {
+  if (b->ctx) return commit_device(b);
+  if (!b->hlog.commit(b->host)) return log_error_word(b, "qp_ballot_box_commit_log", 4);
+  memcpy(b->log_root, b->hlog.root(), 32);
+  b->committed = b->hlog.committed;
+  return QP_OK;
+}
+
+int receipts_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
+                    uint32_t *depth, uint64_t *leaves) {
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  const int rc = log_batch_buffers(b);
+  if (rc) return rc;
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(LOG_BATCH, k - done);
+    QP_HIP_TRY(b, hipMemcpyAsync(b->d_q.p, seqs + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+    qpk::registry_paths(b->d_dig.p, b->lv, b->d_q.p, nb, b->d_sib.p, b->d_bits.as<uint32_t>(),
+                        b->d_depth.as<uint32_t>(), leaves ? b->d_leaf.p : nullptr, s);
+    QP_HIP_TRY(b, hipGetLastError());
+    QP_HIP_TRY(b, hipMemcpyAsync(siblings + (size_t)done * qpk::REG_PATH_SLOTS * 4, b->d_sib.p,
+                                 (size_t)nb * qpk::REG_PATH_SLOTS * 32, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipMemcpyAsync(path_bits + done, b->d_bits.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipMemcpyAsync(depth + done, b->d_depth.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    if (leaves)
+      QP_HIP_TRY(b, hipMemcpyAsync(leaves + (size_t)done * 4, b->d_leaf.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipStreamSynchronize(s));
+    done += nb;
+  }
+  return QP_OK;
+}
+
+int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
+                      uint8_t *flags) {
+  qp_ctx *c = b->ctx;
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(b, hipSetDevice(c->device));
+  const int rc = log_batch_buffers(b);
+  if (rc) return rc;
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(LOG_BATCH, k - done);
+    QP_HIP_TRY(b, hipMemcpyAsync(b->d_q.p, seqs + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+    qpk::ballot_gather(b->t.dev(), b->d_q.p, nb, b->d_leaf.p, b->d_seq.p, b->d_flag.as<uint8_t>(), s);
+    QP_HIP_TRY(b, hipGetLastError());
+    if (nullifiers)
+      QP_HIP_TRY(b, hipMemcpyAsync(nullifiers + (size_t)done * 4, b->d_leaf.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    if (numbers) QP_HIP_TRY(b, hipMemcpyAsync(numbers + done, b->d_seq.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+    if (flags) QP_HIP_TRY(b, hipMemcpyAsync(flags + done, b->d_flag.p, nb, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(b, hipStreamSynchronize(s));
+    done += nb;
+  }
+  return QP_OK;
+}
+
+// a failed device step of the log's calls leaves the box dead, as a failed cast does
+int device_step(qp_ballot_box *b, int rc) {
+  if (rc) b->dead = true;
+  return rc;
+}
+
+// seqs[k] all inside the log, or QP_ERR_ARG naming the first that is not
+int check_seqs(qp_ballot_box *b, const char *fn, const uint64_t *seqs, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++)
+    if (seqs[i] >= b->admitted()) {
+      b->err = std::string(fn) + ": entry " + std::to_string(seqs[i]) + " (position " + std::to_string(i) +
+               ") is outside the log's " + std::to_string(b->admitted());
+      return QP_ERR_ARG;
+    }
+  return QP_OK;
+}
+
+int empty_log(qp_ballot_box *b, const char *fn) {
+  b->err = std::string(fn) + ": empty log (no ballot has been admitted yet)";
+  return QP_ERR_STATE;
 }
 }  // namespace
 
@@ -296,6 +470,8 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
     } catch (const std::bad_alloc &) {
       return bad_alloc(b, "qp_ballot_box_reserve");
     }
+    b->hlog.drop();  // the log tree's layout is the capacity's: the next commit rebuilds it
+    b->committed = 0;
     return QP_OK;
   }
   // a new log and table beside the old; the box moves over only once all of it succeeded
@@ -332,6 +508,10 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
   std::swap(b->t.slot.words, nt.slot.words);
   b->t.mask = nt.mask;
   b->capacity = new_capacity;
+  // the log tree's layout is the capacity's: dropped here, rebuilt by the next
+  // commit from the copied log, which gives the same root
+  b->d_dig.release();
+  b->committed = 0;
   return QP_OK;
 }
 
@@ -391,6 +571,100 @@ int qp_ballot_box_recount(qp_ballot_box *b, uint64_t out[4]) {
   QP_HIP_TRY(b, hipMemcpyAsync(out, b->d_audit.p, 32, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipStreamSynchronize(s));
   return QP_OK;
+}
+
+int qp_ballot_box_find(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_find");
+  if (!k) return QP_OK;
+  if (!nullifiers || !seq_out) {
+    b->err = "qp_ballot_box_find: null buffer";
+    return QP_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < k; i++)
+    for (uint32_t f = 0; f < 4; f++)
+      if (nullifiers[(size_t)i * 4 + f] >= qb::P) {
+        b->err = "qp_ballot_box_find: nullifier at position " + std::to_string(i) + " felt " + std::to_string(f) +
+                 " is not a canonical field element";
+        return QP_ERR_ARG;
+      }
+  if (!b->ctx) {
+    for (uint32_t i = 0; i < k; i++) seq_out[i] = qb::find(b->host, nullifiers + (size_t)i * 4);
+    return QP_OK;
+  }
+  try {
+    return device_step(b, find_device(b, nullifiers, k, seq_out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_find");
+  }
+}
+
+int qp_ballot_box_commit_log(qp_ballot_box *b, uint64_t root_out[4], uint64_t *n_out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_commit_log");
+  if (!b->admitted()) return empty_log(b, "qp_ballot_box_commit_log");
+  try {
+    const int rc = device_step(b, commit_log(b));
+    if (rc) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_commit_log");
+  }
+  if (root_out) memcpy(root_out, b->log_root, 32);
+  if (n_out) *n_out = b->committed;
+  return QP_OK;
+}
+
+int qp_ballot_box_receipts(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
+                           uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_receipts");
+  if (!b->admitted()) return empty_log(b, "qp_ballot_box_receipts");
+  if (k && (!seqs || !siblings || !path_bits || !depth)) {
+    b->err = "qp_ballot_box_receipts: null buffer";
+    return QP_ERR_ARG;
+  }
+  int rc = check_seqs(b, "qp_ballot_box_receipts", seqs, k);
+  if (rc) return rc;
+  try {
+    if ((rc = device_step(b, commit_log(b)))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_receipts");
+  }
+  if (root_out) memcpy(root_out, b->log_root, 32);
+  if (n_out) *n_out = b->committed;
+  if (!k) return QP_OK;
+  if (b->ctx) return device_step(b, receipts_device(b, seqs, k, siblings, path_bits, depth, leaves));
+  for (uint32_t i = 0; i < k; i++)
+    b->hlog.path(seqs[i], siblings + (size_t)i * qb::PATH_SLOTS * 4, path_bits + i, depth + i,
+                 leaves ? leaves + (size_t)i * 4 : nullptr);
+  return QP_OK;
+}
+
+int qp_ballot_box_entries_at(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers,
+                             uint64_t *numbers, uint8_t *flags) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_entries_at");
+  if (!k) return QP_OK;
+  if (!seqs) {
+    b->err = "qp_ballot_box_entries_at: null buffer";
+    return QP_ERR_ARG;
+  }
+  const int rc = check_seqs(b, "qp_ballot_box_entries_at", seqs, k);
+  if (rc) return rc;
+  if (b->ctx) return device_step(b, entries_at_device(b, seqs, k, nullifiers, numbers, flags));
+  for (uint32_t i = 0; i < k; i++) {
+    if (nullifiers) memcpy(nullifiers + (size_t)i * 4, &b->host.nullifier[seqs[i] * 4], 32);
+    if (numbers) numbers[i] = b->host.number[seqs[i]];
+    if (flags) flags[i] = b->host.flags[seqs[i]];
+  }
+  return QP_OK;
+}
+
+int qp_ballot_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],
+                            uint64_t number, uint8_t flags, const uint64_t *siblings, uint32_t path_bits,
+                            uint32_t depth) {
+  if (!root || !nullifier || !siblings) return QP_RECEIPT_NULL;
+  return qb::receipt_check(root, n, seq, nullifier, number, flags, siblings, path_bits, depth);
 }
 
 int qp_ballot_box_cast_times(const qp_ballot_box *b, double ms[2]) {

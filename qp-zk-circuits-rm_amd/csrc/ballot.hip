@@ -1,8 +1,10 @@
 // ballot.hip — the ballot box's nullifier table and tally (gfx950).  Layout
 // and the home-slot rule: ballot_kernels.h.  Memory-latency-bound: a lane does
 // one or a few dependent slot atomics and 32-byte key reads; no arithmetic to
-// speak of.
+// speak of.  The log commitment's leaf kernel is the exception: VALU-bound, one
+// permutation per lane (merkle_node.h), like registry.hip's.
 #include "ballot_kernels.h"
+#include "merkle_node.h"
 
 namespace qpk {
 
@@ -35,6 +37,12 @@ constexpr uint8_t BALLOT_VOTE = 1, BALLOT_COUNTED = 2;
 //    slot exists and the loop ends at it at the latest.  The loop is bounded by
 //    S all the same; running out cannot be reached and is reported through the
 //    error word, after which the box refuses further casts.
+// 4. The lookup (k_ballot_find) takes no atomics and writes no slot.  It runs
+//    on the box's stream in a launch of its own after every insert, resolve
+//    and rebuild has completed, and nothing runs beside it: the slot words and
+//    the log it reads were final before it started, and a kernel boundary on
+//    one stream makes them visible to plain loads on every XCD.  Nothing is
+//    ever removed, so a chain has no gap and an empty slot ends it.
 __device__ __forceinline__ uint32_t ballot_probe(const BallotDev &d, uint32_t seq, uint32_t limit) {
   const uint64_t *key = d.nullifier + (uint64_t)seq * 4;
   const uint64_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3];
@@ -136,6 +144,75 @@ __global__ void __launch_bounds__(256) k_ballot_recount(const uint8_t *__restric
   block_count(pred, dst);
 }
 
+// ---- the log commitment (ballot_kernels.h): leaves, lookup, gather
+
+// log leaf seq = hash_no_pad([nullifier[0..4], number, flags]) into level 0 of
+// the digest buffer: one lane per entry of [first, end), the registry leaf
+// kernel's permutation form.  A number >= p cannot be reached (numbers count
+// ballots); it is not hashed and sets the error word.
+__global__ void __launch_bounds__(256) k_ballot_leaves(BallotDev d, uint32_t first, uint32_t end,
+                                                       uint64_t *__restrict__ dig, uint32_t *__restrict__ err) {
+  const uint64_t seq = (uint64_t)first + blockIdx.x * blockDim.x + threadIdx.x;
+  if (seq >= end) return;
+  const uint64_t *key = d.nullifier + seq * 4;
+  uint64_t s[12];
+#pragma unroll
+  for (int j = 0; j < 4; j++) s[j] = key[j];
+  s[4] = d.number[seq];
+  s[5] = d.flags[seq];
+  s[6] = s[7] = 0;
+  if (s[4] >= 0xFFFFFFFF00000001ull) {
+    atomicOr(err, 4u);
+    return;
+  }
+  node_digest(s);
+  uint64_t *o = dig + seq * 4;
+#pragma unroll
+  for (int j = 0; j < 4; j++) o[j] = s[j];
+}
+
+// one lane per queried nullifier q[i][4]: the read-only probe (fact 4).
+// seq_out[i] = the log index of the counted entry with that nullifier, or
+// 0xFFFFFFFF.  count: the log's entries; a slot word at or beyond it is not a
+// log entry (cannot be reached): nothing is read through it, the error word is set.
+__global__ void __launch_bounds__(256) k_ballot_find(BallotDev d, uint32_t count, const uint64_t *__restrict__ q,
+                                                     uint32_t k, uint32_t *__restrict__ seq_out,
+                                                     uint32_t *__restrict__ err) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const uint64_t *key = q + (uint64_t)i * 4;
+  const uint64_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3];
+  uint32_t found = BALLOT_EMPTY;
+  uint64_t at = k0 & d.mask;
+  for (uint64_t tried = 0; tried <= d.mask; tried++, at = (at + 1) & d.mask) {
+    const uint32_t cur = d.slot[at];
+    if (cur == BALLOT_EMPTY) break;
+    if (cur >= count) {
+      atomicOr(err, 8u);
+      break;
+    }
+    const uint64_t *o = d.nullifier + (uint64_t)cur * 4;
+    if (o[0] == k0 && o[1] == k1 && o[2] == k2 && o[3] == k3) {
+      found = cur;
+      break;
+    }
+  }
+  seq_out[i] = found;
+}
+
+// log entries seq[i] < count (the caller checks) into dense arrays: one lane per entry
+__global__ void __launch_bounds__(256) k_ballot_gather(BallotDev d, const uint64_t *__restrict__ seq, uint32_t k,
+                                                       uint64_t *__restrict__ nullifier, uint64_t *__restrict__ number,
+                                                       uint8_t *__restrict__ flags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const uint64_t at = seq[i];
+#pragma unroll
+  for (int j = 0; j < 4; j++) nullifier[(uint64_t)i * 4 + j] = d.nullifier[at * 4 + j];
+  number[i] = d.number[at];
+  flags[i] = d.flags[at];
+}
+
 static unsigned ballot_blocks(uint32_t n) { return (unsigned)(((uint64_t)n + 255) / 256); }
 
 void ballot_insert(const BallotDev &d, uint32_t first_seq, uint32_t k, uint32_t *stay, BallotCounters *ctr,
@@ -158,6 +235,24 @@ void ballot_rebuild(const BallotDev &d, uint32_t count, BallotCounters *ctr, hip
 void ballot_recount(const uint8_t *flags, uint32_t count, unsigned long long *out, hipStream_t s) {
   if (!count) return;
   k_ballot_recount<<<ballot_blocks(count), 256, 0, s>>>(flags, count, out);
+}
+
+void ballot_leaves(const BallotDev &d, uint32_t first, uint32_t end, uint64_t *dig, BallotCounters *ctr,
+                   hipStream_t s) {
+  if (first >= end) return;
+  k_ballot_leaves<<<ballot_blocks(end - first), 256, 0, s>>>(d, first, end, dig, &ctr->err);
+}
+
+void ballot_find(const BallotDev &d, uint32_t count, const uint64_t *q, uint32_t k, uint32_t *seq_out,
+                 BallotCounters *ctr, hipStream_t s) {
+  if (!k) return;
+  k_ballot_find<<<ballot_blocks(k), 256, 0, s>>>(d, count, q, k, seq_out, &ctr->err);
+}
+
+void ballot_gather(const BallotDev &d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
+                   uint8_t *flags, hipStream_t s) {
+  if (!k) return;
+  k_ballot_gather<<<ballot_blocks(k), 256, 0, s>>>(d, seq, k, nullifier, number, flags);
 }
 
 }  // namespace qpk

@@ -10,6 +10,12 @@
 //   HOME SLOT = nullifier[0] & (S - 1)
 // (ballot_table.h states the same rule for the host path; the tests craft
 // colliding nullifiers from it.)
+//
+// The log commitment (ballot_log.h has the definitions): the log tree's digest
+// buffer is the registry's reserved layout for the box's capacity
+// (registry_layout.h).  k_ballot_leaves writes its level 0; the levels above
+// and the paths are qpk::registry_append and qpk::registry_paths
+// (registry_kernels.h), as the registry calls them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +41,11 @@ __global__ void k_ballot_resolve(BallotDev d, uint32_t first_seq, uint32_t k, co
                                  BallotCounters *ctr);
 __global__ void k_ballot_rebuild(BallotDev d, uint32_t count, uint32_t *err);
 __global__ void k_ballot_recount(const uint8_t *flags, uint32_t count, unsigned long long *out);
+__global__ void k_ballot_leaves(BallotDev d, uint32_t first, uint32_t end, uint64_t *dig, uint32_t *err);
+__global__ void k_ballot_find(BallotDev d, uint32_t count, const uint64_t *q, uint32_t k, uint32_t *seq_out,
+                              uint32_t *err);
+__global__ void k_ballot_gather(BallotDev d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
+                                uint8_t *flags);
 
 // log entries [first_seq, first_seq + k) (already uploaded) into the table;
 // stay[i] = the slot entry first_seq + i stopped at.  The caller keeps
@@ -50,5 +61,15 @@ void ballot_resolve(const BallotDev &d, uint32_t first_seq, uint32_t k, const ui
 void ballot_rebuild(const BallotDev &d, uint32_t count, BallotCounters *ctr, hipStream_t s);
 // out[4] (zeroed by the caller) += yes, no, counted, admitted of flags [0, count)
 void ballot_recount(const uint8_t *flags, uint32_t count, unsigned long long *out, hipStream_t s);
+// the log leaves of entries [first, end) into dig[seq][4] (level 0 of the log tree); end <= C
+void ballot_leaves(const BallotDev &d, uint32_t first, uint32_t end, uint64_t *dig, BallotCounters *ctr,
+                   hipStream_t s);
+// seq_out[i] = the log index of the counted entry with nullifier q[i][4] (device), or 0xFFFFFFFF;
+// count = the log's entries.  After every insert and resolve on the same stream; read-only.
+void ballot_find(const BallotDev &d, uint32_t count, const uint64_t *q, uint32_t k, uint32_t *seq_out,
+                 BallotCounters *ctr, hipStream_t s);
+// the log entries seq[i] (device; each below the log's count, the caller checks) into dense arrays
+void ballot_gather(const BallotDev &d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
+                   uint8_t *flags, hipStream_t s);
 
 }  // namespace qpk

@@ -17,11 +17,12 @@ from .aggregator import (AggregatedProof, CircuitData, TreeAggregationConfig, Wo
                          aggregate_chunk, aggregate_level, aggregate_to_tree)
 from .verifier import WormholeVerifier, merkle_verify  # noqa: F401,E402
 from .registry import VoterRegistry  # noqa: F401,E402
-from .ballot import BALLOT_STATUS_TEXT, BallotBox, BallotResult  # noqa: F401,E402
+from .ballot import BALLOT_STATUS_TEXT, BallotBox, BallotReceipt, BallotResult  # noqa: F401,E402
 
 __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorageProof", "PublicCircuitInputs",
            "Witness", "VoteCircuitData", "VotePrivateInputs", "VotePublicInputs", "Prover", "ProofWithPublicInputs", "WormholeProver", "Context", "PolynomialBatch", "QpError", "ifft", "lde", "poseidon_permute", "lib", "header_symbols",
            "generate_circuit_binaries", "prover_only_bytes", "AggregatedProof", "CircuitData", "TreeAggregationConfig",
            "WormholeProofAggregator", "aggregate_chunk", "aggregate_level", "aggregate_to_tree", "GateDesc", "gate_desc", "quotient", "FriLayer", "fri_fold", "pow_grind",
            "PermutationData", "opening_set", "fri_initial_poly",
-           "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BALLOT_STATUS_TEXT"]
+           "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BallotReceipt",
+           "BALLOT_STATUS_TEXT"]

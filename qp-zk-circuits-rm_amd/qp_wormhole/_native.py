@@ -173,6 +173,13 @@ def lib():
         "qp_ballot_box_entries": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP]),
         "qp_ballot_box_recount": (ctypes.c_int, [VP, U64P]),
         "qp_ballot_box_cast_times": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double)]),
+        "qp_ballot_box_find": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP]),
+        "qp_ballot_box_commit_log": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_receipts": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP, VP, VP, VP,
+                                                  ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_entries_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP, VP]),
+        "qp_ballot_receipt_check": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, ctypes.c_uint64,
+                                                   ctypes.c_uint8, VP, ctypes.c_uint32, ctypes.c_uint32]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

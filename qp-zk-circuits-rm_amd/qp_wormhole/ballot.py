@@ -35,7 +35,13 @@ BALLOT_STATUS_TEXT = ("counted", "proof rejected", "malformed public inputs", "w
                       "bad vote", "double vote")
 FLAG_VOTE, FLAG_COUNTED = 1, 2
 
+PATH_SLOTS = 32             # sibling slots of a receipt's path (the registry's REG_PATH_SLOTS)
+NOT_FOUND = 2**64 - 1       # qp_ballot_box_find: the nullifier was never admitted
+
 BallotResult = namedtuple("BallotResult", "status verify_status number first")
+# one log entry tied to a published commitment (root, n): siblings are the `depth` digests of the
+# levels where the entry's node was hashed, from the leaf up; path_bits bit j = side of sibling j
+BallotReceipt = namedtuple("BallotReceipt", "nullifier number vote counted seq siblings path_bits depth root n")
 # qp_ballot_result
 RESULT_DTYPE = np.dtype([("status", np.uint32), ("verify_status", np.uint32), ("number", np.uint64),
                          ("first", np.uint64)])
@@ -191,6 +197,87 @@ class BallotBox:
         out = np.zeros(4, np.uint64)
         self._check(lib().qp_ballot_box_recount(self.h, out))
         return tuple(int(x) for x in out)
+
+    # ---- the log commitment: what the operator publishes, and the voters' receipts
+    def find(self, nullifiers, raw=False):
+        """Per nullifier (4 canonical felts each; a [k][4] uint64 array, or rows of
+        ints) the log index `seq` of its *counted* entry, or None if it was never
+        admitted (raw=True: a uint64 array, NOT_FOUND for those).  A double vote's
+        nullifier gives the counted entry, not the double's own."""
+        if isinstance(nullifiers, np.ndarray) and nullifiers.dtype == np.uint64 and nullifiers.ndim == 2 \
+                and nullifiers.shape[1] == 4:
+            q = np.ascontiguousarray(nullifiers)
+        else:
+            rows = [[int(x) for x in n] for n in nullifiers]
+            for i, r in enumerate(rows):
+                if len(r) != 4 or any(not 0 <= x < 2**64 for x in r):
+                    raise ValueError(f"nullifier at position {i} must be 4 field elements")
+            q = np.array(rows, dtype=np.uint64).reshape(len(rows), 4)
+        out = np.zeros(len(q), np.uint64)
+        self._check(lib().qp_ballot_box_find(self.h, q.ctypes.data, len(q), out.ctypes.data))
+        return out if raw else [None if int(s) == NOT_FOUND else int(s) for s in out]
+
+    def commit_log(self):
+        """(root, n): the commitment to log entries [0, n), n = admitted.  Brings the
+        log tree up to date (only the new entries are hashed); refused on an empty log."""
+        root, n = np.zeros(4, np.uint64), ctypes.c_uint64()
+        self._check(lib().qp_ballot_box_commit_log(self.h, root.ctypes.data, ctypes.byref(n)))
+        return [int(x) for x in root], n.value
+
+    @property
+    def log_root(self):
+        return self.commit_log()[0]
+
+    @property
+    def log_size(self):
+        return self.commit_log()[1]
+
+    def receipts(self, seqs):
+        """One BallotReceipt per log index in `seqs`, all under one (root, n): the
+        commitment after this call's own commit."""
+        s = np.array([int(x) for x in seqs], dtype=np.uint64).reshape(-1)
+        k = len(s)
+        sib = np.zeros((k, PATH_SLOTS, 4), np.uint64)
+        bits, depth = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        root, n = np.zeros(4, np.uint64), ctypes.c_uint64()
+        self._check(lib().qp_ballot_box_receipts(self.h, s.ctypes.data, k, sib.ctypes.data, bits.ctypes.data,
+                                                 depth.ctypes.data, None, root.ctypes.data, ctypes.byref(n)))
+        nul, num, fl = np.zeros((k, 4), np.uint64), np.zeros(k, np.uint64), np.zeros(k, np.uint8)
+        self._check(lib().qp_ballot_box_entries_at(self.h, s.ctypes.data, k, nul.ctypes.data, num.ctypes.data,
+                                                   fl.ctypes.data))
+        root = [int(x) for x in root]
+        return [BallotReceipt([int(x) for x in nul[i]], int(num[i]), bool(fl[i] & FLAG_VOTE),
+                              bool(fl[i] & FLAG_COUNTED), int(s[i]), sib[i, :depth[i]].tolist(), int(bits[i]),
+                              int(depth[i]), root, n.value) for i in range(k)]
+
+    def receipt_for(self, nullifier):
+        """The receipt of the counted entry with this nullifier; None if it was never admitted."""
+        seq = self.find([nullifier])[0]
+        return None if seq is None else self.receipts([seq])[0]
+
+    @staticmethod
+    def check_receipt(r, root=None, n=None):
+        """True iff receipt `r` holds under the published commitment (root, n), which
+        default to the pair the receipt names.  A receipt is valid only under the
+        (root, n) it was made under.  Needs no box and no device."""
+        root = r.root if root is None else root
+        n = r.n if n is None else n
+        try:
+            sib = np.zeros((PATH_SLOTS, 4), np.uint64)
+            if r.siblings:
+                sib[:len(r.siblings)] = np.array([[int(x) for x in d] for d in r.siblings], dtype=np.uint64)
+            flags = (FLAG_VOTE if r.vote else 0) | (FLAG_COUNTED if r.counted else 0)
+            rt = np.array([int(x) for x in root], dtype=np.uint64)
+            nul = np.array([int(x) for x in r.nullifier], dtype=np.uint64)
+            if rt.shape != (4,) or nul.shape != (4,):
+                return False
+            for v, bound in ((n, 2**64), (r.seq, 2**64), (r.number, 2**64), (r.path_bits, 2**32), (r.depth, 2**32)):
+                if not 0 <= int(v) < bound:
+                    return False
+        except (OverflowError, ValueError, TypeError, IndexError):
+            return False  # a value that fits no field of a receipt
+        return lib().qp_ballot_receipt_check(rt.ctypes.data, int(n), int(r.seq), nul.ctypes.data, int(r.number), flags,
+                                             sib.ctypes.data, int(r.path_bits), int(r.depth)) == 0
 
     def cast_times(self):
         """Device times of the last cast that admitted a ballot (ms): log upload, insert + resolve."""

@@ -10,18 +10,29 @@ table of csrc/ballot_table.h) on the same stream in the same process; there is
 no earlier device counter to compare with.  The results of the two paths are
 compared as well.
 
-Last, `cast` of 1024 real voting proofs beside `verify_batch` alone on the same
+Then `cast` of 1024 real voting proofs beside `verify_batch` alone on the same
 proofs: what the box adds to verification.
+
+The log commitment, on a box of N distinct entries at capacity 2 N, device and
+host path side by side: `commit_log` from empty, `commit_log` after one more
+batch of 1024 and one of 65536, `find` of 1024 and of 65536 nullifiers (half of
+them absent), `receipts` of 1024 entries.
+
+Last, with --parent-lib FILE, one A/B of the path this work must not disturb:
+`cast_public`, distinct, 16 x 65536, in a fresh process per library (plain
+ctypes on the entry points both libraries have), 7 runs each; the new median
+should lie inside the parent's own min-max.
 
 Writes one JSON object (default profiles/ballot_bench.json) stamped with the
 library hash (tools/libhash.py).  Needs an MI355X: without a device it fails.
 
-  python tools/ballot_bench.py [--log-n 20] [--reps 7] [--proofs 1024] [--out FILE]
+  python tools/ballot_bench.py [--log-n 20] [--reps 7] [--proofs 1024] [--parent-lib FILE] [--out FILE]
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -77,13 +88,89 @@ def cast_stream(BallotBox, ctx, pis, capacity, batch, reps):
     return rec, last
 
 
+def log_commitment(BallotBox, ctx, rng, n, reps):
+    """the log-commitment figures on one path: wall medians over `reps` fresh boxes of n distinct entries"""
+    pis = make_stream(rng, n + 1024 + 65536, 0)
+    absent = rng.integers(0, P, size=(65536, 4), dtype=np.uint64)
+    t = {k: [] for k in ("commit_from_empty", "commit_after_1024", "commit_after_65536", "find_1024", "find_65536",
+                         "receipts_1024")}
+    last = None
+    for _ in range(reps):
+        box = BallotBox(ctx, PROPOSAL, [ROOT_DIGEST], capacity=2 * n)
+        box.cast_public(pis[:n], reserve=False, raw=True)
+
+        def timed(key, fn):
+            t0 = time.perf_counter()
+            out = fn()
+            t[key].append(time.perf_counter() - t0)
+            return out
+        roots = [timed("commit_from_empty", box.commit_log)]
+        box.cast_public(pis[n:n + 1024], reserve=False, raw=True)
+        roots.append(timed("commit_after_1024", box.commit_log))
+        box.cast_public(pis[n + 1024:], reserve=False, raw=True)
+        roots.append(timed("commit_after_65536", box.commit_log))
+        finds, qrng = [], np.random.default_rng(3)  # the same queries in every run and on both paths
+        for k in (1024, 65536):
+            q = np.ascontiguousarray(pis[qrng.integers(0, n, k), 9:13])
+            q[1::2] = absent[:k // 2]
+            finds.append((q, timed("find_%d" % k, lambda: box.find(q, raw=True))))
+        seqs = qrng.integers(0, n, 1024)
+        rs = timed("receipts_1024", lambda: box.receipts(seqs))
+        assert all(BallotBox.check_receipt(r) for r in rs[:8])
+        last = (roots, finds, [tuple(r) for r in rs[:8]], seqs)
+        box.free()
+    return {k: _stats(v) for k, v in t.items()}, last
+
+
+def ab_cast_child(lib_path, log_n, reps):
+    """the A/B's child: cast_public, distinct, 16 batches, through plain ctypes on `lib_path`"""
+    import ctypes
+    L = ctypes.CDLL(lib_path)
+    VP = ctypes.c_void_p
+    L.qp_ctx_create.argtypes = [ctypes.c_int, ctypes.POINTER(VP)]
+    L.qp_ctx_destroy.argtypes = [VP]
+    L.qp_ctx_destroy.restype = None
+    L.qp_ballot_box_new.argtypes = [VP, VP, VP, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(VP)]
+    L.qp_ballot_box_cast_public.argtypes = [VP, VP, VP, ctypes.c_uint32, VP]
+    L.qp_ballot_box_tally.argtypes = [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.qp_ballot_box_free.argtypes = [VP]
+    L.qp_ballot_box_free.restype = None
+    n = 1 << log_n
+    batch = n // 16
+    pis = make_stream(np.random.default_rng(1), n, 0)
+    prop, root = np.array(PROPOSAL, np.uint64), np.array(ROOT_DIGEST, np.uint64)
+    out = np.zeros((batch, 3), np.uint64)  # qp_ballot_result: 24 bytes
+    ctx = VP()
+    assert L.qp_ctx_create(0, ctypes.byref(ctx)) == 0
+    wall, tally = [], None
+    for _ in range(reps + 1):  # the first run is the warm-up
+        box = VP()
+        assert L.qp_ballot_box_new(ctx, prop.ctypes.data, root.ctypes.data, 1, 2 * n, ctypes.byref(box)) == 0
+        t0 = time.perf_counter()
+        for at in range(0, n, batch):
+            assert L.qp_ballot_box_cast_public(box, pis[at:at + batch].ctypes.data, None, batch, out.ctypes.data) == 0
+        wall.append(time.perf_counter() - t0)
+        y, no = ctypes.c_uint64(), ctypes.c_uint64()
+        L.qp_ballot_box_tally(box, ctypes.byref(y), ctypes.byref(no))
+        tally = [y.value, no.value]
+        L.qp_ballot_box_free(box)
+    L.qp_ctx_destroy(ctx)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from libhash import lib_sha16
+    print(json.dumps({"lib_sha16": lib_sha16(lib_path), "wall_s": _stats(wall[1:]), "runs_s": wall[1:], "tally": tally}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--proofs", type=int, default=1024, help="real voting proofs of the cast / verify_batch pair (0 = skip)")
+    ap.add_argument("--parent-lib", help="the parent commit's libqpgpu.so: A/B of cast_public, distinct, 16 batches")
+    ap.add_argument("--ab-cast-child", help=argparse.SUPPRESS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ballot_bench.json"))
     args = ap.parse_args()
+    if args.ab_cast_child:
+        return ab_cast_child(args.ab_cast_child, args.log_n, args.reps)
 
     import qp_wormhole
     from qp_wormhole import BallotBox
@@ -162,7 +249,35 @@ def main():
         reg.free()
         prover.free()
         circ.free()
+    # the log commitment, device beside host (the host path hashes 2 n permutations on one thread: three runs)
+    dev, dlast = log_commitment(BallotBox, ctx, np.random.default_rng(2), n, args.reps)
+    host, hlast = log_commitment(BallotBox, None, np.random.default_rng(2), n, min(args.reps, 3))
+    assert dlast[0] == hlast[0] and dlast[2] == hlast[2], "device and host commitments disagree"
+    assert all((a[1] == b[1]).all() for a, b in zip(dlast[1], hlast[1])), "device and host find disagree"
+    out["log_commitment"] = {
+        "entries": n, "capacity": cap, "log_root": dlast[0][0][0], "results_equal": True,
+        "what": "wall of one call each on a fresh box of `entries` distinct ballots; find: half of the queries absent; "
+                "receipts: 1024 random entries, BallotReceipt objects included; host: the same library with ctx None",
+        "device": dev, "host": host,
+        "device_wall_over_host_wall": {k: dev[k]["median"] / host[k]["median"] for k in dev}}
     ctx.close()
+    out["ab_cast_public_16x65536"] = "not measured"
+    if args.parent_lib:
+        # two rounds, the order swapped in the second: the process that runs first in a pair is not always the same library
+        rounds = []
+        for order in (("parent", "this"), ("this", "parent")):
+            ab = {"order": list(order)}
+            for label in order:
+                path = args.parent_lib if label == "parent" else LIB_PATH
+                res = subprocess.run([sys.executable, os.path.abspath(__file__), "--ab-cast-child", path, "--log-n",
+                                      str(args.log_n), "--reps", "7"], check=True, capture_output=True, text=True,
+                                     timeout=600)
+                ab[label] = json.loads(res.stdout.strip().splitlines()[-1])
+            lo, hi = ab["parent"]["wall_s"]["min"], ab["parent"]["wall_s"]["max"]
+            ab["this_median_inside_parent_range"] = bool(lo <= ab["this"]["wall_s"]["median"] <= hi)
+            rounds.append(ab)
+        out["ab_cast_public_16x65536"] = {
+            "what": "cast_public, distinct, 16 batches, fresh process per library, 7 runs after one warm-up", "rounds": rounds}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
