@@ -13,11 +13,11 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include "acc_tree.h"
 #include "ballot_kernels.h"
 #include "ballot_log.h"
 #include "ballot_table.h"
 #include "ctx.h"
-#include "registry_kernels.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_ballot_result) == sizeof(qb::Result) && sizeof(qb::Result) == 24, "qp_ballot_result layout");
@@ -55,19 +55,14 @@ struct qp_ballot_box {
   DeviceTables t;
   DevBuf d_stay, d_first, d_ctr, d_audit;  // per batch: slot stayed at [k] (u32), first [k]; counters; recount's four
   std::vector<uint64_t> h_first;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // upload start, upload end, resolve end of the last cast
+  TimingEvents<3> ev;  // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
   // ---- the log commitment, both paths: built by the first commit, dropped by reserve
   qb::HostLog hlog;
-  DevBuf d_dig;                // the log tree, registry_reserved(capacity) digests
-  qpk::RegistryLevels lv;      // its table at `committed` leaves
-  uint64_t committed = 0;      // leaves of the tree = the n of (log_root, n)
+  AccTree log;             // the device path's log tree, laid out for `capacity`; `committed` leaves
+  uint64_t committed = 0;  // leaves of the tree = the n of (log_root, n)
   uint64_t log_root[4] = {0, 0, 0, 0};
-  DevBuf d_q, d_seq, d_sib, d_bits, d_depth, d_leaf, d_flag;  // per find / receipts batch (LOG_BATCH entries)
-  ~qp_ballot_box() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  DevBuf d_q, d_seq, d_nul, d_flag;  // per find / entries_at batch (LOG_BATCH entries)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
 };
@@ -104,7 +99,7 @@ int cast_device(qp_ballot_box *b, qb::Result *out) {
   const uint32_t k = (uint32_t)pk.size();
   hipStream_t s = c->stream;
   QP_HIP_TRY(b, hipSetDevice(c->device));
-  for (hipEvent_t &e : b->ev)
+  for (hipEvent_t &e : b->ev.e)
     if (!e) QP_HIP_TRY(b, hipEventCreate(&e));
   if (b->d_first.words < k) {
     QP_HIP_TRY(b, b->d_stay.alloc(((size_t)k + 1) / 2));
@@ -114,21 +109,21 @@ int cast_device(qp_ballot_box *b, qb::Result *out) {
   const qpk::BallotDev d = b->t.dev();
   qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
   qpk::BallotCounters now;
-  QP_HIP_TRY(b, hipEventRecord(b->ev[0], s));
+  QP_HIP_TRY(b, hipEventRecord(b->ev.e[0], s));
   QP_HIP_TRY(b, hipMemcpyAsync(d.nullifier + b->count * 4, pk.nullifier.data(), (size_t)k * 32, hipMemcpyHostToDevice, s));
   QP_HIP_TRY(b, hipMemcpyAsync(d.number + b->count, pk.number.data(), (size_t)k * 8, hipMemcpyHostToDevice, s));
   QP_HIP_TRY(b, hipMemcpyAsync(d.flags + b->count, pk.flags.data(), k, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(b, hipEventRecord(b->ev[1], s));
+  QP_HIP_TRY(b, hipEventRecord(b->ev.e[1], s));
   qpk::ballot_insert(d, (uint32_t)b->count, k, b->d_stay.as<uint32_t>(), ctr, s);
   QP_HIP_TRY(b, hipGetLastError());
   qpk::ballot_resolve(d, (uint32_t)b->count, k, b->d_stay.as<uint32_t>(), b->d_first.p, ctr, s);
   QP_HIP_TRY(b, hipGetLastError());
-  QP_HIP_TRY(b, hipEventRecord(b->ev[2], s));
+  QP_HIP_TRY(b, hipEventRecord(b->ev.e[2], s));
   QP_HIP_TRY(b, hipMemcpyAsync(b->h_first.data(), b->d_first.p, (size_t)k * 8, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipStreamSynchronize(s));
-  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[0], b->ev[0], b->ev[1]));
-  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[1], b->ev[1], b->ev[2]));
+  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[0], b->ev.e[0], b->ev.e[1]));
+  QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[1], b->ev.e[1], b->ev.e[2]));
   if (now.err) {
     b->err = "qp_ballot_box_cast: the nullifier table's probe found no slot (an internal invariant broke)";
     return QP_ERR_STATE;
@@ -172,17 +167,13 @@ int bad_alloc(qp_ballot_box *b, const char *fn) {
   return QP_ERR_OOM;
 }
 
-// entries per k_ballot_find / k_registry_paths / k_ballot_gather launch (the batch buffers hold this
-// many: 8 MB of siblings)
+// entries per k_ballot_find / k_ballot_gather launch (the batch buffers hold this many)
 constexpr uint32_t LOG_BATCH = 8192;
 
 int log_batch_buffers(qp_ballot_box *b) {
   if (b->d_q.p) return QP_OK;
   QP_HIP_TRY(b, b->d_seq.alloc(LOG_BATCH));
-  QP_HIP_TRY(b, b->d_sib.alloc((size_t)LOG_BATCH * qpk::REG_PATH_SLOTS * 4));
-  QP_HIP_TRY(b, b->d_bits.alloc(LOG_BATCH / 2));
-  QP_HIP_TRY(b, b->d_depth.alloc(LOG_BATCH / 2));
-  QP_HIP_TRY(b, b->d_leaf.alloc((size_t)LOG_BATCH * 4));
+  QP_HIP_TRY(b, b->d_nul.alloc((size_t)LOG_BATCH * 4));
   QP_HIP_TRY(b, b->d_flag.alloc(LOG_BATCH / 8));
   QP_HIP_TRY(b, b->d_q.alloc((size_t)LOG_BATCH * 4));
   return QP_OK;
@@ -228,26 +219,26 @@ int commit_device(qp_ballot_box *b) {
   hipStream_t s = c->stream;
   if (b->committed == b->count) return QP_OK;
   QP_HIP_TRY(b, hipSetDevice(c->device));
-  if (!b->d_dig.p) QP_HIP_TRY(b, b->d_dig.alloc((size_t)qpk::registry_reserved(b->capacity) * 4));
-  qpk::RegistryLevels lv;
-  if (!qpk::registry_levels_reserved(b->count, b->capacity, lv)) {
+  if (!b->log.dig.p)
+    if (int rc = b->log.alloc({b->err}, b->capacity)) return rc;
+  qpk::AccLevels lv;
+  if (!qpk::acc_levels_reserved(b->count, b->capacity, lv)) {
     b->err = "qp_ballot_box_commit_log: the log does not fit its capacity (an internal invariant broke)";
     return QP_ERR_STATE;
   }
   qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
   uint64_t root[4];
   uint32_t err = 0;
-  qpk::ballot_leaves(b->t.dev(), (uint32_t)b->committed, (uint32_t)b->count, b->d_dig.p, ctr, s);
+  qpk::ballot_leaves(b->t.dev(), (uint32_t)b->committed, (uint32_t)b->count, b->log.dig.p, ctr, s);
   QP_HIP_TRY(b, hipGetLastError());
-  qpk::registry_append(b->d_dig.p, lv, b->committed, s);
+  b->log.append(lv, qpk::acc_row_max(), s);  // the tree holds `committed` leaves
   QP_HIP_TRY(b, hipGetLastError());
-  QP_HIP_TRY(b, hipMemcpyAsync(root, b->d_dig.p + lv.off[lv.nlevels - 1] * 4, 32, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(b, hipMemcpyAsync(root, b->log.root(lv), 32, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipStreamSynchronize(s));
-  const int rc = log_error_word(b, "qp_ballot_box_commit_log", err);
-  if (rc) return rc;
+  if (int rc = log_error_word(b, "qp_ballot_box_commit_log", err)) return rc;
   memcpy(b->log_root, root, 32);
-  b->lv = lv;
+  b->log.lv = lv;
   b->committed = b->count;
   return QP_OK;
 }
@@ -257,33 +248,14 @@ int commit_log(qp_ballot_box *b) {
   if (b->ctx) return commit_device(b);
   if (!b->hlog.commit(b->host)) return log_error_word(b, "qp_ballot_box_commit_log", 4);
   memcpy(b->log_root, b->hlog.root(), 32);
-  b->committed = b->hlog.committed;
+  b->committed = b->hlog.n;
   return QP_OK;
 }
 
 int receipts_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
                     uint32_t *depth, uint64_t *leaves) {
-  qp_ctx *c = b->ctx;
-  hipStream_t s = c->stream;
-  QP_HIP_TRY(b, hipSetDevice(c->device));
-  const int rc = log_batch_buffers(b);
-  if (rc) return rc;
-  for (uint32_t done = 0; done < k;) {
-    const uint32_t nb = std::min(LOG_BATCH, k - done);
-    QP_HIP_TRY(b, hipMemcpyAsync(b->d_q.p, seqs + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-    qpk::registry_paths(b->d_dig.p, b->lv, b->d_q.p, nb, b->d_sib.p, b->d_bits.as<uint32_t>(),
-                        b->d_depth.as<uint32_t>(), leaves ? b->d_leaf.p : nullptr, s);
-    QP_HIP_TRY(b, hipGetLastError());
-    QP_HIP_TRY(b, hipMemcpyAsync(siblings + (size_t)done * qpk::REG_PATH_SLOTS * 4, b->d_sib.p,
-                                 (size_t)nb * qpk::REG_PATH_SLOTS * 32, hipMemcpyDeviceToHost, s));
-    QP_HIP_TRY(b, hipMemcpyAsync(path_bits + done, b->d_bits.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
-    QP_HIP_TRY(b, hipMemcpyAsync(depth + done, b->d_depth.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
-    if (leaves)
-      QP_HIP_TRY(b, hipMemcpyAsync(leaves + (size_t)done * 4, b->d_leaf.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
-    QP_HIP_TRY(b, hipStreamSynchronize(s));
-    done += nb;
-  }
-  return QP_OK;
+  QP_HIP_TRY(b, hipSetDevice(b->ctx->device));
+  return b->log.paths({b->err}, b->ctx->stream, seqs, k, siblings, path_bits, depth, leaves);
 }
 
 int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
@@ -296,10 +268,10 @@ int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64
   for (uint32_t done = 0; done < k;) {
     const uint32_t nb = std::min(LOG_BATCH, k - done);
     QP_HIP_TRY(b, hipMemcpyAsync(b->d_q.p, seqs + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
-    qpk::ballot_gather(b->t.dev(), b->d_q.p, nb, b->d_leaf.p, b->d_seq.p, b->d_flag.as<uint8_t>(), s);
+    qpk::ballot_gather(b->t.dev(), b->d_q.p, nb, b->d_nul.p, b->d_seq.p, b->d_flag.as<uint8_t>(), s);
     QP_HIP_TRY(b, hipGetLastError());
     if (nullifiers)
-      QP_HIP_TRY(b, hipMemcpyAsync(nullifiers + (size_t)done * 4, b->d_leaf.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+      QP_HIP_TRY(b, hipMemcpyAsync(nullifiers + (size_t)done * 4, b->d_nul.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
     if (numbers) QP_HIP_TRY(b, hipMemcpyAsync(numbers + done, b->d_seq.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
     if (flags) QP_HIP_TRY(b, hipMemcpyAsync(flags + done, b->d_flag.p, nb, hipMemcpyDeviceToHost, s));
     QP_HIP_TRY(b, hipStreamSynchronize(s));
@@ -498,19 +470,11 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
     b->err = "qp_ballot_box_reserve: the nullifier table's probe found no slot (an internal invariant broke)";
     return QP_ERR_STATE;
   }
-  std::swap(b->t.nul.p, nt.nul.p);
-  std::swap(b->t.nul.words, nt.nul.words);
-  std::swap(b->t.num.p, nt.num.p);
-  std::swap(b->t.num.words, nt.num.words);
-  std::swap(b->t.flags.p, nt.flags.p);
-  std::swap(b->t.flags.words, nt.flags.words);
-  std::swap(b->t.slot.p, nt.slot.p);
-  std::swap(b->t.slot.words, nt.slot.words);
-  b->t.mask = nt.mask;
+  b->t = std::move(nt);
   b->capacity = new_capacity;
   // the log tree's layout is the capacity's: dropped here, rebuilt by the next
   // commit from the copied log, which gives the same root
-  b->d_dig.release();
+  b->log.drop();
   b->committed = 0;
   return QP_OK;
 }

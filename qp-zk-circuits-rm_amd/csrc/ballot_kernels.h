@@ -11,11 +11,10 @@
 // (ballot_table.h states the same rule for the host path; the tests craft
 // colliding nullifiers from it.)
 //
-// The log commitment (ballot_log.h has the definitions): the log tree's digest
-// buffer is the registry's reserved layout for the box's capacity
-// (registry_layout.h).  k_ballot_leaves writes its level 0; the levels above
-// and the paths are qpk::registry_append and qpk::registry_paths
-// (registry_kernels.h), as the registry calls them.
+// The log commitment (ballot_log.h has the definitions): the log tree is an
+// accumulator tree (acc_tree.h) laid out for the box's capacity.
+// k_ballot_leaves writes its level 0; the levels above and the paths are the
+// tree's own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

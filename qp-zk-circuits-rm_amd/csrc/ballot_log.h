@@ -1,35 +1,36 @@
 // ballot_log.h — the ballot box's log commitment in host C++: the read-only
-// lookup in the host table, the log tree of the host path, path extraction, and
+// lookup in the host table, the log's leaf and node hashes, the log tree of the
+// host path (an accumulator tree, acc_layout.h's HostTree, with the log's leaf), and
 // the receipt check (host code on both paths; it needs no box and no device).
 // Included by ballot.cpp and by the stand-alone check tools/ballot_log_check.cpp.
 //
 // Definitions (DESIGN §13 and qpgpu.h state the same):
 //   log leaf of entry seq = hash_no_pad([nullifier[0..4], number, flags]): six
 //     felts, one permutation; flags is the log's byte (bit 0 vote, bit 1 counted)
-//   log tree over leaves [0, n), n = admitted, in the registry's convention
-//     (registry_kernels.h): node = hash_no_pad(left || right), the last node of
-//     an odd level moves up unchanged; laid out for the box's capacity with
-//     registry_levels_reserved, so it grows in place
+//   log tree over leaves [0, n), n = admitted: an accumulator tree
+//     (acc_layout.h): node = hash_no_pad(left || right), the last node of an odd
+//     level moves up unchanged; laid out for the box's capacity, so it grows in
+//     place
 //   commitment = (root, n)
-// The checker takes the tree's shape from (seq, n), never from the receipt: at
-// level l node j = seq >> l has a sibling iff (j ^ 1) < ceil(n / 2^l), and a
-// receipt whose depth or side bits say otherwise is rejected.  A six-felt leaf
-// hashes as the eight-felt node (nullifier || number, flags, 0, 0) would, so
-// without this a node whose right child has that form could be offered as a
-// leaf.  (depth, side bits) is the route from the root to one node of the tree,
+// The checker takes the tree's shape from (seq, n), never from the receipt
+// (qpk::path_levels: at level l node j = seq >> l has a sibling iff (j ^ 1) <
+// ceil(n / 2^l)), and a receipt whose depth or side bits say otherwise is
+// rejected.  A six-felt leaf hashes as the eight-felt node (nullifier ||
+// number, flags, 0, 0) would, so without this a node whose right child has
+// that form could be offered as a leaf.  (depth, side bits) is the route from the root to one node of the tree,
 // and the shape rule yields the routes of level-0 nodes only.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <vector>
+#include "acc_layout.h"
 #include "ballot_table.h"
 #include "poseidon.h"
-#include "registry_layout.h"
 
 namespace qb {
 
 constexpr uint64_t NOT_FOUND = ~0ull;
-constexpr uint32_t PATH_SLOTS = qpk::REG_PATH_SLOTS;
+constexpr uint32_t PATH_SLOTS = qpk::ACC_PATH_SLOTS;
 // qp_receipt_status (qpgpu.h)
 enum : int { RECEIPT_OK = 0, RECEIPT_SHAPE = 1, RECEIPT_ROOT = 2, RECEIPT_NON_CANONICAL = 3, RECEIPT_NULL = 4 };
 
@@ -64,77 +65,24 @@ inline uint64_t find(const HostBox &b, const uint64_t q[4]) {
   return NOT_FOUND;
 }
 
-// the tree's shape at entry seq of n: bit l of the result is set iff the node
-// of seq at level l is hashed with a sibling (seq < n, 1 <= n <= 2^31)
-inline uint32_t path_levels(uint64_t seq, uint64_t n) {
-  uint32_t m = 0, l = 0;
-  for (uint64_t len = n; len > 1; len = (len + 1) / 2, l++)
-    if (((seq >> l) ^ 1) < len) m |= 1u << l;
-  return m;
-}
-
-// the host path's log tree: every level resident, the registry's reserved layout
-struct HostLog {
-  uint64_t capacity = 0, committed = 0;
-  qpk::RegistryLevels lv;
-  std::vector<uint64_t> dig;  // [registry_reserved(capacity)][4], allocated by the first commit
-
-  void drop() {
-    committed = 0;
-    capacity = 0;
-    std::vector<uint64_t>().swap(dig);
-  }
-  uint64_t *node(uint32_t l, uint64_t j) { return &dig[(size_t)(lv.off[l] + j) * 4]; }
-  const uint64_t *node(uint32_t l, uint64_t j) const { return &dig[(size_t)(lv.off[l] + j) * 4]; }
-  const uint64_t *root() const { return node(lv.nlevels - 1, 0); }
-
-  // brings the tree up to the box's log: leaves [committed, count), then the
-  // nodes above that the append changes (registry_append_ranges).  false: a
-  // number >= p in the log (cannot be reached); the tree is then dropped.
+// the host path's log tree: a qpk::HostTree laid out for the box's capacity, the log's entries its leaves
+struct HostLog : qpk::HostTree {
+  // brings the tree up to the box's log: leaves [n, count), then the nodes above.  A tree laid out
+  // for another capacity (the box was reserved) is rebuilt.  false: a number >= p in the log
+  // (cannot be reached); the tree is then dropped.
   bool commit(const HostBox &b) {
-    const uint64_t n = b.count();
-    if (capacity != b.capacity) {
-      drop();
-      capacity = b.capacity;
-      dig.assign((size_t)qpk::registry_reserved(capacity) * 4, 0);
-    }
-    if (committed == n) return true;
-    qpk::registry_levels_reserved(n, capacity, lv);
-    for (uint64_t seq = committed; seq < n; seq++) {
+    const uint64_t count = b.count();
+    if (capacity != b.capacity) open(b.capacity);
+    if (n == count) return true;
+    for (uint64_t seq = n; seq < count; seq++) {
       if (b.number[seq] >= P) {
         drop();
         return false;
       }
       log_leaf(&b.nullifier[(size_t)seq * 4], b.number[seq], b.flags[seq], node(0, seq));
     }
-    qpk::RegistryRange rg[qpk::REG_MAX_LEVELS];
-    const uint32_t nl = qpk::registry_append_ranges(committed, n, rg);
-    for (uint32_t l = 1; l < nl; l++)
-      for (uint64_t j = rg[l].first; j < rg[l].end; j++) {
-        if (2 * j + 1 < lv.len[l - 1])
-          log_node(node(l - 1, 2 * j), node(l - 1, 2 * j + 1), node(l, j));
-        else
-          memcpy(node(l, j), node(l - 1, 2 * j), 32);
-      }
-    committed = n;
+    append(count, log_node);
     return true;
-  }
-
-  // entry seq < committed: siblings [PATH_SLOTS][4] compacted (zero above the
-  // depth), side bits, depth, and the leaf digest (may be null): the layout
-  // qpk::registry_paths writes
-  void path(uint64_t seq, uint64_t *siblings, uint32_t *path_bits, uint32_t *depth, uint64_t *leaf) const {
-    memset(siblings, 0, PATH_SLOTS * 32);
-    uint32_t bits = 0, d = 0;
-    for (uint32_t l = 0; l + 1 < lv.nlevels; l++) {
-      const uint64_t j = seq >> l;
-      if ((j ^ 1) >= lv.len[l]) continue;
-      memcpy(siblings + d * 4, node(l, j ^ 1), 32);
-      bits |= (uint32_t)(j & 1) << d++;
-    }
-    *path_bits = bits;
-    *depth = d;
-    if (leaf) memcpy(leaf, node(0, seq), 32);
   }
 };
 
@@ -145,8 +93,8 @@ inline int receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const
   if (!canonical(root, 4) || !canonical(nullifier, 4) || number >= P || flags > (FLAG_VOTE | FLAG_COUNTED) ||
       !canonical(siblings, PATH_SLOTS * 4))
     return RECEIPT_NON_CANONICAL;
-  if (!n || n > qpk::REG_MAX_VOTERS || seq >= n) return RECEIPT_SHAPE;
-  const uint32_t m = path_levels(seq, n);
+  if (!n || n > qpk::ACC_MAX_LEAVES || seq >= n) return RECEIPT_SHAPE;
+  const uint32_t m = qpk::path_levels(seq, n);
   uint32_t d = 0, bits = 0;
   for (uint32_t l = 0; l < 32; l++)
     if (m >> l & 1) bits |= (uint32_t)((seq >> l) & 1) << d++;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <utility>
 #include "kernels.h"
 
 struct qp_ctx {
@@ -34,6 +35,11 @@ struct DevBuf {
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
   DevBuf(DevBuf &&o) noexcept : p(o.p), words(o.words) { o.p = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept {  // a swap: o frees what this one held
+    std::swap(p, o.p);
+    std::swap(words, o.words);
+    return *this;
+  }
   hipError_t alloc(size_t w) {  // at least one word: p is non-null after a successful alloc(0)
     release();
     words = w;
@@ -51,6 +57,19 @@ struct DevBuf {
   // hipFree waits for the device, so freeing while launches on the context's
   // stream are still running is safe.
   ~DevBuf() { release(); }
+};
+
+// The HIP timing events of a handle or of one ABI call: the owner creates the
+// null ones before it records them; every return path of the owner destroys them.
+template <int N>
+struct TimingEvents {
+  hipEvent_t e[N] = {};
+  TimingEvents() = default;
+  TimingEvents(const TimingEvents &) = delete;
+  ~TimingEvents() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
 };
 
 // ctx: any handle with a std::string err (qp_ctx, qp_verifier)

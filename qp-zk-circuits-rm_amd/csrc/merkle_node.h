@@ -1,6 +1,6 @@
 // merkle_node.h — the node hash every device Merkle tree shares: the prover's
-// power-of-two trees (merkle.hip) and the voter registry's promoted-odd-node
-// trees (registry.hip).
+// power-of-two trees (merkle.hip) and the promoted-odd-node accumulator trees of the voter registry and
+// the ballot log (acc_tree.hip; their leaves in registry.hip and ballot.hip).
 #pragma once
 #include <stdint.h>
 #include "poseidon_dev.h"

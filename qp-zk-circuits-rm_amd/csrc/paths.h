@@ -17,7 +17,8 @@
 //   wit_mode=0|1      device witness: one workgroup per proof (0) / a launch per level (1)
 //   wit_row=0         cooperative witness Poseidons one per wave instead of one per row
 //   host_chain=N      host witness chains of depth >= N permutations (0 = none)
-//   registry_row=N    registry updates: the row form for dirty ranges below N nodes (0 = never)
+//   registry_row=N    updates of every accumulator tree (acc_kernels.h: the registry's, and the ballot
+//                     log's commits): the row form for dirty ranges below N nodes (0 = never)
 #pragma once
 #include <stdlib.h>
 #include <string.h>

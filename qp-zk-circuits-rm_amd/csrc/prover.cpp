@@ -1245,7 +1245,7 @@ int qp_prover_prove_voting_inputs(qp_prover *P, const qp_voting_inputs *in, uint
 }
 
 // voters of a registry: the inputs qp_prover_prove_voting_inputs takes, filled
-// from the device tree's path buffers (k_registry_paths' layout)
+// from the device tree's path buffers (k_acc_paths' layout)
 int qp_prover_prove_voters(qp_prover *P, qp_registry *r, const uint64_t *idx, const qp_vote_ballot *ballots,
                            uint32_t nproofs, uint8_t *out, size_t stride, size_t *lens) {
   if (!P || !r || !idx || !ballots || !out || !nproofs) return QP_ERR_ARG;
@@ -1263,12 +1263,12 @@ int qp_prover_prove_voters(qp_prover *P, qp_registry *r, const uint64_t *idx, co
     return QP_ERR_STATE;
   }
   try {
-    constexpr uint32_t S = qpk::REG_PATH_SLOTS;
+    constexpr uint32_t S = qpk::ACC_PATH_SLOTS;
     std::vector<uint64_t> sib((size_t)nproofs * S * 4), leaf((size_t)nproofs * 4);
     std::vector<uint32_t> bits(nproofs), depth(nproofs);
     std::vector<uint8_t> path((size_t)nproofs * S);
     std::vector<qp_voting_inputs> in(nproofs);
-    int rc = registry_paths_host(r, idx, nproofs, sib.data(), bits.data(), depth.data(), leaf.data());
+    int rc = registry_paths(r, idx, nproofs, sib.data(), bits.data(), depth.data(), leaf.data());
     if (rc) return rc;
     for (uint32_t b = 0; b < nproofs; b++) {
       qp_voting_inputs &v = in[b];

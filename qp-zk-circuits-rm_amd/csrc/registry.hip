@@ -1,33 +1,12 @@
-// registry.hip — the voter registry's eligibility tree and Merkle paths
-// (gfx950).  The tree is the reference's (voting/src/lib.rs:285-316): leaf =
-// hash_no_pad(key), node = hash_no_pad(left || right), a lone last node of an
-// odd level moves up unchanged; the paths are the ones the voting circuit
-// walks (:123-180): the siblings of the levels where the voter's node was
-// hashed, compacted, with one side bit each.
-// VALU-bound like merkle.hip: one lane per leaf / parent, one capacity-zero
+// registry.hip — level 0 of the voter registry's eligibility tree (gfx950):
+// leaf = hash_no_pad(key), the reference's (voting/src/lib.rs:285-316).  The
+// levels above and the paths are the accumulator tree's (acc_tree.hip).
+// VALU-bound like merkle.hip: one lane per leaf, one capacity-zero
 // permutation each (merkle_node.h), the state in registers.
-#include "registry_kernels.h"
+#include "registry.h"
 #include "merkle_node.h"
-#include "paths.h"
-#include "poseidon_coop.h"
 
 namespace qpk {
-
-bool registry_levels(uint64_t n, RegistryLevels &lv) {
-  if (!n) return false;
-  RegistryLevels t;
-  uint64_t o = 0;
-  for (uint64_t len = n;; len = (len + 1) / 2) {
-    if (t.nlevels == REG_MAX_LEVELS) return false;
-    t.off[t.nlevels] = o;
-    t.len[t.nlevels] = len;
-    t.nlevels++;
-    o += len;
-    if (len == 1) break;
-  }
-  lv = t;
-  return true;
-}
 
 // leaf i = hash_no_pad(key i): the four felts of a key are four coalesced
 // column loads (64 lanes x 8 B = 512 contiguous bytes each)
@@ -45,255 +24,8 @@ __global__ void __launch_bounds__(256) k_registry_leaves(const uint64_t *__restr
   for (int k = 0; k < 4; k++) o[k] = s[k];
 }
 
-// one wide level: lane t hashes nodes 2t, 2t+1 of src into node t of dst.  The
-// lone last node of an odd src is copied by lane 0 once its own hash is
-// stored (a branch around the permutation for that one lane cost every lane
-// registers: 84 and 108 VGPRs in two forms against this form's count)
-__global__ void __launch_bounds__(256) k_registry_level(const uint64_t *__restrict__ src, uint64_t nsrc,
-                                                        uint64_t *__restrict__ dst) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t npair = nsrc / 2;
-  if (t >= npair) return;
-  const uint64_t *c = src + t * 8;
-  uint64_t s[12];
-#pragma unroll
-  for (int j = 0; j < 8; j++) s[j] = c[j];
-  node_digest(s);
-  uint64_t *o = dst + t * 4;
-#pragma unroll
-  for (int j = 0; j < 4; j++) o[j] = s[j];
-  if (t == 0 && (nsrc & 1)) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) dst[npair * 4 + j] = src[(nsrc - 1) * 4 + j];
-  }
-}
-
-// every level above level l0 (at most REG_FOLD_MAX nodes) in one wave: the
-// nodes fold through LDS level by level, every level written out
-__global__ void __launch_bounds__(REG_FOLD_MAX) k_registry_fold(uint64_t *__restrict__ dig, RegistryLevels lv,
-                                                                uint32_t l0) {
-  __shared__ uint64_t sh[REG_FOLD_MAX * 4];
-  const uint32_t t = threadIdx.x;
-  if (t < lv.len[l0]) {
-    const uint64_t *c = dig + (lv.off[l0] + t) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; j++) sh[t * 4 + j] = c[j];
-  }
-  __syncthreads();
-  for (uint32_t l = l0 + 1; l < lv.nlevels; l++) {
-    const uint32_t nsrc = (uint32_t)lv.len[l - 1], ndst = (uint32_t)lv.len[l];
-    uint64_t s[12];
-    if (t < ndst) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) s[j] = sh[t * 8 + j];
-      if (2 * t + 1 < nsrc) {
-#pragma unroll
-        for (int j = 4; j < 8; j++) s[j] = sh[t * 8 + j];
-        node_digest(s);
-      }
-      uint64_t *o = dig + (lv.off[l] + t) * 4;
-#pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = s[j];
-    }
-    __syncthreads();
-    if (t < ndst) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) sh[t * 4 + j] = s[j];
-    }
-    __syncthreads();
-  }
-}
-
-// one lane per (voter of the batch, level): 32 lanes per voter, two voters per
-// wave.  Lane l marks whether the voter's node at level l was hashed (it has a
-// sibling) or promoted; the voter's half of the wave ballot is its level mask,
-// so the slot of lane l's sibling is the count of hashed levels below l.
-// Every one of the voter's 32 sibling slots is written exactly once: slots
-// below the depth by the hashed lanes, slot l >= depth (zero digest) by lane l.
-__global__ void __launch_bounds__(256) k_registry_paths(const uint64_t *__restrict__ dig, RegistryLevels lv,
-                                                        const uint64_t *__restrict__ idx, uint32_t nidx,
-                                                        uint64_t *__restrict__ siblings,
-                                                        uint32_t *__restrict__ path_bits, uint32_t *__restrict__ depth,
-                                                        uint64_t *__restrict__ leaves) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t b = g >> 5, l = g & 31;
-  const bool valid = b < nidx;
-  const uint64_t i = valid ? idx[b] : 0;
-  const uint64_t sib = (i >> l) ^ 1;
-  const bool hashed = valid && l + 1 < lv.nlevels && sib < lv.len[l];
-  const uint32_t m = (uint32_t)(__ballot(hashed) >> (threadIdx.x & 32));
-  if (!valid) return;
-  const uint32_t d = __popc(m);
-  uint64_t *out = siblings + (uint64_t)b * REG_PATH_SLOTS * 4;
-  if (hashed) {
-    const uint64_t *c = dig + (lv.off[l] + sib) * 4;
-    uint64_t *o = out + __popc(m & ((1u << l) - 1)) * 4;
-#pragma unroll
-    for (int j = 0; j < 4; j++) o[j] = c[j];
-  }
-  if (l >= d) {
-#pragma unroll
-    for (int j = 0; j < 4; j++) out[l * 4 + j] = 0;
-  }
-  if (l == 0) {
-    uint32_t bits = 0, k = 0;
-    for (uint32_t mm = m; mm; mm &= mm - 1, k++) bits |= (uint32_t)((i >> (__ffs(mm) - 1)) & 1) << k;
-    path_bits[b] = bits;
-    depth[b] = d;
-    if (leaves) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) leaves[(uint64_t)b * 4 + j] = dig[i * 4 + j];
-    }
-  }
-}
-
-// ---- updates of a commitment registry (registry_kernels.h).  A node of level
-// l is remade from nodes 2j, 2j + 1 of level l - 1, which the previous launch
-// (or the upload, for the leaves) left final; a node whose right child lies
-// beyond the level's end is a promotion, a copy of the left child.
-
-// the row form of one node: the 16-lane row of lane l16 remakes node j of
-// `level`.  The permutation runs for a promoted node too (on the left child
-// alone) and is dropped at the store, so no lane leaves the DPP broadcasts.
-__device__ __forceinline__ void registry_node_row(uint64_t *__restrict__ dig, const RegistryLevels &lv, uint32_t level,
-                                                  uint64_t j, uint32_t l16) {
-  const uint64_t *c = dig + (lv.off[level - 1] + 2 * j) * 4;
-  const bool pair = 2 * j + 1 < lv.len[level - 1];
-  const uint64_t in = l16 < (pair ? 8u : 4u) ? c[l16] : 0;
-  const uint64_t x = pc::permute_row(in);
-  if (l16 < 4) dig[(lv.off[level] + j) * 4 + l16] = pair ? psd::canon(x) : in;
-}
-
-// append, narrow range: nodes [first, first + count) of `level`, one 16-lane
-// row per node, 16 nodes per block; rows past the range exit together
-__global__ void __launch_bounds__(256) k_registry_range_row(uint64_t *__restrict__ dig, RegistryLevels lv,
-                                                            uint32_t level, uint64_t first, uint32_t count) {
-  const uint32_t r = blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (r >= count) return;
-  registry_node_row(dig, lv, level, first + r, threadIdx.x & 15);
-}
-
-// replace, level 0: leaf b of the batch into voter idx[b]'s slot (one lane per felt)
-__global__ void __launch_bounds__(256) k_registry_put(uint64_t *__restrict__ dig, const uint64_t *__restrict__ idx,
-                                                      const uint64_t *__restrict__ leaves, uint32_t k) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (uint64_t)k * 4) return;
-  dig[idx[g >> 2] * 4 + (g & 3)] = leaves[g];
-}
-
-// replace, one level: the dirty nodes are unique(idx >> level), idx ascending.
-// Of the batch entries with the same idx >> level the first owns the node and
-// the others leave at once, so every dirty node is written exactly once; its
-// children are final because the level below was a launch of its own.  One
-// lane per batch entry.
-__global__ void __launch_bounds__(256) k_registry_scatter(uint64_t *__restrict__ dig, RegistryLevels lv,
-                                                          uint32_t level, const uint64_t *__restrict__ idx,
-                                                          uint32_t k) {
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= k) return;
-  const uint64_t j = idx[b] >> level;
-  if (b && (idx[b - 1] >> level) == j) return;
-  const uint64_t *c = dig + (lv.off[level - 1] + 2 * j) * 4;
-  const bool pair = 2 * j + 1 < lv.len[level - 1];
-  uint64_t s[12];
-#pragma unroll
-  for (int i = 0; i < 4; i++) s[i] = c[i];
-#pragma unroll
-  for (int i = 4; i < 8; i++) s[i] = pair ? c[i] : 0;
-  node_digest(s);
-  if (!pair) {  // promoted: the left child again, unhashed
-#pragma unroll
-    for (int i = 0; i < 4; i++) s[i] = c[i];
-  }
-  uint64_t *o = dig + (lv.off[level] + j) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; i++) o[i] = s[i];
-}
-
-// the same in the row form: one 16-lane row per batch entry; the rows that do
-// not own their node exit whole (the owner rule of k_registry_scatter)
-__global__ void __launch_bounds__(256) k_registry_scatter_row(uint64_t *__restrict__ dig, RegistryLevels lv,
-                                                              uint32_t level, const uint64_t *__restrict__ idx,
-                                                              uint32_t k) {
-  const uint32_t b = blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (b >= k) return;
-  const uint64_t j = idx[b] >> level;
-  if (b && (idx[b - 1] >> level) == j) return;
-  registry_node_row(dig, lv, level, j, threadIdx.x & 15);
-}
-
 void registry_leaves(const uint64_t *keys, uint64_t n, uint64_t *dig, hipStream_t s) {
   k_registry_leaves<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(keys, n, dig);
-}
-
-void registry_tree(uint64_t *dig, const RegistryLevels &lv, hipStream_t s) {
-  for (uint32_t l = 1; l < lv.nlevels; l++) {
-    if (lv.len[l - 1] <= REG_FOLD_MAX) {
-      k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
-      return;
-    }
-    // one lane per pair (len > REG_FOLD_MAX: at least 32 pairs)
-    k_registry_level<<<(unsigned)((lv.len[l - 1] / 2 + 255) / 256), 256, 0, s>>>(dig + lv.off[l - 1] * 4,
-                                                                                   lv.len[l - 1], dig + lv.off[l] * 4);
-  }
-}
-
-void registry_paths(const uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, uint32_t nidx,
-                    uint64_t *siblings, uint32_t *path_bits, uint32_t *depth, uint64_t *leaves, hipStream_t s) {
-  if (!nidx) return;
-  k_registry_paths<<<(unsigned)(((uint64_t)nidx * REG_PATH_SLOTS + 255) / 256), 256, 0, s>>>(
-      dig, lv, idx, nidx, siblings, path_bits, depth, leaves);
-}
-
-// path hook registry_row=N: the row form for dirty ranges below N nodes (read per call)
-static uint64_t registry_row_max() { return (uint64_t)path_opt("registry_row", REG_ROW_MAX); }
-
-// nodes [a, e) of level l (a even-aligned source: pairs from 2a) from level
-// l - 1; true when k_registry_fold finished the tree from level l - 1 up
-static bool registry_range(uint64_t *dig, const RegistryLevels &lv, uint32_t l, uint64_t a, uint64_t e,
-                           uint64_t row_max, hipStream_t s) {
-  const uint64_t count = e - a;
-  if (count < row_max) {
-    k_registry_range_row<<<(unsigned)((count + 15) / 16), 256, 0, s>>>(dig, lv, l, a, (uint32_t)count);
-    return false;
-  }
-  if (lv.len[l - 1] <= REG_FOLD_MAX) {
-    k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
-    return true;
-  }
-  const uint64_t *src = dig + (lv.off[l - 1] + 2 * a) * 4;
-  uint64_t *dst = dig + (lv.off[l] + a) * 4;
-  const uint64_t nsrc = lv.len[l - 1] - 2 * a;
-  if (nsrc == 1)  // the range is one promoted node: no pair for k_registry_level's lane 0
-    (void)hipMemcpyAsync(dst, src, 32, hipMemcpyDeviceToDevice, s);
-  else
-    k_registry_level<<<(unsigned)((nsrc / 2 + 255) / 256), 256, 0, s>>>(src, nsrc, dst);
-  return false;
-}
-
-void registry_append(uint64_t *dig, const RegistryLevels &lv, uint64_t n_old, hipStream_t s) {
-  const uint64_t row_max = registry_row_max();
-  for (uint32_t l = 1; l < lv.nlevels; l++)
-    if (registry_range(dig, lv, l, n_old >> l, lv.len[l], row_max, s)) return;
-}
-
-void registry_replace(uint64_t *dig, const RegistryLevels &lv, const uint64_t *idx, const uint64_t *leaves, uint32_t k,
-                      hipStream_t s) {
-  if (!k) return;
-  const uint64_t row_max = registry_row_max();
-  k_registry_put<<<(unsigned)(((uint64_t)k * 4 + 255) / 256), 256, 0, s>>>(dig, idx, leaves, k);
-  for (uint32_t l = 1; l < lv.nlevels; l++) {
-    if (k >= lv.len[l]) {  // no fewer entries than nodes: the whole level, as a range
-      if (registry_range(dig, lv, l, 0, lv.len[l], row_max, s)) return;
-    } else if (k < row_max) {
-      k_registry_scatter_row<<<(k + 15) / 16, 256, 0, s>>>(dig, lv, l, idx, k);
-    } else if (lv.len[l - 1] <= REG_FOLD_MAX) {
-      k_registry_fold<<<1, REG_FOLD_MAX, 0, s>>>(dig, lv, l - 1);
-      return;
-    } else {
-      k_registry_scatter<<<(k + 255) / 256, 256, 0, s>>>(dig, lv, l, idx, k);
-    }
-  }
 }
 
 }  // namespace qpk

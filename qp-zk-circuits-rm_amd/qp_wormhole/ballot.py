@@ -22,6 +22,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._native import Context, QpError, lib
+from .registry import PATH_SLOTS  # sibling slots of a receipt's path: the log tree is the registry's kind of tree
 
 P = 0xFFFFFFFF00000001
 NPI = 13
@@ -35,7 +36,6 @@ BALLOT_STATUS_TEXT = ("counted", "proof rejected", "malformed public inputs", "w
                       "bad vote", "double vote")
 FLAG_VOTE, FLAG_COUNTED = 1, 2
 
-PATH_SLOTS = 32             # sibling slots of a receipt's path (the registry's REG_PATH_SLOTS)
 NOT_FOUND = 2**64 - 1       # qp_ballot_box_find: the nullifier was never admitted
 
 BallotResult = namedtuple("BallotResult", "status verify_status number first")

@@ -1,6 +1,6 @@
 """The ballot box's log commitment on the device (csrc/ballot.hip:
 k_ballot_leaves, k_ballot_find, k_ballot_gather; the levels and paths through
-the registry's launchers): the cases of test_ballot_receipts.py against the
+the accumulator tree's launchers, csrc/acc_tree.hip): the cases of test_ballot_receipts.py against the
 same model and, result for result, against the host path; then real voting
 proofs end to end: registry, prover, verifier, box, receipts."""
 import numpy as np
@@ -67,6 +67,65 @@ def test_find(device_box):
 
 def test_receipt_rules(device_box):
     assert check_receipt_rules(device_box) == check_receipt_rules(host_box)
+
+
+@pytest.mark.parametrize("hook", [None, "registry_row=0"], ids=["default", "one_lane"])
+@pytest.mark.parametrize("n", [1, 2, 3, 64, 65, 129])
+def test_one_tree_serves_log_and_registry(ctx, device_box, monkeypatch, hook, n):
+    """The ballot log and the voter registry are two clients of one accumulator
+    tree (csrc/acc_tree.h): a commitment registry built from a committed log's
+    leaves (the model's leaf function over `entries`) has the log's root, and
+    its paths_raw are the receipts' buffers bit for bit.  Sizes: no parent, one
+    pair, a promoted leaf, ACC_FOLD_MAX = 64 on the leaf level (64, 65) and on
+    the level above (129).  Every log of at least two entries holds double
+    votes (entry i = 1 mod 4 repeats entry i - 1's nullifier with the other
+    vote); a log of one entry cannot.  With the one-lane form (registry_row=0)
+    and the default, which governs both trees."""
+    import ctypes
+
+    from ballot_model import ROOT_A, ballot, cast_batch
+    from ballot_receipt_model import leaf
+    from qp_wormhole import VoterRegistry
+    from qp_wormhole._native import lib
+    from qp_wormhole.ballot import DOUBLE_VOTE, PATH_SLOTS
+    if hook:
+        monkeypatch.setenv("QPGPU_PATHS", hook)
+    else:
+        monkeypatch.delenv("QPGPU_PATHS", raising=False)
+    rng = np.random.default_rng(1000 + n)
+    nuls = rng.integers(0, 0xFFFFFFFF00000001, size=(n, 4), dtype=np.uint64).tolist()
+    doubles = [i for i in range(n) if i % 4 == 1]
+    for i in doubles:
+        nuls[i] = nuls[i - 1]
+    box = device_box(PROPOSAL, [ROOT_A], n)
+    reg = None
+    try:
+        res = cast_batch(box, [(ballot(k, i & 1, PROPOSAL), 0) for i, k in enumerate(nuls)])
+        assert [i for i, r in enumerate(res) if r.status == DOUBLE_VOTE] == doubles and (n < 2 or doubles)
+        root, committed = box.commit_log()
+        assert committed == n == box.admitted
+        nul, num, counted, votes = box.entries()
+        assert nul.tolist() == nuls and [i for i in range(n) if not counted[i]] == doubles
+        leaves = [leaf((nul[i].tolist(), int(num[i]), bool(counted[i]), bool(votes[i]))) for i in range(n)]
+        reg = VoterRegistry.from_commitments(ctx, leaves)
+        assert [int(x) for x in reg.root] == root
+        seqs = np.array(sorted({0, n // 2, n - 1}), dtype=np.uint64)
+        k = len(seqs)
+        sib, bits, depth = reg.paths_raw(seqs)
+        rsib = np.full((k, PATH_SLOTS, 4), 0xA5A5A5A5A5A5A5A5, np.uint64)  # every slot is written
+        rbits, rdepth = np.full(k, 0xFFFFFFFF, np.uint32), np.full(k, 0xFFFFFFFF, np.uint32)
+        rleaf, rroot, rn = np.zeros((k, 4), np.uint64), np.zeros(4, np.uint64), ctypes.c_uint64()
+        assert lib().qp_ballot_box_receipts(box.h, seqs.ctypes.data, k, rsib.ctypes.data, rbits.ctypes.data,
+                                            rdepth.ctypes.data, rleaf.ctypes.data, rroot.ctypes.data,
+                                            ctypes.byref(rn)) == 0
+        assert (rroot.tolist(), rn.value) == (root, n)
+        assert rsib.tobytes() == sib.tobytes() and rbits.tobytes() == bits.tobytes()
+        assert rdepth.tobytes() == depth.tobytes()
+        assert rleaf.tolist() == [leaves[int(s)] for s in seqs]
+    finally:
+        if reg is not None:
+            reg.free()
+        box.free()
 
 
 def test_voting_proofs_to_receipts(ctx):

@@ -4,7 +4,7 @@ the compacted paths equal the host fallback's and the oracle loop's
 registry.prove are the bytes of prove_inputs on hand-built inputs.
 
 Sizes: 1, 2, 3; 63, 64, 65 (the wave edge and the one-workgroup fold's
-REG_FOLD_MAX = 64 boundary); 127, 129 (one launch-per-level level above the
+ACC_FOLD_MAX = 64 boundary); 127, 129 (one launch-per-level level above the
 fold, odd on both sides); 4097 (several launch-per-level levels, a promoted
 node at more than one level, more than one block); 2^16 + 1 (a promoted node
 climbing 16 levels)."""

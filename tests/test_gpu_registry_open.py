@@ -5,10 +5,10 @@ current commitments (registry_open_model.py) and the host fallback taken
 through the same steps.
 
 Every sequence runs twice: with the row form forced for every dirty range
-(QPGPU_PATHS registry_row=2^31: k_registry_range_row / k_registry_scatter_row
-up to the root) and with the one-lane form (registry_row=0: k_registry_level on
-a level's suffix, a copy for a lone promoted node, k_registry_scatter, and
-k_registry_fold from a level of at most 64 nodes).  Both are compared with the
+(QPGPU_PATHS registry_row=2^31: k_acc_range_row / k_acc_scatter_row
+up to the root) and with the one-lane form (registry_row=0: k_acc_level on
+a level's suffix, a copy for a lone promoted node, k_acc_scatter, and
+k_acc_fold from a level of at most 64 nodes).  Both are compared with the
 same model, so they give the same digests.
 
 Beyond the host test's sequences: 1000 -> 1001 -> 1003 -> 1027 (a dirty range

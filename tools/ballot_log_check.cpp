@@ -1,6 +1,6 @@
 // ballot_log_check.cpp — the ballot box's log commitment in host C++
-// (csrc/ballot_log.h: the read-only find, the leaf hash and level loop of
-// HostLog, path extraction, the receipt check) under the sanitizers, against a
+// (csrc/ballot_log.h: the read-only find, the leaf and node hashes, HostLog on
+// acc_layout.h's host tree, path extraction, the receipt check) under the sanitizers, against a
 // brute-force scan of the log and a naive recursive tree, at 1, 2, 3, 64 and 65
 // entries and on a capacity-full box, with doubles among the entries, committed
 // in one step and in several, across a reserve.  A stand-alone CPU program;
@@ -56,7 +56,7 @@ static uint64_t felt() { return rng() % P; }
 
 // every receipt of the committed log checks, and each tampering gives its reason
 static void check_receipts(const HostBox &box, const HostLog &log, const std::vector<Digest> &leaves) {
-  const uint64_t n = log.committed;
+  const uint64_t n = log.n;
   CHECK(n == box.count());
   const Digest want = naive_root(leaves, n);
   CHECK(!memcmp(want.v, log.root(), 32));
@@ -114,7 +114,7 @@ static void run(uint64_t n, uint64_t capacity, const std::vector<uint64_t> &step
     box.admit(nul, 2 * i + 1, i & 1, &first);
     if (next < steps.size() && steps[next] == i + 1) {
       next++;
-      CHECK(log.commit(box) && log.committed == i + 1);
+      CHECK(log.commit(box) && log.n == i + 1);
       for (uint64_t s = leaves.size(); s <= i; s++) {
         Digest d;
         log_leaf(&box.nullifier[s * 4], box.number[s], box.flags[s], d.v);
@@ -126,7 +126,7 @@ static void run(uint64_t n, uint64_t capacity, const std::vector<uint64_t> &step
       CHECK(!memcmp(want.v, log.root(), 32));
     }
   }
-  CHECK(log.committed == n && leaves.size() == n);
+  CHECK(log.n == n && leaves.size() == n);
   check_receipts(box, log, leaves);
   // find: every entry's nullifier gives the counted entry; absent keys with a crowded, an empty and the last home slot
   for (uint64_t s = 0; s < n; s++) {
@@ -152,14 +152,14 @@ int main() {
   // the shape rule against the level table
   for (uint64_t n : {1ull, 2ull, 3ull, 5ull, 64ull, 65ull, 131ull})
     for (uint64_t seq = 0; seq < n; seq++) {
-      qpk::RegistryLevels lv;
-      CHECK(qpk::registry_levels_reserved(n, n, lv));
+      qpk::AccLevels lv;
+      CHECK(qpk::acc_levels_reserved(n, n, lv));
       uint32_t m = 0;
       for (uint32_t l = 0; l + 1 < lv.nlevels; l++)
         if (((seq >> l) ^ 1) < lv.len[l]) m |= 1u << l;
-      CHECK(path_levels(seq, n) == m);
+      CHECK(qpk::path_levels(seq, n) == m);
     }
-  CHECK(path_levels(0, qpk::REG_MAX_VOTERS) == 0x7FFFFFFFu && path_levels(qpk::REG_MAX_VOTERS - 1, qpk::REG_MAX_VOTERS) == 0x7FFFFFFFu);
+  CHECK(qpk::path_levels(0, qpk::ACC_MAX_LEAVES) == 0x7FFFFFFFu && qpk::path_levels(qpk::ACC_MAX_LEAVES - 1, qpk::ACC_MAX_LEAVES) == 0x7FFFFFFFu);
   for (uint64_t n : {1ull, 2ull, 3ull, 64ull, 65ull}) {
     run(n, n, {n}, 0);              // capacity-full, one commit
     run(n, 2 * n + 3, {n}, 0);      // room to spare: the reserved layout's offsets differ

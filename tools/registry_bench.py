@@ -217,7 +217,7 @@ def main():
         "build_wall_perm_per_s": perms / statistics.median(wall),
         "paths_batch": args.batch,
         "paths_wall_s": {"median": statistics.median(pt), "min": min(pt), "max": max(pt), "runs": len(pt),
-                         "what": "paths_raw(1024 indices): index upload, k_registry_paths, copies back, sync"},
+                         "what": "paths_raw(1024 indices): index upload, k_acc_paths, copies back, sync"},
         "host_fallback": {"voters": hn, "build_s": host_s,
                           "build_s_scaled_to_voters": host_s * n / hn,
                           "note": "SCALED linearly from %d voters, not run at %d" % (hn, n)},
