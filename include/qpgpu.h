@@ -607,6 +607,65 @@ int qp_ballot_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, co
                             uint64_t number, uint8_t flags, const uint64_t *siblings, uint32_t path_bits,
                             uint32_t depth);
 
+/* ---- the audit of a published log, prefix roots, reopening a box -------------
+ * A published log is what qp_ballot_box_entries returns: nullifiers[n][4],
+ * numbers[n], flags[n], 1 <= n <= 2^31.  Beside it come optional claims: a
+ * root, a tally (yes, no), and earlier commitments (root_i, n_i).  The audit
+ * reports the first reason that fires, in this order, with the lowest offender
+ * as its witness, so the report is a function of the input alone:            */
+typedef enum {
+    QP_AUDIT_OK = 0,
+    QP_AUDIT_NON_CANONICAL = 1, /* a nullifier felt >= p, a number >= p or a flags byte > 3; witness = the lowest
+                                   such seq.  Nothing is hashed: the report's root and counts are zero */
+    QP_AUDIT_ORDER = 2,         /* numbers[seq] <= numbers[seq - 1] (a box's log has strictly increasing numbers);
+                                   witness = the lowest such seq >= 1 */
+    QP_AUDIT_COUNT_RULE = 3,    /* an entry's counted bit != "no earlier entry has this nullifier"; witness = the
+                                   lowest such seq, first = the lowest seq holding that nullifier */
+    QP_AUDIT_TALLY = 4,         /* a tally is claimed and differs from (counted & vote, counted & !vote) of the flags */
+    QP_AUDIT_ROOT = 5,          /* a root is claimed and differs from the log tree's root over [0, n) */
+    QP_AUDIT_COMMITMENT = 6     /* some (root_i, n_i) has n_i > n, or the root of the prefix [0, n_i) != root_i;
+                                   witness = the lowest such index i */
+} qp_audit_status;
+/* On every status but QP_AUDIT_NON_CANONICAL the report carries the recomputed
+ * root and (yes, no, counted) of the flags.
+ * Prefix root of m, 1 <= m <= n, in a tree of n leaves: acc = leaf m - 1; at
+ * each level l while c = ceil(m / 2^l) > 1: c odd, acc moves up unchanged; c
+ * even, acc = hash_no_pad(dig[l][c - 2] || acc).  dig[l][c - 2] covers only
+ * leaves below m, so it is the same digest in the larger tree: the log tree's
+ * shape, with the odd node promoted, is the append-only shape.  The prefix root
+ * at m = n is the root.  With a context the audit runs on the device: one lane
+ * per entry inserts the whole log into a fresh nullifier table, whose slots
+ * end at the lowest seq of each nullifier whatever the scheduling.            */
+typedef struct {
+    uint32_t status;         /* qp_audit_status */
+    uint32_t pad;
+    uint64_t witness, first; /* UINT64_MAX: none */
+    uint64_t root[4], yes, no, counted;
+} qp_audit_report;
+/* audits a published log against the claims given (each NULL / ncommit == 0: not claimed).  QP_OK:
+ * the audit ran, the verdict is out->status.  QP_ERR_ARG: a null buffer, n outside 1..2^31, a claimed
+ * or commitment root with a felt >= p, some n_i == 0.  Needs no box; the log is not altered.      */
+int qp_ballot_log_audit(qp_ctx *ctx /* NULL: host */, const uint64_t *nullifiers, const uint64_t *numbers,
+                        const uint8_t *flags, uint64_t n, const uint64_t *claimed_root /* NULL: none */,
+                        const uint64_t *claimed_tally /* [2] or NULL */, const uint64_t *commit_roots,
+                        const uint64_t *commit_ns, uint32_t ncommit, qp_audit_report *out);
+/* commits, as qp_ballot_box_receipts does, then roots_out[i][4] = the root the log had at ms[i]
+ * entries: the commitment (root, ms[i]) the box gave, or would have given, then.  Each ms[i] in
+ * 1..admitted, else QP_ERR_ARG naming the position, before anything is enqueued.  Nothing admitted:
+ * QP_ERR_STATE "empty log".  k == 0: QP_OK, nothing launched beyond the commit.                  */
+int qp_ballot_box_roots_at(qp_ballot_box *b, const uint64_t *ms, uint32_t k, uint64_t *roots_out /* [k][4] */);
+/* reopens a box from a published log: the arguments of qp_ballot_box_new, the log, and cast_count,
+ * the number the next ballot takes.  Runs the audit's reasons 1-3, and 5 when expect_root is given;
+ * on a failing audit QP_ERR_FORMAT, no box, and qp_ballot_box_last_error(NULL) names the reason and
+ * the witness.  QP_ERR_ARG unless capacity >= max(n, 1) and cast_count > numbers[n - 1]; n == 0 is
+ * allowed, with any cast_count.  The box keeps the uploaded log and the table the audit built; its
+ * tally comes from the flags, cast = cast_count, admitted = n, nothing is committed yet; from there
+ * it is an ordinary box.  A failed HIP step: QP_ERR_HIP, no box.                                  */
+int qp_ballot_box_restore(qp_ctx *ctx, const uint64_t proposal_id[4], const uint64_t *roots, uint32_t nroots,
+                          uint64_t capacity, const uint64_t *nullifiers, const uint64_t *numbers,
+                          const uint8_t *flags, uint64_t n, uint64_t cast_count,
+                          const uint64_t *expect_root /* NULL: none */, qp_ballot_box **out);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

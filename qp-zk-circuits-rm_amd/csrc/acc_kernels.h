@@ -30,6 +30,14 @@ __global__ void k_acc_paths(const uint64_t *dig, AccLevels lv, const uint64_t *i
 void acc_paths(const uint64_t *dig, const AccLevels &lv, const uint64_t *idx, uint32_t nidx, uint64_t *siblings,
                uint32_t *path_bits, uint32_t *depth, uint64_t *leaves, hipStream_t s);
 
+__global__ void k_acc_prefix_roots(const uint64_t *dig, AccLevels lv, const uint64_t *m, uint32_t k, uint64_t *roots);
+
+// roots[i][4] = the root the tree had when it held leaves [0, m[i]) (m device, each in 1..n: the
+// caller checks the bound), by acc_layout.h's HostTree::prefix_root fold.  Read-only; after the
+// append that made `lv`, on the same stream.
+void acc_prefix_roots(const uint64_t *dig, const AccLevels &lv, const uint64_t *m, uint32_t k, uint64_t *roots,
+                      hipStream_t s);
+
 // ---- the levels above level 0.  Each launcher recomputes the nodes that a
 // change of level 0 changes, level by level in launch order, every loop bound
 // from the host's table.

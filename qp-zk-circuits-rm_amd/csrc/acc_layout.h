@@ -140,6 +140,20 @@ struct HostTree {
     *depth = d;
     if (leaf) memcpy(leaf, node(0, i), 32);
   }
+
+  // the root the tree had when it held leaves [0, m), 1 <= m <= n: a fold from leaf m - 1 up.  At level l
+  // the prefix has c = ceil(m / 2^l) nodes and the fold holds its last one: c odd, that node is promoted;
+  // c even, its left sibling c - 2 covers only leaves below m, so it is the same digest in this larger
+  // tree.  The layout qpk::acc_prefix_roots answers in.
+  template <class NodeHash>
+  void prefix_root(uint64_t m, NodeHash hash, uint64_t out[4]) const {
+    memcpy(out, node(0, m - 1), 32);
+    for (uint32_t l = 0;; l++) {
+      const uint64_t c = (m + ((uint64_t)1 << l) - 1) >> l;
+      if (c <= 1) return;
+      if (!(c & 1)) hash(node(l, c - 2), out, out);
+    }
+  }
 };
 
 // the order that sorts a replace batch by leaf index: order[b] = position in

@@ -37,6 +37,23 @@ int AccTree::paths(AccErr e, hipStream_t s, const uint64_t *idx, uint32_t nidx, 
   return QP_OK;
 }
 
+int AccTree::prefix_roots(AccErr e, hipStream_t s, const uint64_t *ms, uint32_t k, uint64_t *roots_out) {
+  if (k && d_m.words < ACC_BATCH) {
+    QP_HIP_TRY(&e, d_m.alloc(ACC_BATCH));
+    QP_HIP_TRY(&e, d_roots.alloc((size_t)ACC_BATCH * 4));
+  }
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(ACC_BATCH, k - done);
+    QP_HIP_TRY(&e, hipMemcpyAsync(d_m.p, ms + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+    qpk::acc_prefix_roots(dig.p, lv, d_m.p, nb, d_roots.p, s);
+    QP_HIP_TRY(&e, hipGetLastError());
+    QP_HIP_TRY(&e, hipMemcpyAsync(roots_out + (size_t)done * 4, d_roots.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(&e, hipStreamSynchronize(s));
+    done += nb;
+  }
+  return QP_OK;
+}
+
 int AccTree::reserve(AccErr e, uint64_t new_capacity, const qpk::AccLevels &nlv, hipStream_t s) {
   DevBuf nd;
   QP_HIP_TRY(&e, nd.alloc((size_t)qpk::acc_reserved(new_capacity) * 4));

@@ -22,6 +22,7 @@ struct AccTree {
   qpk::AccLevels lv;      // the table of the current leaves in that layout
   uint64_t capacity = 0;  // 0: no tree (dig.p is null)
   DevBuf d_idx, d_sib, d_bits, d_depth, d_leaf;  // one batch of paths, allocated by the first
+  DevBuf d_m, d_roots;                           // one batch of prefix-root queries, allocated by the first
 
   uint64_t n() const { return lv.nlevels ? lv.len[0] : 0; }
   // the root of the tree at table `at` (device)
@@ -46,6 +47,9 @@ struct AccTree {
   // checks the bound) into host buffers laid out as k_acc_paths writes them; one synchronise per ACC_BATCH
   int paths(AccErr e, hipStream_t s, const uint64_t *idx, uint32_t nidx, uint64_t *siblings, uint32_t *path_bits,
             uint32_t *depth, uint64_t *leaves);
+  // roots_out[i][4] (host) = the root the tree had at ms[i] leaves (host; each in 1..n(), the caller checks
+  // the bound before anything is enqueued); one synchronise per ACC_BATCH
+  int prefix_roots(AccErr e, hipStream_t s, const uint64_t *ms, uint32_t k, uint64_t *roots_out);
   // the same leaves re-laid for new_capacity, nlv = their table there: a new buffer beside the old, every
   // level copied, the stream synchronised; the tree moves over only once all of it succeeded
   int reserve(AccErr e, uint64_t new_capacity, const qpk::AccLevels &nlv, hipStream_t s);

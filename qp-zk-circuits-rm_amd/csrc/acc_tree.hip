@@ -110,6 +110,43 @@ __global__ void __launch_bounds__(256) k_acc_paths(const uint64_t *__restrict__ 
   }
 }
 
+// one lane per queried size m[i]: the root the tree had when it held leaves
+// [0, m), HostTree::prefix_root's fold (acc_layout.h): at most 31 dependent
+// permutations, the running digest in registers.  Read-only; it runs after the
+// append that made `lv` on the same stream.  The level counter is uniform, so
+// the table is read with scalar loads; a lane whose prefix is finished leaves
+// the loop.  m outside 1..n cannot be reached (the host checks before it
+// enqueues): such a lane reads nothing and answers the zero digest.
+__global__ void __launch_bounds__(256) k_acc_prefix_roots(const uint64_t *__restrict__ dig, AccLevels lv,
+                                                          const uint64_t *__restrict__ m, uint32_t k,
+                                                          uint64_t *__restrict__ roots) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const uint64_t mi = m[i];
+  uint64_t s[12];
+  if (mi == 0 || mi > lv.len[0]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) roots[(uint64_t)i * 4 + j] = 0;
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) s[j] = dig[(mi - 1) * 4 + j];
+  for (uint32_t l = 0; l + 1 < lv.nlevels; l++) {
+    const uint64_t c = (mi + ((uint64_t)1 << l) - 1) >> l;
+    if (c <= 1) break;
+    if (c & 1) continue;  // the prefix's last node at this level is promoted
+    const uint64_t *left = dig + (lv.off[l] + c - 2) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      s[4 + j] = s[j];
+      s[j] = left[j];
+    }
+    node_digest(s);
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) roots[(uint64_t)i * 4 + j] = s[j];
+}
+
 // ---- the levels above level 0 after an update (acc_kernels.h).  A node of
 // level l is remade from nodes 2j, 2j + 1 of level l - 1, which the previous
 // launch (or the owner, for the leaves) left final; a node whose right child
@@ -188,6 +225,12 @@ void acc_paths(const uint64_t *dig, const AccLevels &lv, const uint64_t *idx, ui
   if (!nidx) return;
   k_acc_paths<<<(unsigned)(((uint64_t)nidx * ACC_PATH_SLOTS + 255) / 256), 256, 0, s>>>(
       dig, lv, idx, nidx, siblings, path_bits, depth, leaves);
+}
+
+void acc_prefix_roots(const uint64_t *dig, const AccLevels &lv, const uint64_t *m, uint32_t k, uint64_t *roots,
+                      hipStream_t s) {
+  if (!k) return;
+  k_acc_prefix_roots<<<(k + 255) / 256, 256, 0, s>>>(dig, lv, m, k, roots);
 }
 
 // nodes [a, e) of level l (a even-aligned source: pairs from 2a) from level

@@ -4,7 +4,9 @@
 // nullifier set and the tally live on the device (ballot.hip); without one the
 // same semantics run on the host (qb::HostBox).  The log commitment (find,
 // commit_log, receipts and the receipt check: ballot_log.h) is brought up to
-// date on demand; a cast does not touch it.
+// date on demand; a cast does not touch it.  roots_at answers from that tree;
+// restore reopens a box from a published log through the audit's passes
+// (ballot_audit.h, ballot_audit.cpp) and keeps the table they built.
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <algorithm>
@@ -14,6 +16,8 @@
 #include <utility>
 #include <vector>
 #include "acc_tree.h"
+#include "ballot_audit.h"
+#include "ballot_audit_device.h"
 #include "ballot_kernels.h"
 #include "ballot_log.h"
 #include "ballot_table.h"
@@ -76,6 +80,14 @@ int refuse_new(qp_ctx *c, const std::string &why) {
   return QP_ERR_ARG;
 }
 
+}  // namespace
+
+void qba::set_boxless_error(qp_ctx *c, const std::string &why) {
+  g_new_err = why;
+  if (c) c->err = why;
+}
+
+namespace {
 int alloc_tables(qp_ballot_box *b, uint64_t capacity, DeviceTables &t) {
   const uint64_t S = qb::table_slots(capacity);
   QP_HIP_TRY(b, t.nul.alloc(capacity * 4));
@@ -622,6 +634,104 @@ int qp_ballot_box_entries_at(qp_ballot_box *b, const uint64_t *seqs, uint32_t k,
     if (flags) flags[i] = b->host.flags[seqs[i]];
   }
   return QP_OK;
+}
+
+int qp_ballot_box_roots_at(qp_ballot_box *b, const uint64_t *ms, uint32_t k, uint64_t *roots_out) {
+  if (!b) return QP_ERR_ARG;
+  if (b->dead) return dead_box(b, "qp_ballot_box_roots_at");
+  if (!b->admitted()) return empty_log(b, "qp_ballot_box_roots_at");
+  if (k && (!ms || !roots_out)) {
+    b->err = "qp_ballot_box_roots_at: null buffer";
+    return QP_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < k; i++)
+    if (!ms[i] || ms[i] > b->admitted()) {
+      b->err = "qp_ballot_box_roots_at: size " + std::to_string(ms[i]) + " (position " + std::to_string(i) +
+               ") is outside 1.." + std::to_string(b->admitted()) + ", the sizes the log has had";
+      return QP_ERR_ARG;
+    }
+  try {
+    if (int rc = device_step(b, commit_log(b))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(b, "qp_ballot_box_roots_at");
+  }
+  if (!k) return QP_OK;
+  if (b->ctx) {
+    QP_HIP_TRY(b, hipSetDevice(b->ctx->device));
+    return device_step(b, b->log.prefix_roots({b->err}, b->ctx->stream, ms, k, roots_out));
+  }
+  for (uint32_t i = 0; i < k; i++) b->hlog.prefix_root(ms[i], qb::log_node, roots_out + (size_t)i * 4);
+  return QP_OK;
+}
+
+int qp_ballot_box_restore(qp_ctx *c, const uint64_t proposal_id[4], const uint64_t *roots, uint32_t nroots,
+                          uint64_t capacity, const uint64_t *nullifiers, const uint64_t *numbers, const uint8_t *flags,
+                          uint64_t n, uint64_t cast_count, const uint64_t *expect_root, qp_ballot_box **out) {
+  if (!out) return QP_ERR_ARG;
+  *out = nullptr;
+  auto refuse = [c](int rc, const std::string &why) {
+    qba::set_boxless_error(c, "qp_ballot_box_restore: " + why);
+    return rc;
+  };
+  if (n && (!nullifiers || !numbers || !flags)) return refuse(QP_ERR_ARG, "null log buffer");
+  if (expect_root && (!n || !qb::canonical(expect_root, 4)))
+    return refuse(QP_ERR_ARG, n ? "the expected root is not four canonical field elements" : "an empty log has no root");
+  try {
+    const std::string why = qb::restore_refusal(numbers, n, capacity, cast_count);
+    if (!why.empty()) return refuse(QP_ERR_ARG, why);
+    qp_ballot_box *fresh = nullptr;
+    int rc = qp_ballot_box_new(c, proposal_id, roots, nroots, capacity, &fresh);
+    if (rc) return rc;  // qp_ballot_box_new left its reason
+    std::unique_ptr<qp_ballot_box, void (*)(qp_ballot_box *)> b(fresh, qp_ballot_box_free);
+    b->cast = cast_count;
+    if (!n) {
+      *out = b.release();
+      return QP_OK;
+    }
+    qb::AuditFacts f;
+    bool canonical = false;
+    if (!c) {
+      qb::HostLog tree;
+      canonical = qb::audit_facts_host(nullifiers, numbers, flags, n, capacity, expect_root != nullptr, b->host, tree, f);
+    } else {
+      // the log into the new box's own buffers and its fresh table: what the audit builds is what the box keeps
+      hipStream_t s = c->stream;
+      const qpk::BallotDev d = b->t.dev();
+      // With an expected root the audit builds the log tree for n leaves in `tree`, and the tree is discarded
+      // on purpose: a restored box has committed nothing yet, and its own tree is laid out for the capacity,
+      // not for n, by the first commit_log (which hashes these leaves again).
+      AccTree tree;
+      auto device_restore = [&]() -> int {
+        QP_HIP_TRY(b, hipSetDevice(c->device));
+        QP_HIP_TRY(b, hipMemcpyAsync(d.nullifier, nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
+        QP_HIP_TRY(b, hipMemcpyAsync(d.number, numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        QP_HIP_TRY(b, hipMemcpyAsync(d.flags, flags, (size_t)n, hipMemcpyHostToDevice, s));
+        if (int r = qba::audit_facts_device(c, {b->err}, d, n, expect_root ? &tree : nullptr, f, &canonical)) return r;
+        if (!canonical) return QP_OK;
+        const qpk::BallotCounters now{f.yes, f.no, 0, 0};
+        QP_HIP_TRY(b, hipMemcpyAsync(b->d_ctr.p, &now, sizeof now, hipMemcpyHostToDevice, s));
+        QP_HIP_TRY(b, hipStreamSynchronize(s));
+        return QP_OK;
+      };
+      if ((rc = device_restore())) return refuse(rc, b->err);
+      b->count = n;
+      b->yes = f.yes;
+      b->no = f.no;
+    }
+    qb::AuditReport r;
+    if (!canonical) {
+      qb::audit_non_canonical(f.non_canonical, r);
+    } else {
+      qb::AuditClaims claims;
+      claims.root = expect_root;
+      qb::audit_verdict(f, n, claims, qb::AUDIT_RESTORE_REASONS, [](uint32_t, uint64_t, uint64_t *) {}, r);
+    }
+    if (r.status != qb::AUDIT_OK) return refuse(QP_ERR_FORMAT, qb::audit_failure_text(r));
+    *out = b.release();
+    return QP_OK;
+  } catch (const std::bad_alloc &) {
+    return refuse(QP_ERR_OOM, "out of host memory");
+  }
 }
 
 int qp_ballot_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],

@@ -3,16 +3,13 @@
 // one or a few dependent slot atomics and 32-byte key reads; no arithmetic to
 // speak of.  The log commitment's leaf kernel is the exception: VALU-bound, one
 // permutation per lane (merkle_node.h), like registry.hip's.
+#include "ballot_device.h"
 #include "ballot_kernels.h"
 #include "merkle_node.h"
 
 namespace qpk {
 
 namespace {
-constexpr uint32_t BALLOT_EMPTY = 0xFFFFFFFFu;
-constexpr uint32_t BALLOT_NO_SLOT = 0xFFFFFFFFu;  // stay[] of a lane whose probe ran out (defensive)
-constexpr uint8_t BALLOT_VOTE = 1, BALLOT_COUNTED = 2;
-
 // The probe of log entry seq (the log holds `limit` entries): returns the slot
 // where it stays, BALLOT_NO_SLOT if S slots were tried (see fact 3 below).
 //
@@ -62,26 +59,6 @@ __device__ __forceinline__ uint32_t ballot_probe(const BallotDev &d, uint32_t se
     }
   }
   return BALLOT_NO_SLOT;
-}
-
-// adds N per-lane predicates over the block into N 64-bit counters: a wave
-// ballot and popcount each, the waves' counts through LDS, one integer atomic
-// per counter and block (integer sums are order-independent).  Every lane of
-// the block calls it.
-template <int N>
-__device__ __forceinline__ void block_count(const bool (&pred)[N], unsigned long long *const (&dst)[N]) {
-  __shared__ uint32_t sh[4][N];
-  const uint32_t wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < N; j++) {
-    const uint32_t n = __popcll(__ballot(pred[j]));
-    if ((threadIdx.x & 63) == 0) sh[wave][j] = n;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    const uint32_t t = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
-    if (t) atomicAdd(dst[threadIdx.x], (unsigned long long)t);
-  }
 }
 }  // namespace
 
@@ -161,7 +138,7 @@ __global__ void __launch_bounds__(256) k_ballot_leaves(BallotDev d, uint32_t fir
   s[4] = d.number[seq];
   s[5] = d.flags[seq];
   s[6] = s[7] = 0;
-  if (s[4] >= 0xFFFFFFFF00000001ull) {
+  if (s[4] >= BALLOT_P) {
     atomicOr(err, 4u);
     return;
   }

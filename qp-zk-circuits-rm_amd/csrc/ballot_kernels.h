@@ -71,4 +71,26 @@ void ballot_find(const BallotDev &d, uint32_t count, const uint64_t *q, uint32_t
 void ballot_gather(const BallotDev &d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
                    uint8_t *flags, hipStream_t s);
 
+// ---- the audit of a published log (ballot_audit.hip; ballot_audit.h has the definitions).  The
+// log is uploaded whole, a fresh all-empty table takes it in one ballot_insert (first_seq = 0,
+// k = n), and the audit writes nothing but its report.
+constexpr uint32_t AUDIT_NO_SEQ = 0xFFFFFFFFu;  // no offender (seqs stay below 2^31)
+
+// the device half of a report; the host sets the three offender words to all-ones, the rest to zero
+struct BallotAuditDev {
+  BallotCounters ctr;             // yes, no of the counted flags; the defensive error word of insert and leaves
+  unsigned long long counted;     // entries with the counted bit
+  unsigned long long count_rule;  // the lowest (seq << 32 | owner) whose counted bit != (owner == seq)
+  uint32_t non_canonical, order;  // the lowest offending seq of each
+};
+
+__global__ void k_audit_screen(BallotDev d, uint32_t n, BallotAuditDev *rep);
+__global__ void k_audit_resolve(BallotDev d, uint32_t n, const uint32_t *stay, BallotAuditDev *rep);
+
+// one lane per entry of [0, n): the canonical checks and number[seq] > number[seq - 1]
+void ballot_audit_screen(const BallotDev &d, uint32_t n, BallotAuditDev *rep, hipStream_t s);
+// after ballot_insert(d, 0, n, stay, &rep->ctr, s) into a fresh table, a launch of its own: the count
+// rule per entry from stay[] and the final slot words, and the counts of the flags.  Writes no flag.
+void ballot_audit_resolve(const BallotDev &d, uint32_t n, const uint32_t *stay, BallotAuditDev *rep, hipStream_t s);
+
 }  // namespace qpk

@@ -180,6 +180,10 @@ def lib():
         "qp_ballot_box_entries_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP, VP]),
         "qp_ballot_receipt_check": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, ctypes.c_uint64,
                                                    ctypes.c_uint8, VP, ctypes.c_uint32, ctypes.c_uint32]),
+        "qp_ballot_log_audit": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_uint64, VP, VP, VP, VP, ctypes.c_uint32, VP]),
+        "qp_ballot_box_roots_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP]),
+        "qp_ballot_box_restore": (ctypes.c_int, [VP, U64P, U64P, ctypes.c_uint32, ctypes.c_uint64, VP, VP, VP,
+                                                 ctypes.c_uint64, ctypes.c_uint64, VP, PP]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

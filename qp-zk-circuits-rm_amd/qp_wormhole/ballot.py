@@ -47,11 +47,72 @@ RESULT_DTYPE = np.dtype([("status", np.uint32), ("verify_status", np.uint32), ("
                          ("first", np.uint64)])
 
 
+# qp_audit_status: the first reason that fires, in this order
+(AUDIT_OK, AUDIT_NON_CANONICAL, AUDIT_ORDER, AUDIT_COUNT_RULE, AUDIT_TALLY, AUDIT_ROOT, AUDIT_COMMITMENT) = range(7)
+AUDIT_STATUS_TEXT = ("ok", "non-canonical entry", "ballot numbers out of order", "count rule broken",
+                     "claimed tally differs", "claimed root differs", "earlier commitment does not hold")
+# the verdict on a published log: witness = the lowest offender (an entry's seq; for a commitment
+# its index), first = the lowest seq holding the witness's nullifier (count rule only), None where
+# there is none; root and (yes, no, counted) recomputed from the log (zero on a non-canonical one)
+AuditReport = namedtuple("AuditReport", "status witness first root yes no counted")
+# qp_audit_report
+AUDIT_DTYPE = np.dtype([("status", np.uint32), ("pad", np.uint32), ("witness", np.uint64), ("first", np.uint64),
+                        ("root", np.uint64, 4), ("yes", np.uint64), ("no", np.uint64), ("counted", np.uint64)])
+
+
 def _digest(v, what):
     d = [int(x) for x in v]
     if len(d) != 4 or any(not 0 <= x < P for x in d):
         raise ValueError(f"{what} must be 4 canonical field elements")
     return np.array(d, dtype=np.uint64)
+
+
+def _log_arrays(entries):
+    """(nullifiers [n][4], numbers [n], flags [n]) of a published log: the 4-tuple
+    `BallotBox.entries()` returns, or (nullifiers, numbers, flags bytes)"""
+    entries = tuple(entries)
+    if len(entries) == 4:
+        nul, num, counted, votes = entries
+        fl = (np.asarray(votes, dtype=bool).astype(np.uint8) * FLAG_VOTE
+              + np.asarray(counted, dtype=bool).astype(np.uint8) * FLAG_COUNTED)
+    elif len(entries) == 3:
+        nul, num, fl = entries
+    else:
+        raise ValueError("a log is (nullifiers, numbers, counted, votes) or (nullifiers, numbers, flags)")
+    nul = np.ascontiguousarray(nul, dtype=np.uint64).reshape(-1, 4)
+    num = np.ascontiguousarray(num, dtype=np.uint64).reshape(-1)
+    fl = np.ascontiguousarray(fl, dtype=np.uint8).reshape(-1)
+    if not len(nul) == len(num) == len(fl):
+        raise ValueError(f"a log of {len(nul)} nullifiers, {len(num)} numbers and {len(fl)} flags")
+    return nul, num, fl
+
+
+def audit_log(ctx_or_none, entries, root=None, tally=None, commitments=()):
+    """Audits a published log against what was published beside it: `root` (4
+    felts), `tally` (yes, no) and earlier `commitments` [(root_i, n_i), ...], each
+    optional.  Returns an AuditReport whose status is the first reason that fires
+    (AUDIT_STATUS_TEXT), with the lowest offender as the witness.  With a Context
+    the audit runs on the device (csrc/ballot_audit.hip), with None on the host;
+    it needs no box and does not alter the log."""
+    nul, num, fl = _log_arrays(entries)
+    r = None if root is None else np.array([int(x) for x in root], dtype=np.uint64)
+    t = None if tally is None else np.array([int(x) for x in tally], dtype=np.uint64)
+    if (r is not None and r.shape != (4,)) or (t is not None and t.shape != (2,)):
+        raise ValueError("root is 4 field elements, tally is (yes, no)")
+    commitments = list(commitments)
+    cr = np.array([[int(x) for x in c[0]] for c in commitments], dtype=np.uint64).reshape(len(commitments), 4)
+    cn = np.array([int(c[1]) for c in commitments], dtype=np.uint64)
+    out = np.zeros(1, AUDIT_DTYPE)
+    rc = lib().qp_ballot_log_audit(None if ctx_or_none is None else ctx_or_none.h, nul.ctypes.data, num.ctypes.data,
+                                   fl.ctypes.data, len(num), None if r is None else r.ctypes.data,
+                                   None if t is None else t.ctypes.data, cr.ctypes.data, cn.ctypes.data,
+                                   len(commitments), out.ctypes.data)
+    if rc:
+        raise QpError(rc, lib().qp_ballot_box_last_error(None).decode())
+    o = out[0]
+    none = lambda v: None if int(v) == NOT_FOUND else int(v)  # noqa: E731
+    return AuditReport(int(o["status"]), none(o["witness"]), none(o["first"]), [int(x) for x in o["root"]],
+                       int(o["yes"]), int(o["no"]), int(o["counted"]))
 
 
 class BallotBox:
@@ -231,6 +292,57 @@ class BallotBox:
     @property
     def log_size(self):
         return self.commit_log()[1]
+
+    def roots_at(self, ms):
+        """Per m in `ms` (each 1..admitted) the root the log had at m entries: the
+        commitment (root, m) the box gave, or would have given, then.  Today's
+        commitment extends an earlier one iff `roots_at([n_i]) == [root_i]`.
+        Commits first, as `receipts` does."""
+        m = np.array([int(x) for x in ms], dtype=np.uint64).reshape(-1)
+        out = np.zeros((len(m), 4), np.uint64)
+        self._check(lib().qp_ballot_box_roots_at(self.h, m.ctypes.data, len(m), out.ctypes.data))
+        return [[int(x) for x in r] for r in out]
+
+    def root_at(self, m):
+        return self.roots_at([m])[0]
+
+    @classmethod
+    def restore(cls, ctx_or_device, proposal_id, roots, entries, cast_count=None, verifier=None, capacity=None,
+                root=None):
+        """Reopens a box from a published log (`entries`: what `entries()` returned, or
+        (nullifiers, numbers, flags)) and continues from it: the arguments of the
+        constructor, `cast_count` = the number the next ballot takes (None: the
+        log's last number + 1), `capacity` (None: the default, or what the log
+        needs), `root` = the log's published root, checked if given.  The log is
+        audited first (canonical entries, increasing numbers, the count rule, the
+        root); a log that fails raises QpError with the reason and the witness."""
+        nul, num, fl = _log_arrays(entries)
+        n = len(num)
+        prop = _digest(proposal_id, "proposal_id")
+        roots = list(roots)
+        if not 1 <= len(roots) <= MAX_ROOTS:
+            raise ValueError(f"{len(roots)} accepted roots: a ballot box needs 1 to {MAX_ROOTS}")
+        r = np.concatenate([_digest(x, "a root") for x in roots])
+        capacity = max(DEFAULT_CAPACITY, n) if capacity is None else int(capacity)
+        if cast_count is None:
+            cast_count = int(num[-1]) + 1 if n else 0
+        expect = None if root is None else _digest(root, "root")
+        self = cls.__new__(cls)
+        self.verifier = verifier
+        self.h = self._own_ctx = None
+        if ctx_or_device is None or isinstance(ctx_or_device, Context):
+            self.ctx = ctx_or_device
+        else:
+            self.ctx = self._own_ctx = Context(int(ctx_or_device))
+        h = ctypes.c_void_p()
+        rc = lib().qp_ballot_box_restore(None if self.ctx is None else self.ctx.h, prop, r, len(roots), capacity,
+                                         nul.ctypes.data, num.ctypes.data, fl.ctypes.data, n, int(cast_count),
+                                         None if expect is None else expect.ctypes.data, ctypes.byref(h))
+        if rc:
+            self.free()
+            raise QpError(rc, lib().qp_ballot_box_last_error(None).decode())
+        self.h = h
+        return self
 
     def receipts(self, seqs):
         """One BallotReceipt per log index in `seqs`, all under one (root, n): the

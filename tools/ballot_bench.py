@@ -18,6 +18,14 @@ host path side by side: `commit_log` from empty, `commit_log` after one more
 batch of 1024 and one of 65536, `find` of 1024 and of 65536 nullifiers (half of
 them absent), `receipts` of 1024 entries.
 
+The log audit, on a log of N honest entries (a quarter double votes):
+`audit_log` with the root and the tally claimed, the same with 1024 earlier
+commitments, `restore`, `roots_at` of 1024 sizes, and beside them what an
+auditor could do before: `cast_public` of the log's public inputs into a fresh
+box plus `commit_log`.  The host path of the same library runs at 2^16 entries
+(--audit-host-log-n), with the device at that size next to it.  --audit-only
+takes these records alone and puts them into the output file's `log_audit` key.
+
 Last, with --parent-lib FILE, one A/B of the path this work must not disturb:
 `cast_public`, distinct, 16 x 65536, in a fresh process per library (plain
 ctypes on the entry points both libraries have), 7 runs each; the new median
@@ -122,6 +130,56 @@ def log_commitment(BallotBox, ctx, rng, n, reps):
     return {k: _stats(v) for k, v in t.items()}, last
 
 
+def log_audit(qp, ctx, n, reps):
+    """the audit figures on one path (ctx None: the host path) for a log of n honest entries, a
+    quarter of them double votes: wall medians of `reps` runs after one warm-up run"""
+    BallotBox, audit_log = qp.BallotBox, qp.audit_log
+    pis = make_stream(np.random.default_rng(4), n, n // 4)
+    box = BallotBox(ctx, PROPOSAL, [ROOT_DIGEST], capacity=n)
+    box.cast_public(pis, reserve=False, raw=True)
+    entries, (root, got_n), tally = box.entries(), box.commit_log(), box.tally
+    ms = [(i + 1) * n // 1024 for i in range(1024)]
+    t = {}
+
+    def timed(key, fn):
+        runs = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            out = fn()
+            runs.append(time.perf_counter() - t0)
+            if hasattr(out, "free"):
+                out.free()
+        t[key] = _stats(runs[1:])
+        return out
+    roots = timed("roots_at_1024", lambda: box.roots_at(ms))
+    box.free()
+    commitments = list(zip(roots, ms))
+    assert got_n == n and roots[-1] == root
+    plain = timed("audit_root_tally", lambda: audit_log(ctx, entries, root=root, tally=tally))
+    full = timed("audit_root_tally_1024_commitments",
+                 lambda: audit_log(ctx, entries, root=root, tally=tally, commitments=commitments))
+    assert plain == full and (plain.status, plain.root, (plain.yes, plain.no)) == (0, root, tally)
+    timed("restore", lambda: BallotBox.restore(ctx, PROPOSAL, [ROOT_DIGEST], entries, capacity=n))
+    timed("restore_root_expected", lambda: BallotBox.restore(ctx, PROPOSAL, [ROOT_DIGEST], entries, capacity=n, root=root))
+
+    # what an auditor can do without the audit: the log's public inputs cast into a fresh box, then
+    # commit_log.  It checks less: no order, no witness, no earlier commitment, and it needs the
+    # ballots' public inputs, which the published log does not carry (rebuilt here from the log)
+    again = np.zeros((n, 13), np.uint64)
+    again[:, 0:4], again[:, 4:8] = PROPOSAL, ROOT_DIGEST
+    again[:, 8], again[:, 9:13] = entries[3], entries[0]
+
+    def recast():
+        b = BallotBox(ctx, PROPOSAL, [ROOT_DIGEST], capacity=n)
+        b.cast_public(again, reserve=False, raw=True)
+        got = (b.commit_log()[0], b.tally)
+        b.free()
+        return got
+    # the recast box numbers its ballots 0..n-1; the stream had no rejected ballot, so the roots agree
+    assert timed("cast_public_plus_commit_log", recast) == (root, tally)
+    return t, (root, tally, roots[::128], tuple(plain))
+
+
 def ab_cast_child(lib_path, log_n, reps):
     """the A/B's child: cast_public, distinct, 16 batches, through plain ctypes on `lib_path`"""
     import ctypes
@@ -160,8 +218,30 @@ def ab_cast_child(lib_path, log_n, reps):
     print(json.dumps({"lib_sha16": lib_sha16(lib_path), "wall_s": _stats(wall[1:]), "runs_s": wall[1:], "tally": tally}))
 
 
+def audit_records(qp, ctx, args, sha):
+    """audit_log, restore and roots_at: the device at 2^log_n entries; the device and the host path
+    of the same library side by side at 2^audit_host_log_n (the host path hashes 2 n permutations
+    on one thread, 6 s per 2^20-leaf root: its figures are taken at the smaller size, labelled scaled)"""
+    n, hn = 1 << args.log_n, 1 << args.audit_host_log_n
+    dev, dlast = log_audit(qp, ctx, n, args.reps)
+    sdev, slast = log_audit(qp, ctx, hn, args.reps)
+    host, hlast = log_audit(qp, None, hn, args.reps)  # at the scaled size the host path affords every run
+    assert slast == hlast, "device and host audits disagree"
+    return {"lib_sha16": sha, "entries": n, "doubles": n // 4, "scaled_entries": hn, "log_root": dlast[0],
+            "results_equal_at_scaled": True,
+            "what": "wall of one call each, median of `runs` runs after one warm-up run, the same count on the device "
+                    "and on the host path; the log and the claims are host arrays, so "
+                    "audit_log and restore include the log's upload; roots_at: 1024 sizes spread over the log, on a "
+                    "committed box; cast_public_plus_commit_log: what an auditor could do before (it checks less); "
+                    "*_scaled: the same at scaled_entries, where the host path (ctx None) is run; reported, not gated",
+            "device": dev, "device_scaled": sdev, "host_scaled": host,
+            "device_wall_over_host_wall_scaled": {k: sdev[k]["median"] / host[k]["median"] for k in sdev}}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--audit-only", action="store_true", help="only the log audit's records, into --out's log_audit key")
+    ap.add_argument("--audit-host-log-n", type=int, default=16, help="log2 of the size the host path's audit runs at")
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--proofs", type=int, default=1024, help="real voting proofs of the cast / verify_batch pair (0 = skip)")
@@ -181,6 +261,17 @@ def main():
     cap = 2 * n
     rng = np.random.default_rng(1)
     ctx = qp_wormhole.Context(0)
+    if args.audit_only:
+        # the log audit's records alone, into the file's "log_audit" key; the other records stay as they are
+        with open(args.out) as f:
+            out = json.load(f)
+        out["log_audit"] = audit_records(qp_wormhole, ctx, args, lib_sha16(LIB_PATH))
+        ctx.close()
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        print(json.dumps(out["log_audit"]))
+        return
     out = {"lib_sha16": lib_sha16(LIB_PATH), "ballots": n, "capacity": cap, "reps": args.reps,
            "what": "wall: perf_counter around the cast_public calls of the whole stream, fresh box per run, one warm-up "
                    "run dropped; *_ms: HIP events summed over the stream's calls; host: the same library with ctx None",
@@ -260,6 +351,7 @@ def main():
                 "receipts: 1024 random entries, BallotReceipt objects included; host: the same library with ctx None",
         "device": dev, "host": host,
         "device_wall_over_host_wall": {k: dev[k]["median"] / host[k]["median"] for k in dev}}
+    out["log_audit"] = audit_records(qp_wormhole, ctx, args, out["lib_sha16"])
     ctx.close()
     out["ab_cast_public_16x65536"] = "not measured"
     if args.parent_lib:
