@@ -666,6 +666,107 @@ int qp_ballot_box_restore(qp_ctx *ctx, const uint64_t proposal_id[4], const uint
                           const uint8_t *flags, uint64_t n, uint64_t cast_count,
                           const uint64_t *expect_root /* NULL: none */, qp_ballot_box **out);
 
+/* ---- transfer ledger: settle Wormhole transfers once per nullifier ------------
+ * The settler's side of the Wormhole circuit.  A verified proof says only that
+ * some unspent transfer of `funding_amount` under storage root `root_hash` may
+ * be paid to `exit_account`, with this `nullifier` ("its purpose is to prevent
+ * double-spending"); the reference has no object that uses it.  A ledger is
+ * opened with the storage roots of the blocks the settler knows (1 to 4096),
+ * optionally the public inputs of the aggregator's padding proof, and a
+ * capacity of admitted transfers.  The 16 public inputs are nullifier[0:4]
+ * root_hash[4:8] funding_amount[8:12] exit_account[12:16] (wormhole/circuit/
+ * src/inputs.rs:12-19,92-97); funding_amount is four 32-bit limbs, most
+ * significant first (felts_to_u128).  Every transfer cast gets a number: its
+ * position in the stream of all transfers cast into the ledger, rejected ones
+ * included, from 0.  Its status is the first of these checks that fails, in
+ * this order:                                                                  */
+typedef enum {
+    QP_TRANSFER_CREDITED = 0,       /* admitted and credited; first = its own number */
+    QP_TRANSFER_PROOF_REJECTED = 1, /* the verifier's verdict is not QP_VERIFY_OK (it is in verify_status) */
+    QP_TRANSFER_MALFORMED = 2,      /* a public input >= p (reachable only through qp_ledger_cast_public) */
+    QP_TRANSFER_PADDING = 3,        /* all 16 public inputs equal the ledger's padding inputs */
+    QP_TRANSFER_BAD_AMOUNT = 4,     /* an amount limb >= 2^32 (the reference's felts_to_u128 refuses it) */
+    QP_TRANSFER_UNKNOWN_ROOT = 5,   /* root_hash is not among the accepted roots */
+    QP_TRANSFER_DOUBLE_SPEND = 6    /* an earlier transfer with this nullifier was credited; first = its number */
+} qp_transfer_status;
+/* A transfer that passes the first six checks is admitted and takes a log
+ * entry: nullifier, number, amount limbs, exit account, flags (bit 0 =
+ * credited).  Of the admitted transfers with one nullifier the one with the
+ * lowest number is credited, inside a batch and across batches; a transfer
+ * rejected by an earlier check does not spend its nullifier.  A credited
+ * transfer adds its amount to its exit account's total.  Totals may exceed
+ * 2^128 and nothing is rejected for that: an account's total is reported as four
+ * limb sums, total = sum over i of sums[i] << (96 - 32 i); with at most 2^31
+ * entries each sum stays below 2^63.  Statuses, `first`, the log and every total
+ * are a function of the transfer stream alone: not of how it is cut into
+ * batches, of the path (device or host) or of the device's scheduling.
+ *
+ * With a context the log, both tables (nullifiers, accounts) and the sums live
+ * on the device and the ledger uses the context's stream (free it before
+ * qp_ctx_destroy): a cast uploads the raw public inputs and the verdicts, and
+ * the screen, the pack, the insert and the credit run there (ledger.hip).
+ * ctx == NULL runs the same semantics on the host.  Every call is all or
+ * nothing: a refused call leaves every count, the log and the totals as they
+ * were (out[] is then unspecified).  A device step that fails, or a set error
+ * word of the kernels' cannot-be-reached branches, is QP_ERR_HIP and leaves the
+ * ledger dead: later calls return QP_ERR_STATE.                               */
+typedef struct qp_ledger qp_ledger;
+typedef struct {
+    uint32_t status;         /* qp_transfer_status */
+    uint32_t verify_status;  /* qp_verify_status of the proof (cast_public: verdicts[i]) */
+    uint64_t number;         /* the transfer's number */
+    uint64_t first;          /* double spend: the credited transfer's number; else number */
+} qp_transfer_result;
+/* roots [nroots][4] canonical, 1 <= nroots <= 4096 (a root given twice is held once); padding_pis:
+ * the 16 canonical public inputs of the padding proof, or NULL for none; 1 <= capacity <= 2^31
+ * admitted transfers.  Device memory: 93 bytes per entry of capacity and 40 per table slot (the
+ * power of two >= 2 capacity slots).                                                        */
+int qp_ledger_new(qp_ctx *ctx /* NULL: host */, const uint64_t *roots, uint32_t nroots,
+                  const uint64_t *padding_pis /* [16] or NULL */, uint64_t capacity, qp_ledger **out);
+void qp_ledger_free(qp_ledger *l);
+/* the reason of the ledger's last refused call; l == NULL: of this thread's last refused qp_ledger_new */
+const char *qp_ledger_last_error(const qp_ledger *l);
+/* one more accepted root (a new block's); a root the ledger already accepts: QP_OK, held once; a 4097th: QP_ERR_ARG */
+int qp_ledger_accept_root(qp_ledger *l, const uint64_t root[4]);
+/* moves the ledger to a log and tables for new_capacity >= admitted (and >= 1, <= 2^31): the log is
+ * copied, both tables and the sums are rebuilt from the credited entries; everything handed out stays true */
+int qp_ledger_reserve(qp_ledger *l, uint64_t new_capacity);
+/* transfers cast, admitted, credited, accounts credited so far, capacity (each may be NULL) */
+int qp_ledger_state(const qp_ledger *l, uint64_t *cast, uint64_t *admitted, uint64_t *credited, uint64_t *accounts,
+                    uint64_t *capacity);
+/* verifies proofs[0..n) with v, a verifier of a circuit with 16 public inputs (else QP_ERR_ARG), then
+ * casts them: out[n].  More admitted transfers than the capacity has room for: QP_ERR_ARG (call
+ * qp_ledger_reserve); n == 0: QP_OK; n > 2^22: QP_ERR_ARG                                   */
+int qp_ledger_cast(qp_ledger *l, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens,
+                   uint32_t n, qp_transfer_result *out);
+/* the routine-level seam: public inputs pis[n][16] of proofs verified elsewhere (verdicts[i] != 0
+ * marks a rejected one; NULL = all verified), e.g. the leaves of a verified aggregation root; also
+ * the small-shape test surface of the kernels.  n <= 2^22 per call, more is QP_ERR_ARG        */
+int qp_ledger_cast_public(qp_ledger *l, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                          qp_transfer_result *out);
+/* seq_out[i] = the log index of the credited entry with nullifiers[i][4] (canonical, else QP_ERR_ARG),
+ * or UINT64_MAX if that nullifier was never admitted                                        */
+int qp_ledger_find(qp_ledger *l, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out);
+/* the log, entries [first, first + k) in admission order: nullifiers [k][4], numbers [k], amounts
+ * [k][4] (32-bit limbs, most significant first), accounts [k][4], flags [k]; each may be NULL */
+int qp_ledger_entries(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
+                      uint32_t *amounts, uint64_t *accounts, uint8_t *flags);
+/* the accounts credited so far, [first, first + k) in the order of the log index of each account's
+ * first credited entry (a function of the stream alone; qp_ledger_state gives their count):
+ * accounts [k][4], sums [k][4], first_seq [k]; each may be NULL                             */
+int qp_ledger_payouts(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accounts, uint64_t *sums,
+                      uint64_t *first_seq);
+/* the limb sums of accounts[k][4] given by the caller (canonical, else QP_ERR_ARG): sums [k][4],
+ * found [k]; an account never credited gives zeros and found = 0; sums and found may be NULL   */
+int qp_ledger_totals_for(qp_ledger *l, const uint64_t *accounts, uint32_t k, uint64_t *sums, uint8_t *found);
+/* the audit: out = credited, admitted, then the four limb sums over all credited entries, recomputed
+ * from the log alone; the grand total equals the sum of the payouts                         */
+int qp_ledger_recount(qp_ledger *l, uint64_t out[6]);
+/* HIP-event times of the last device cast (ms): [0] the upload of the public inputs and verdicts,
+ * [1] screen to credit, the read-back of the admitted count included.  Diagnostic entry point
+ * (tools/ledger_bench.py); 0 on the host path.                                              */
+int qp_ledger_cast_times(const qp_ledger *l, double ms[2]);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

@@ -1,0 +1,670 @@
+// ledger.cpp — the qp_ledger_* entry points (qpgpu.h): Wormhole transfers
+// settled after verification.  Each nullifier is admitted once, only storage
+// roots the ledger knows are accepted, the padding proof's inputs are set
+// aside, and the amounts are credited to the exit accounts.  With a context the
+// raw public inputs are uploaded and screened, packed, inserted and credited on
+// the device (ledger.hip); without one the same semantics run on the host
+// (ql::HostLedger).  Both paths state the checks once, in ledger_table.h.
+#include "../../include/qpgpu.h"
+#include <string.h>
+#include <algorithm>
+#include <memory>
+#include <new>
+#include <string>
+#include <utility>
+#include <vector>
+#include "ctx.h"
+#include "ledger_kernels.h"
+#include "ledger_table.h"
+#include "verifier.h"
+
+static_assert(sizeof(qp_transfer_result) == sizeof(ql::Result) && sizeof(ql::Result) == 24 &&
+                  sizeof(qpk::LedgerResult) == 24,
+              "qp_transfer_result layout");
+static_assert(QP_TRANSFER_CREDITED == ql::CREDITED && QP_TRANSFER_PROOF_REJECTED == ql::PROOF_REJECTED &&
+                  QP_TRANSFER_MALFORMED == ql::MALFORMED && QP_TRANSFER_PADDING == ql::PADDING &&
+                  QP_TRANSFER_BAD_AMOUNT == ql::BAD_AMOUNT && QP_TRANSFER_UNKNOWN_ROOT == ql::UNKNOWN_ROOT &&
+                  QP_TRANSFER_DOUBLE_SPEND == ql::DOUBLE_SPEND,
+              "qp_transfer_status and ledger_table.h differ");
+
+namespace {
+// the device half of a ledger for one capacity: the log, the two tables, the sums
+struct LedgerTables {
+  DevBuf nul, num, amt, acc, flags, astay, nslot, aslot, sum;
+  uint64_t mask = 0;
+  qpk::LedgerDev dev() const {
+    return qpk::LedgerDev{nul.p,          num.p,
+                          amt.as<uint32_t>(),   acc.p,
+                          flags.as<uint8_t>(),  astay.as<uint32_t>(),
+                          nslot.as<uint32_t>(), aslot.as<uint32_t>(),
+                          sum.as<unsigned long long>(), mask};
+  }
+};
+
+// entries per launch of the lookups and gathers (their buffers hold this many)
+constexpr uint32_t QUERY_BATCH = 8192;
+}  // namespace
+
+struct qp_ledger {
+  qp_ctx *ctx = nullptr;  // null: the host path
+  std::string err;
+  bool dead = false;  // a device step failed part-way, or the defensive error word was set: no further calls
+  ql::Screen screen;
+  uint64_t cast = 0;
+  ql::Packed pk;  // the host path's batch in flight
+  ql::HostLedger host;
+  // ---- device path
+  uint64_t capacity = 0, count = 0, credited = 0, accounts = 0;  // credited / accounts: the device counters as of the last cast
+  LedgerTables t;
+  DevBuf d_roots, d_ctr, d_audit;
+  uint32_t batch_room = 0;                          // transfers the per-batch buffers hold
+  DevBuf d_pis, d_ver, d_res, d_blk, d_pos, d_stay;  // per batch: inputs, verdicts, results, block counts (+ total), pos, stay
+  DevBuf d_pblk, d_payee;                           // the payees' block counts (+ total); the payees
+  uint64_t payee_room = 0;                          // log entries d_pblk / d_payee are sized for
+  bool payee_valid = false;                         // d_payee lists the accounts of the log as it is
+  DevBuf d_q, d_qsum, d_qaux;                       // per lookup / gather batch (QUERY_BATCH entries)
+  TimingEvents<3> ev;                               // upload start, upload end, resolve end of the last cast
+  float ms[2] = {0, 0};
+  uint64_t admitted() const { return ctx ? count : host.count(); }
+  uint64_t cap() const { return ctx ? capacity : host.capacity; }
+  uint64_t ncredited() const { return ctx ? credited : host.credited; }
+  uint64_t naccounts() const { return ctx ? accounts : host.accounts(); }
+};
+
+namespace {
+thread_local std::string g_new_err;  // why the last qp_ledger_new on this thread was refused
+
+int refuse_new(qp_ctx *c, const std::string &why) {
+  g_new_err = "qp_ledger_new: " + why;
+  if (c) c->err = g_new_err;
+  return QP_ERR_ARG;
+}
+
+int alloc_tables(qp_ledger *l, uint64_t capacity, LedgerTables &t) {
+  const uint64_t S = ql::table_slots(capacity);
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, t.nul.alloc(capacity * 4));
+  QP_HIP_TRY(l, t.num.alloc(capacity));
+  QP_HIP_TRY(l, t.amt.alloc(capacity * 2));
+  QP_HIP_TRY(l, t.acc.alloc(capacity * 4));
+  QP_HIP_TRY(l, t.flags.alloc((capacity + 7) / 8));
+  QP_HIP_TRY(l, t.astay.alloc((capacity + 1) / 2));
+  QP_HIP_TRY(l, t.nslot.alloc(S / 2));
+  QP_HIP_TRY(l, t.aslot.alloc(S / 2));
+  QP_HIP_TRY(l, t.sum.alloc(S * 4));
+  t.mask = S - 1;
+  QP_HIP_TRY(l, hipMemsetAsync(t.nslot.p, 0xFF, S * 4, s));
+  QP_HIP_TRY(l, hipMemsetAsync(t.aslot.p, 0xFF, S * 4, s));
+  QP_HIP_TRY(l, hipMemsetAsync(t.sum.p, 0, S * 32, s));
+  return QP_OK;
+}
+
+int dead_ledger(qp_ledger *l, const char *fn) {
+  l->err = std::string(fn) + ": an earlier call on this ledger failed on the device part-way; its state is not known";
+  return QP_ERR_STATE;
+}
+
+int bad_alloc(qp_ledger *l, const char *fn) {
+  l->err = std::string(fn) + ": out of host memory";
+  return QP_ERR_OOM;
+}
+
+// a failed device step leaves the ledger dead
+int device_step(qp_ledger *l, int rc) {
+  if (rc) l->dead = true;
+  return rc;
+}
+
+// the defensive error word after a launch (copied by the caller, stream synchronised)
+int error_word(qp_ledger *l, const char *fn, uint32_t err) {
+  if (!err) return QP_OK;
+  l->err = std::string(fn) +
+           (err & 1 ? ": the nullifier table's probe found no slot"
+                    : err & 2 ? ": a nullifier slot holds a later entry than the one that stopped at it"
+                              : err & 4 ? ": the account table's probe found no slot" : ": a table slot holds no log entry") +
+           " (an internal invariant broke)";
+  return QP_ERR_HIP;
+}
+
+int over_capacity(qp_ledger *l, const char *fn, uint64_t k) {
+  l->err = std::string(fn) + ": " + std::to_string(l->admitted()) + " + " + std::to_string(k) +
+           " admitted transfers exceed the capacity " + std::to_string(l->cap()) + "; call qp_ledger_reserve first";
+  return QP_ERR_ARG;
+}
+
+int upload_roots(qp_ledger *l) {
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  QP_HIP_TRY(l, hipMemcpyAsync(l->d_roots.p, l->screen.roots.data(), l->screen.roots.size() * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int batch_buffers(qp_ledger *l, uint32_t n) {
+  if (n <= l->batch_room) return QP_OK;
+  l->batch_room = 0;
+  QP_HIP_TRY(l, l->d_pis.alloc((size_t)n * ql::NPI));
+  QP_HIP_TRY(l, l->d_ver.alloc(((size_t)n + 1) / 2));
+  QP_HIP_TRY(l, l->d_res.alloc((size_t)n * 3));
+  QP_HIP_TRY(l, l->d_blk.alloc(((size_t)qpk::ledger_blocks(n) + 2) / 2));
+  QP_HIP_TRY(l, l->d_pos.alloc(((size_t)n + 1) / 2));
+  QP_HIP_TRY(l, l->d_stay.alloc(((size_t)n + 1) / 2));
+  l->batch_room = n;
+  return QP_OK;
+}
+
+// The device steps of one batch.  The raw inputs go up; screen and scan run; the host reads the
+// admitted count k back and refuses an overflow (*refused, nothing of the ledger written yet);
+// then pack, insert, resolve and credit.
+int cast_device(qp_ledger *l, const char *fn, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                ql::Result *out, bool *refused) {
+  qp_ctx *c = l->ctx;
+  hipStream_t s = c->stream;
+  QP_HIP_TRY(l, hipSetDevice(c->device));
+  for (hipEvent_t &e : l->ev.e)
+    if (!e) QP_HIP_TRY(l, hipEventCreate(&e));
+  if (int rc = batch_buffers(l, n)) return rc;
+  const qpk::LedgerDev d = l->t.dev();
+  qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
+  qpk::LedgerCounters now;
+  qpk::LedgerScreen sc;
+  sc.roots = l->d_roots.p;
+  sc.nroots = l->screen.nroots();
+  sc.has_padding = l->screen.has_padding;
+  memcpy(sc.padding, l->screen.padding, sizeof sc.padding);
+  const uint32_t nb = qpk::ledger_blocks(n);
+  uint32_t *blk = l->d_blk.as<uint32_t>(), *d_ver = verdicts ? l->d_ver.as<uint32_t>() : nullptr;
+  qpk::LedgerResult *res = l->d_res.as<qpk::LedgerResult>();
+  uint32_t k = 0;
+  QP_HIP_TRY(l, hipEventRecord(l->ev.e[0], s));
+  QP_HIP_TRY(l, hipMemcpyAsync(l->d_pis.p, pis, (size_t)n * ql::NPI * 8, hipMemcpyHostToDevice, s));
+  if (verdicts) QP_HIP_TRY(l, hipMemcpyAsync(d_ver, verdicts, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipEventRecord(l->ev.e[1], s));
+  qpk::ledger_screen(sc, l->d_pis.p, d_ver, n, l->cast, res, blk, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  qpk::ledger_scan(blk, nb, blk + nb, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipMemcpyAsync(&k, blk + nb, 4, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  if (k > n) {
+    l->err = std::string(fn) + ": the pack's scan counted more admitted transfers than were cast (an internal invariant broke)";
+    return QP_ERR_HIP;
+  }
+  if (k > l->capacity - l->count) {
+    *refused = true;
+    return over_capacity(l, fn, k);
+  }
+  qpk::ledger_pack(d, l->d_pis.p, res, blk, n, (uint32_t)l->count, l->d_pos.as<uint32_t>(), s);
+  QP_HIP_TRY(l, hipGetLastError());
+  qpk::ledger_insert(d, (uint32_t)l->count, k, l->d_stay.as<uint32_t>(), ctr, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  qpk::ledger_resolve(d, (uint32_t)l->count, k, l->d_stay.as<uint32_t>(), l->d_pos.as<uint32_t>(), res, ctr, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipEventRecord(l->ev.e[2], s));
+  QP_HIP_TRY(l, hipMemcpyAsync(out, res, (size_t)n * sizeof(ql::Result), hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  QP_HIP_TRY(l, hipEventElapsedTime(&l->ms[0], l->ev.e[0], l->ev.e[1]));
+  QP_HIP_TRY(l, hipEventElapsedTime(&l->ms[1], l->ev.e[1], l->ev.e[2]));
+  if (int rc = error_word(l, fn, now.err)) return rc;
+  l->count += k;
+  l->credited = now.credited;
+  l->accounts = now.accounts;
+  if (k) l->payee_valid = false;
+  return QP_OK;
+}
+
+// pis [n][16], verdicts (may be null): screen, pack, refuse an overflow, settle
+int cast_screened(qp_ledger *l, const char *fn, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                  ql::Result *out) {
+  if (l->ctx) {
+    bool refused = false;
+    const int rc = cast_device(l, fn, pis, verdicts, n, out, &refused);
+    if (rc) {
+      if (!refused) l->dead = true;
+      return rc;
+    }
+  } else {
+    ql::screen_and_pack(l->screen, pis, verdicts, n, l->cast, out, l->pk);
+    if (l->pk.size() > l->cap() - l->admitted()) return over_capacity(l, fn, l->pk.size());
+    l->host.admit_packed(l->pk, out);
+  }
+  l->cast += n;
+  return QP_OK;
+}
+
+int query_buffers(qp_ledger *l) {
+  if (l->d_q.p) return QP_OK;
+  QP_HIP_TRY(l, l->d_qsum.alloc((size_t)QUERY_BATCH * 4));
+  QP_HIP_TRY(l, l->d_qaux.alloc(QUERY_BATCH));
+  QP_HIP_TRY(l, l->d_q.alloc((size_t)QUERY_BATCH * 4));
+  return QP_OK;
+}
+
+int find_device(qp_ledger *l, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (int rc = query_buffers(l)) return rc;
+  qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
+  std::vector<uint32_t> h(std::min(k, QUERY_BATCH));
+  uint32_t err = 0;
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(QUERY_BATCH, k - done);
+    QP_HIP_TRY(l, hipMemcpyAsync(l->d_q.p, nullifiers + (size_t)done * 4, (size_t)nb * 32, hipMemcpyHostToDevice, s));
+    qpk::ledger_find(l->t.dev(), (uint32_t)l->count, l->d_q.p, nb, l->d_qaux.as<uint32_t>(), ctr, s);
+    QP_HIP_TRY(l, hipGetLastError());
+    QP_HIP_TRY(l, hipMemcpyAsync(h.data(), l->d_qaux.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipStreamSynchronize(s));
+    if (int rc = error_word(l, "qp_ledger_find", err)) return rc;
+    for (uint32_t i = 0; i < nb; i++) seq_out[done + i] = h[i] == ql::EMPTY ? ql::NOT_FOUND : h[i];
+    done += nb;
+  }
+  return QP_OK;
+}
+
+int totals_device(qp_ledger *l, const uint64_t *accounts, uint32_t k, uint64_t *sums, uint8_t *found) {
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (int rc = query_buffers(l)) return rc;
+  qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
+  std::vector<uint32_t> h(std::min(k, QUERY_BATCH));
+  uint32_t err = 0;
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(QUERY_BATCH, k - done);
+    QP_HIP_TRY(l, hipMemcpyAsync(l->d_q.p, accounts + (size_t)done * 4, (size_t)nb * 32, hipMemcpyHostToDevice, s));
+    qpk::ledger_totals(l->t.dev(), (uint32_t)l->count, l->d_q.p, nb, l->d_qsum.as<unsigned long long>(),
+                       l->d_qaux.as<uint32_t>(), ctr, s);
+    QP_HIP_TRY(l, hipGetLastError());
+    if (sums) QP_HIP_TRY(l, hipMemcpyAsync(sums + (size_t)done * 4, l->d_qsum.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(h.data(), l->d_qaux.p, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipStreamSynchronize(s));
+    if (int rc = error_word(l, "qp_ledger_totals_for", err)) return rc;
+    if (found)
+      for (uint32_t i = 0; i < nb; i++) found[done + i] = h[i] != 0;
+    done += nb;
+  }
+  return QP_OK;
+}
+
+// d_payee = the log entries that own their account slot, in log order: the accounts in the order of
+// their first credited entry
+int payees_device(qp_ledger *l) {
+  if (l->payee_valid) return QP_OK;
+  hipStream_t s = l->ctx->stream;
+  const uint32_t count = (uint32_t)l->count, nb = qpk::ledger_blocks(count);
+  if (l->payee_room < l->count) {
+    l->payee_room = 0;
+    QP_HIP_TRY(l, l->d_pblk.alloc(((size_t)nb + 2) / 2));
+    QP_HIP_TRY(l, l->d_payee.alloc((l->count + 1) / 2));
+    l->payee_room = l->count;
+  }
+  if (count) {
+    uint32_t *blk = l->d_pblk.as<uint32_t>(), total = 0;
+    qpk::ledger_payee_count(l->t.dev(), count, blk, s);
+    QP_HIP_TRY(l, hipGetLastError());
+    qpk::ledger_scan(blk, nb, blk + nb, s);
+    QP_HIP_TRY(l, hipGetLastError());
+    qpk::ledger_payee_write(l->t.dev(), count, blk, l->d_payee.as<uint32_t>(), s);
+    QP_HIP_TRY(l, hipGetLastError());
+    QP_HIP_TRY(l, hipMemcpyAsync(&total, blk + nb, 4, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipStreamSynchronize(s));
+    if (total != l->accounts) {
+      l->err = "qp_ledger_payouts: " + std::to_string(total) + " entries own an account slot, the ledger counts " +
+               std::to_string(l->accounts) + " accounts (an internal invariant broke)";
+      return QP_ERR_HIP;
+    }
+  }
+  l->payee_valid = true;
+  return QP_OK;
+}
+
+int payouts_device(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accounts, uint64_t *sums, uint64_t *first_seq) {
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (int rc = query_buffers(l)) return rc;
+  if (int rc = payees_device(l)) return rc;
+  for (uint64_t done = 0; done < k;) {
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(QUERY_BATCH, k - done);
+    qpk::ledger_payouts(l->t.dev(), l->d_payee.as<uint32_t>() + first + done, nb, l->d_q.p,
+                        l->d_qsum.as<unsigned long long>(), l->d_qaux.p, s);
+    QP_HIP_TRY(l, hipGetLastError());
+    if (accounts) QP_HIP_TRY(l, hipMemcpyAsync(accounts + done * 4, l->d_q.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    if (sums) QP_HIP_TRY(l, hipMemcpyAsync(sums + done * 4, l->d_qsum.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    if (first_seq) QP_HIP_TRY(l, hipMemcpyAsync(first_seq + done, l->d_qaux.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipStreamSynchronize(s));
+    done += nb;
+  }
+  return QP_OK;
+}
+
+int reserve_device(qp_ledger *l, uint64_t new_capacity) {
+  // a new log and new tables beside the old; the ledger moves over only once all of it succeeded
+  qp_ctx *c = l->ctx;
+  hipStream_t s = c->stream;
+  LedgerTables nt;
+  qpk::LedgerCounters now;
+  QP_HIP_TRY(l, hipSetDevice(c->device));
+  if (int rc = alloc_tables(l, new_capacity, nt)) return rc;
+  const qpk::LedgerDev od = l->t.dev(), nd = nt.dev();
+  qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
+  if (l->count) {
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.nullifier, od.nullifier, l->count * 32, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.number, od.number, l->count * 8, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.amount, od.amount, l->count * 16, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.account, od.account, l->count * 32, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.flags, od.flags, l->count, hipMemcpyDeviceToDevice, s));
+    QP_HIP_TRY(l, hipMemcpyAsync(nd.astay, od.astay, l->count * 4, hipMemcpyDeviceToDevice, s));
+    qpk::ledger_rebuild(nd, (uint32_t)l->count, ctr, s);
+    QP_HIP_TRY(l, hipGetLastError());
+  }
+  QP_HIP_TRY(l, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  if (int rc = error_word(l, "qp_ledger_reserve", now.err)) return device_step(l, rc);
+  l->t = std::move(nt);
+  l->capacity = new_capacity;
+  l->payee_valid = false;  // the payees are the same entries, but the list is cheap and this keeps one rule
+  return QP_OK;
+}
+
+int canonical_keys(qp_ledger *l, const char *fn, const char *what, const uint64_t *keys, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++)
+    for (uint32_t f = 0; f < 4; f++)
+      if (keys[(size_t)i * 4 + f] >= ql::P) {
+        l->err = std::string(fn) + ": " + what + " at position " + std::to_string(i) + " felt " + std::to_string(f) +
+                 " is not a canonical field element";
+        return QP_ERR_ARG;
+      }
+  return QP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int qp_ledger_new(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const uint64_t *padding_pis, uint64_t capacity,
+                  qp_ledger **out) {
+  if (!out) return QP_ERR_ARG;
+  *out = nullptr;
+  if (!roots) return refuse_new(c, "null roots");
+  if (!nroots || nroots > ql::MAX_ROOTS)
+    return refuse_new(c, std::to_string(nroots) + " accepted roots: a ledger needs 1 to " + std::to_string(ql::MAX_ROOTS));
+  if (!ql::canonical(roots, (size_t)nroots * 4)) return refuse_new(c, "a root is not four canonical field elements");
+  if (padding_pis && !ql::canonical(padding_pis, ql::NPI))
+    return refuse_new(c, "the padding inputs are not 16 canonical field elements");
+  if (!capacity || capacity > ql::MAX_CAPACITY)
+    return refuse_new(c, "capacity " + std::to_string(capacity) + ": it must be 1 to 2^31 admitted transfers");
+  std::unique_ptr<qp_ledger> l(new (std::nothrow) qp_ledger);
+  if (!l) return QP_ERR_OOM;
+  l->ctx = c;
+  if (padding_pis) {
+    l->screen.has_padding = true;
+    memcpy(l->screen.padding, padding_pis, sizeof l->screen.padding);
+  }
+  try {
+    for (uint32_t i = 0; i < nroots; i++)
+      if (!l->screen.accepts(roots + 4 * i)) l->screen.add_root(roots + 4 * i);
+    if (!c) {
+      l->host.open(capacity);
+      *out = l.release();
+      return QP_OK;
+    }
+  } catch (const std::bad_alloc &) {
+    g_new_err = "qp_ledger_new: out of host memory";
+    return QP_ERR_OOM;
+  }
+  int rc = QP_OK;
+  auto device_open = [&]() -> int {
+    QP_HIP_TRY(l, hipSetDevice(c->device));
+    if ((rc = alloc_tables(l.get(), capacity, l->t))) return rc;
+    QP_HIP_TRY(l, l->d_roots.alloc((size_t)ql::MAX_ROOTS * 4));
+    QP_HIP_TRY(l, l->d_ctr.alloc((sizeof(qpk::LedgerCounters) + 7) / 8));
+    QP_HIP_TRY(l, l->d_audit.alloc(6));
+    QP_HIP_TRY(l, hipMemsetAsync(l->d_ctr.p, 0, sizeof(qpk::LedgerCounters), c->stream));
+    return upload_roots(l.get());
+  };
+  if ((rc = device_open())) {
+    g_new_err = c->err = "qp_ledger_new: " + l->err;
+    return rc;
+  }
+  l->capacity = capacity;
+  *out = l.release();
+  return QP_OK;
+}
+
+void qp_ledger_free(qp_ledger *l) {
+  if (!l) return;
+  if (l->ctx) (void)hipSetDevice(l->ctx->device);
+  delete l;
+}
+
+const char *qp_ledger_last_error(const qp_ledger *l) { return l ? l->err.c_str() : g_new_err.c_str(); }
+
+int qp_ledger_accept_root(qp_ledger *l, const uint64_t root[4]) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_accept_root");
+  if (!root || !ql::canonical(root, 4)) {
+    l->err = "qp_ledger_accept_root: the root must be four canonical field elements";
+    return QP_ERR_ARG;
+  }
+  if (l->screen.accepts(root)) return QP_OK;
+  if (l->screen.nroots() >= ql::MAX_ROOTS) {
+    l->err = "qp_ledger_accept_root: the ledger already accepts " + std::to_string(ql::MAX_ROOTS) + " roots, the most";
+    return QP_ERR_ARG;
+  }
+  try {
+    l->screen.add_root(root);
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_accept_root");
+  }
+  return l->ctx ? device_step(l, upload_roots(l)) : QP_OK;
+}
+
+int qp_ledger_cast_public(qp_ledger *l, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
+                          qp_transfer_result *out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_cast_public");
+  if (!n) return QP_OK;
+  if (n > ql::MAX_BATCH) {
+    l->err = "qp_ledger_cast_public: " + std::to_string(n) + " transfers in one call; the most is 2^22";
+    return QP_ERR_ARG;
+  }
+  if (!pis || !out) {
+    l->err = "qp_ledger_cast_public: null buffer";
+    return QP_ERR_ARG;
+  }
+  try {
+    return cast_screened(l, "qp_ledger_cast_public", pis, verdicts, n, reinterpret_cast<ql::Result *>(out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_cast_public");
+  }
+}
+
+int qp_ledger_cast(qp_ledger *l, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens, uint32_t n,
+                   qp_transfer_result *out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_cast");
+  const uint32_t npi = qv::public_input_count(v);
+  if (npi != ql::NPI) {
+    l->err = !v ? "qp_ledger_cast: null verifier"
+                : !npi ? "qp_ledger_cast: the verifier is not usable"
+                       : "qp_ledger_cast: the verifier's circuit has " + std::to_string(npi) +
+                             " public inputs; the Wormhole circuit's has " + std::to_string(ql::NPI);
+    return QP_ERR_ARG;
+  }
+  if (!n) return QP_OK;
+  if (n > ql::MAX_BATCH) {
+    l->err = "qp_ledger_cast: " + std::to_string(n) + " transfers in one call; the most is 2^22";
+    return QP_ERR_ARG;
+  }
+  if (!proofs || !lens || !out) {
+    l->err = "qp_ledger_cast: null buffer";
+    return QP_ERR_ARG;
+  }
+  try {
+    std::vector<uint32_t> verdicts(n);
+    const int rc = qp_verifier_verify(v, proofs, lens, n, verdicts.data());
+    if (rc) {
+      l->err = std::string("qp_ledger_cast: qp_verifier_verify: ") + qp_verifier_last_error(v);
+      return rc;
+    }
+    std::vector<uint64_t> pis((size_t)n * ql::NPI, 0);
+    for (uint32_t i = 0; i < n; i++)
+      if (verdicts[i] == QP_VERIFY_OK) memcpy(&pis[(size_t)i * ql::NPI], qv::public_inputs(v, proofs[i]), ql::NPI * 8);
+    return cast_screened(l, "qp_ledger_cast", pis.data(), verdicts.data(), n, reinterpret_cast<ql::Result *>(out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_cast");
+  }
+}
+
+int qp_ledger_reserve(qp_ledger *l, uint64_t new_capacity) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_reserve");
+  if (new_capacity > ql::MAX_CAPACITY || new_capacity < l->admitted() || !new_capacity) {
+    l->err = "qp_ledger_reserve: capacity " + std::to_string(new_capacity) + " for " + std::to_string(l->admitted()) +
+             " admitted transfers: it must hold them (and at least one) and be at most 2^31";
+    return QP_ERR_ARG;
+  }
+  if (new_capacity == l->cap()) return QP_OK;
+  if (l->ctx) return reserve_device(l, new_capacity);
+  try {
+    l->host.reserve(new_capacity);
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_reserve");
+  }
+  return QP_OK;
+}
+
+int qp_ledger_state(const qp_ledger *l, uint64_t *cast, uint64_t *admitted, uint64_t *credited, uint64_t *accounts,
+                    uint64_t *capacity) {
+  if (!l) return QP_ERR_ARG;
+  if (cast) *cast = l->cast;
+  if (admitted) *admitted = l->admitted();
+  if (credited) *credited = l->ncredited();
+  if (accounts) *accounts = l->naccounts();
+  if (capacity) *capacity = l->cap();
+  return QP_OK;
+}
+
+int qp_ledger_find(qp_ledger *l, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_find");
+  if (!k) return QP_OK;
+  if (!nullifiers || !seq_out) {
+    l->err = "qp_ledger_find: null buffer";
+    return QP_ERR_ARG;
+  }
+  if (int rc = canonical_keys(l, "qp_ledger_find", "nullifier", nullifiers, k)) return rc;
+  if (!l->ctx) {
+    for (uint32_t i = 0; i < k; i++) seq_out[i] = l->host.find(nullifiers + (size_t)i * 4);
+    return QP_OK;
+  }
+  try {
+    return device_step(l, find_device(l, nullifiers, k, seq_out));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_find");
+  }
+}
+
+int qp_ledger_entries(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
+                      uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_entries");
+  if (first > l->admitted() || k > l->admitted() - first) {
+    l->err = "qp_ledger_entries: entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
+             std::to_string(k) + ") are outside the log's " + std::to_string(l->admitted());
+    return QP_ERR_ARG;
+  }
+  if (!k) return QP_OK;
+  if (!l->ctx) {
+    const ql::HostLedger &h = l->host;
+    if (nullifiers) memcpy(nullifiers, &h.nullifier[first * 4], k * 32);
+    if (numbers) memcpy(numbers, &h.number[first], k * 8);
+    if (amounts) memcpy(amounts, &h.amount[first * 4], k * 16);
+    if (accounts) memcpy(accounts, &h.account[first * 4], k * 32);
+    if (flags) memcpy(flags, &h.flags[first], k);
+    return QP_OK;
+  }
+  hipStream_t s = l->ctx->stream;
+  const qpk::LedgerDev d = l->t.dev();
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (nullifiers) QP_HIP_TRY(l, hipMemcpyAsync(nullifiers, d.nullifier + first * 4, k * 32, hipMemcpyDeviceToHost, s));
+  if (numbers) QP_HIP_TRY(l, hipMemcpyAsync(numbers, d.number + first, k * 8, hipMemcpyDeviceToHost, s));
+  if (amounts) QP_HIP_TRY(l, hipMemcpyAsync(amounts, d.amount + first * 4, k * 16, hipMemcpyDeviceToHost, s));
+  if (accounts) QP_HIP_TRY(l, hipMemcpyAsync(accounts, d.account + first * 4, k * 32, hipMemcpyDeviceToHost, s));
+  if (flags) QP_HIP_TRY(l, hipMemcpyAsync(flags, d.flags + first, k, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_ledger_payouts(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accounts, uint64_t *sums,
+                      uint64_t *first_seq) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_payouts");
+  if (first > l->naccounts() || k > l->naccounts() - first) {
+    l->err = "qp_ledger_payouts: accounts [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
+             std::to_string(k) + ") are outside the " + std::to_string(l->naccounts()) + " credited so far";
+    return QP_ERR_ARG;
+  }
+  if (!k) return QP_OK;
+  if (l->ctx) return device_step(l, payouts_device(l, first, k, accounts, sums, first_seq));
+  const ql::HostLedger &h = l->host;
+  for (uint64_t i = 0; i < k; i++) {
+    const uint32_t seq = h.payee[first + i];
+    if (accounts) memcpy(accounts + i * 4, &h.account[(size_t)seq * 4], 32);
+    if (sums) memcpy(sums + i * 4, &h.sum[(size_t)h.astay[seq] * 4], 32);
+    if (first_seq) first_seq[i] = seq;
+  }
+  return QP_OK;
+}
+
+int qp_ledger_totals_for(qp_ledger *l, const uint64_t *accounts, uint32_t k, uint64_t *sums, uint8_t *found) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_totals_for");
+  if (!k) return QP_OK;
+  if (!accounts) {
+    l->err = "qp_ledger_totals_for: null buffer";
+    return QP_ERR_ARG;
+  }
+  if (int rc = canonical_keys(l, "qp_ledger_totals_for", "account", accounts, k)) return rc;
+  if (!l->ctx) {
+    for (uint32_t i = 0; i < k; i++) {
+      uint64_t s[4];
+      const bool f = l->host.total_for(accounts + (size_t)i * 4, s);
+      if (sums) memcpy(sums + (size_t)i * 4, s, 32);
+      if (found) found[i] = f;
+    }
+    return QP_OK;
+  }
+  try {
+    return device_step(l, totals_device(l, accounts, k, sums, found));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_totals_for");
+  }
+}
+
+int qp_ledger_recount(qp_ledger *l, uint64_t out[6]) {
+  if (!l || !out) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_recount");
+  if (!l->ctx) {
+    l->host.recount(out);
+    return QP_OK;
+  }
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  QP_HIP_TRY(l, hipMemsetAsync(l->d_audit.p, 0, 48, s));
+  qpk::ledger_recount(l->t.dev(), (uint32_t)l->count, l->d_audit.as<unsigned long long>(), s);
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipMemcpyAsync(out, l->d_audit.p, 48, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  return QP_OK;
+}
+
+int qp_ledger_cast_times(const qp_ledger *l, double ms[2]) {
+  if (!l || !ms) return QP_ERR_ARG;
+  ms[0] = l->ms[0];
+  ms[1] = l->ms[1];
+  return QP_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@ from .verifier import WormholeVerifier, merkle_verify  # noqa: F401,E402
 from .registry import VoterRegistry  # noqa: F401,E402
 from .ballot import (AUDIT_STATUS_TEXT, BALLOT_STATUS_TEXT, AuditReport, BallotBox, BallotReceipt,  # noqa: F401,E402
                      BallotResult, audit_log)
+from .ledger import TRANSFER_STATUS_TEXT, TransferResult, WormholeLedger  # noqa: F401,E402
 
 __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorageProof", "PublicCircuitInputs",
            "Witness", "VoteCircuitData", "VotePrivateInputs", "VotePublicInputs", "Prover", "ProofWithPublicInputs", "WormholeProver", "Context", "PolynomialBatch", "QpError", "ifft", "lde", "poseidon_permute", "lib", "header_symbols",
@@ -26,4 +27,5 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "WormholeProofAggregator", "aggregate_chunk", "aggregate_level", "aggregate_to_tree", "GateDesc", "gate_desc", "quotient", "FriLayer", "fri_fold", "pow_grind",
            "PermutationData", "opening_set", "fri_initial_poly",
            "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BallotReceipt",
-           "BALLOT_STATUS_TEXT", "AuditReport", "AUDIT_STATUS_TEXT", "audit_log"]
+           "BALLOT_STATUS_TEXT", "AuditReport", "AUDIT_STATUS_TEXT", "audit_log",
+           "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT"]

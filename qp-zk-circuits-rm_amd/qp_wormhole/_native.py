@@ -184,6 +184,21 @@ def lib():
         "qp_ballot_box_roots_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP]),
         "qp_ballot_box_restore": (ctypes.c_int, [VP, U64P, U64P, ctypes.c_uint32, ctypes.c_uint64, VP, VP, VP,
                                                  ctypes.c_uint64, ctypes.c_uint64, VP, PP]),
+        "qp_ledger_new": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, ctypes.c_uint64, PP]),
+        "qp_ledger_free": (None, [VP]),
+        "qp_ledger_last_error": (ctypes.c_char_p, [VP]),
+        "qp_ledger_accept_root": (ctypes.c_int, [VP, VP]),
+        "qp_ledger_reserve": (ctypes.c_int, [VP, ctypes.c_uint64]),
+        "qp_ledger_state": (ctypes.c_int, [VP] + [ctypes.POINTER(ctypes.c_uint64)] * 5),
+        "qp_ledger_cast": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t),
+                                          ctypes.c_uint32, VP]),
+        "qp_ledger_cast_public": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint32, VP]),
+        "qp_ledger_find": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP]),
+        "qp_ledger_entries": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP, VP, VP]),
+        "qp_ledger_payouts": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP]),
+        "qp_ledger_totals_for": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP]),
+        "qp_ledger_recount": (ctypes.c_int, [VP, VP]),
+        "qp_ledger_cast_times": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double)]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),
