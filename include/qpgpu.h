@@ -767,6 +767,104 @@ int qp_ledger_recount(qp_ledger *l, uint64_t out[6]);
  * (tools/ledger_bench.py); 0 on the host path.                                              */
 int qp_ledger_cast_times(const qp_ledger *l, double ms[2]);
 
+/* ---- the ledger's log commitment: what the settler publishes, and an exit
+ * account's receipt.  The log is append-only and final, like the ballot box's,
+ * and its commitment is (root, n), n = the admitted count:
+ *   log leaf of entry seq = hash_no_pad([nullifier[0..4], number, amount[0..4],
+ *     account[0..4], flags]): 14 felts.  amount is the four 32-bit limbs as the
+ *     log holds them, most significant first, each as one felt; flags is the
+ *     log's byte (bit 0 credited).  In plonky2's overwrite sponge that is two
+ *     permutations: state = 0; felts 0..7 into state[0..8], permute; felts
+ *     8..13 into state[0..6], state[6..12] as the first permutation left them,
+ *     permute; the digest is state[0..4];
+ *   the accumulator tree over leaves [0, n): node = hash_no_pad(left || right),
+ *     the last node of an odd level moves up unchanged; laid out for the
+ *     ledger's capacity.
+ * The settler publishes (root, n, payouts).  A receipt is the entry
+ * (nullifier, number, amount limbs, account, flags) plus at most 31 siblings
+ * compacted as qp_registry_paths compacts them, the side bits and the depth,
+ * and holds only under the (root, n) it was made under.  The checker takes the
+ * tree's shape from (seq, n) alone, as qp_ballot_receipt_check does.  The tree
+ * (64 bytes per entry of capacity on the device) is allocated by the first
+ * commit and brought up to date on demand only: qp_ledger_cast and
+ * qp_ledger_cast_public do no tree work.  qp_ledger_reserve drops it, and the
+ * next commit rebuilds it to the same root.                                    */
+/* hashes the leaves the tree does not hold yet and the nodes above them; root_out, *n_out (either
+ * may be NULL) = the commitment.  Nothing admitted: QP_ERR_STATE "empty log"; nothing new since the
+ * last commit: the same pair, nothing launched                                              */
+int qp_ledger_commit_log(qp_ledger *l, uint64_t root_out[4], uint64_t *n_out);
+/* the log entries seqs[0..k) (each < admitted, else QP_ERR_ARG naming the position; any order), as
+ * qp_ledger_entries gives them: nullifiers [k][4], numbers [k], amounts [k][4], accounts [k][4],
+ * flags [k]; each may be NULL.  What a receipt carries beside its path                          */
+int qp_ledger_entries_at(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
+                         uint32_t *amounts, uint64_t *accounts, uint8_t *flags);
+/* commits, then the paths of entries seqs[0..k) (each < admitted, else QP_ERR_ARG naming the position,
+ * before anything is enqueued): siblings [k][32][4] (the zero digest from the depth up), path_bits[i]
+ * bit j = side of sibling j (1: the entry's node is the right child), depth[i], leaves [k][4] (may be
+ * NULL) = the entries' log leaves; root_out, *n_out (either may be NULL) = the commitment they hold under */
+int qp_ledger_receipts(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
+                       uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out);
+/* commits, then roots_out[i][4] = the root the log had at ms[i] entries.  Each ms[i] in 1..admitted,
+ * else QP_ERR_ARG naming the position, before anything is enqueued.  Nothing admitted: QP_ERR_STATE
+ * "empty log".  k == 0: QP_OK, nothing launched beyond the commit.                               */
+int qp_ledger_roots_at(qp_ledger *l, const uint64_t *ms, uint32_t k, uint64_t *roots_out /* [k][4] */);
+/* checks a receipt against a published (root, n); needs no ledger and no device.  siblings [32][4].
+ * Returns a qp_receipt_status: the first reason found, in the order non-canonical (a felt >= p in root,
+ * nullifier, number, account or siblings, or flags > 1; an amount limb is in range by its type), shape, root */
+int qp_ledger_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],
+                            uint64_t number, const uint32_t amount[4], const uint64_t account[4], uint8_t flags,
+                            const uint64_t *siblings, uint32_t path_bits, uint32_t depth);
+
+/* ---- the audit of a published transfer log ----------------------------------
+ * A published log is what qp_ledger_entries returns, 1 <= n <= 2^31 entries.
+ * Beside it come optional claims: a root, totals (credited, then the four limb
+ * sums over the credited entries: what qp_ledger_recount gives as out[0] and
+ * out[2..6]), the payouts as qp_ledger_payouts gives them, and earlier
+ * commitments (root_i, n_i).  The audit reports the first reason that fires,
+ * in this order, with the lowest offender as its witness, so the report is a
+ * function of the input alone:                                                 */
+typedef enum {
+    QP_LEDGER_AUDIT_OK = 0,
+    QP_LEDGER_AUDIT_NON_CANONICAL = 1, /* a nullifier or account felt >= p, a number >= p or flags > 1; witness = the
+                                          lowest such seq.  Nothing is hashed: the report's root and counts are zero */
+    QP_LEDGER_AUDIT_ORDER = 2,         /* numbers[seq] <= numbers[seq - 1]; witness = the lowest such seq >= 1 */
+    QP_LEDGER_AUDIT_CREDIT_RULE = 3,   /* an entry's credited bit != "no earlier entry has this nullifier"; witness =
+                                          the lowest such seq, first = the lowest seq holding that nullifier */
+    QP_LEDGER_AUDIT_TOTALS = 4,        /* totals are claimed and differ from (credited, limb sums) of the entries
+                                          whose credited bit is set */
+    QP_LEDGER_AUDIT_PAYOUTS = 5,       /* payouts are claimed and differ from the log's (per account the limb sums of
+                                          its entries with the credited bit, accounts in the order of their first
+                                          such entry): witness = the lowest i < min(A, K) where account, sums or
+                                          first_seq differ; none and A != K: min(A, K).  A = the log's accounts */
+    QP_LEDGER_AUDIT_ROOT = 6,          /* a root is claimed and differs from the log tree's root over [0, n) */
+    QP_LEDGER_AUDIT_COMMITMENT = 7     /* some (root_i, n_i) has n_i > n, or the root of the prefix [0, n_i) != root_i;
+                                          witness = the lowest such index i */
+} qp_ledger_audit_status;
+/* On every status but NON_CANONICAL the report carries the recomputed root, credited, the four limb sums and
+ * the account count.  Claimed limb sums are compared with the log's as the totals they name (sum of sums[i] <<
+ * (96 - 32 i)), so a claim may split an exact total into its four words in any way.  With a context the audit
+ * runs on the device: one lane per entry inserts the whole log into a fresh nullifier table, whose slots end
+ * at the lowest seq of each nullifier whatever the scheduling; the entries with the credited bit build a fresh
+ * account table and its sums; the claimed payouts are compared one lane each, in a launch after the one that
+ * adds the sums.                                                                                 */
+typedef struct {
+    uint32_t status;         /* qp_ledger_audit_status */
+    uint32_t pad;
+    uint64_t witness, first; /* UINT64_MAX: none */
+    uint64_t root[4], credited, sums[4], accounts;
+} qp_ledger_audit_report;
+/* audits a published log against the claims given (claimed_root, claimed_totals [5], pay_accounts NULL, ncommit
+ * == 0: not claimed; pay_accounts [npay][4], pay_sums [npay][4], pay_first_seq [npay]).  QP_OK: the audit ran,
+ * the verdict is out->status.  QP_ERR_ARG: a null buffer, n outside 1..2^31, a claimed or commitment root or a
+ * claimed account with a felt >= p, some n_i == 0; the reason is qp_ledger_last_error(NULL)'s.  Needs no
+ * ledger; the log is not altered.                                                               */
+int qp_ledger_log_audit(qp_ctx *ctx /* NULL: host */, const uint64_t *nullifiers, const uint64_t *numbers,
+                        const uint32_t *amounts, const uint64_t *accounts, const uint8_t *flags, uint64_t n,
+                        const uint64_t *claimed_root, const uint64_t *claimed_totals, const uint64_t *pay_accounts,
+                        const uint64_t *pay_sums, const uint64_t *pay_first_seq, uint64_t npay,
+                        const uint64_t *commit_roots, const uint64_t *commit_ns, uint32_t ncommit,
+                        qp_ledger_audit_report *out);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

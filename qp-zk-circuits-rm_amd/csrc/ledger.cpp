@@ -5,6 +5,9 @@
 // raw public inputs are uploaded and screened, packed, inserted and credited on
 // the device (ledger.hip); without one the same semantics run on the host
 // (ql::HostLedger).  Both paths state the checks once, in ledger_table.h.
+// The log commitment (commit_log, receipts, entries_at, roots_at and the
+// receipt check: ledger_log.h) is brought up to date on demand; a cast does
+// not touch it, and the tree is allocated by the first commit only.
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <algorithm>
@@ -13,8 +16,11 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include "acc_tree.h"
 #include "ctx.h"
+#include "ledger_audit_device.h"
 #include "ledger_kernels.h"
+#include "ledger_log.h"
 #include "ledger_table.h"
 #include "verifier.h"
 
@@ -26,6 +32,10 @@ static_assert(QP_TRANSFER_CREDITED == ql::CREDITED && QP_TRANSFER_PROOF_REJECTED
                   QP_TRANSFER_BAD_AMOUNT == ql::BAD_AMOUNT && QP_TRANSFER_UNKNOWN_ROOT == ql::UNKNOWN_ROOT &&
                   QP_TRANSFER_DOUBLE_SPEND == ql::DOUBLE_SPEND,
               "qp_transfer_status and ledger_table.h differ");
+static_assert(QP_RECEIPT_OK == ql::RECEIPT_OK && QP_RECEIPT_SHAPE == ql::RECEIPT_SHAPE &&
+                  QP_RECEIPT_ROOT == ql::RECEIPT_ROOT && QP_RECEIPT_NON_CANONICAL == ql::RECEIPT_NON_CANONICAL &&
+                  QP_RECEIPT_NULL == ql::RECEIPT_NULL,
+              "qp_receipt_status and ledger_log.h differ");
 
 namespace {
 // the device half of a ledger for one capacity: the log, the two tables, the sums
@@ -65,6 +75,12 @@ struct qp_ledger {
   DevBuf d_q, d_qsum, d_qaux;                       // per lookup / gather batch (QUERY_BATCH entries)
   TimingEvents<3> ev;                               // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
+  // ---- the log commitment, both paths: built by the first commit, dropped by reserve
+  ql::HostLog hlog;
+  AccTree log;             // the device path's log tree, laid out for `capacity`; `committed` leaves
+  uint64_t committed = 0;  // leaves of the tree = the n of (log_root, n)
+  uint64_t log_root[4] = {0, 0, 0, 0};
+  DevBuf d_gacc, d_gnum, d_gamt, d_gflag;  // per entries_at batch, beside d_q (the seqs) and d_qsum (the nullifiers)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
   uint64_t ncredited() const { return ctx ? credited : host.credited; }
@@ -80,6 +96,14 @@ int refuse_new(qp_ctx *c, const std::string &why) {
   return QP_ERR_ARG;
 }
 
+}  // namespace
+
+void qla::set_ledgerless_error(qp_ctx *c, const std::string &why) {
+  g_new_err = why;
+  if (c) c->err = why;
+}
+
+namespace {
 int alloc_tables(qp_ledger *l, uint64_t capacity, LedgerTables &t) {
   const uint64_t S = ql::table_slots(capacity);
   hipStream_t s = l->ctx->stream;
@@ -121,7 +145,9 @@ int error_word(qp_ledger *l, const char *fn, uint32_t err) {
   l->err = std::string(fn) +
            (err & 1 ? ": the nullifier table's probe found no slot"
                     : err & 2 ? ": a nullifier slot holds a later entry than the one that stopped at it"
-                              : err & 4 ? ": the account table's probe found no slot" : ": a table slot holds no log entry") +
+                              : err & 4 ? ": the account table's probe found no slot"
+                                        : err & 8 ? ": a table slot holds no log entry"
+                                                  : ": a transfer number in the log is not a field element") +
            " (an internal invariant broke)";
   return QP_ERR_HIP;
 }
@@ -365,7 +391,97 @@ int reserve_device(qp_ledger *l, uint64_t new_capacity) {
   l->t = std::move(nt);
   l->capacity = new_capacity;
   l->payee_valid = false;  // the payees are the same entries, but the list is cheap and this keeps one rule
+  // the log tree's layout is the capacity's: dropped here, rebuilt by the next commit from the copied
+  // log, which gives the same root
+  l->log.drop();
+  l->committed = 0;
   return QP_OK;
+}
+
+// the log tree up to the admitted count (> 0; the caller checks): leaves [committed, count), the
+// levels above them, the root
+int commit_device(qp_ledger *l) {
+  hipStream_t s = l->ctx->stream;
+  if (l->committed == l->count) return QP_OK;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (!l->log.dig.p)
+    if (int rc = l->log.alloc({l->err}, l->capacity)) return rc;
+  qpk::AccLevels lv;
+  if (!qpk::acc_levels_reserved(l->count, l->capacity, lv)) {
+    l->err = "qp_ledger_commit_log: the log does not fit its capacity (an internal invariant broke)";
+    return QP_ERR_HIP;
+  }
+  qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
+  uint64_t root[4];
+  uint32_t err = 0;
+  qpk::ledger_leaves(l->t.dev(), (uint32_t)l->committed, (uint32_t)l->count, l->log.dig.p, ctr, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  l->log.append(lv, qpk::acc_row_max(), s);  // the tree holds `committed` leaves
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipMemcpyAsync(root, l->log.root(lv), 32, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  if (int rc = error_word(l, "qp_ledger_commit_log", err)) return rc;
+  memcpy(l->log_root, root, 32);
+  l->log.lv = lv;
+  l->committed = l->count;
+  return QP_OK;
+}
+
+// commit on either path; the caller checked that the log is not empty
+int commit_log(qp_ledger *l) {
+  if (l->ctx) return commit_device(l);
+  if (!l->hlog.commit(l->host)) return error_word(l, "qp_ledger_commit_log", qpk::LEDGER_ERR_NUMBER);
+  memcpy(l->log_root, l->hlog.root(), 32);
+  l->committed = l->hlog.n;
+  return QP_OK;
+}
+
+int entries_at_device(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
+                      uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
+  hipStream_t s = l->ctx->stream;
+  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+  if (int rc = query_buffers(l)) return rc;
+  if (!l->d_gnum.p) {
+    QP_HIP_TRY(l, l->d_gacc.alloc((size_t)QUERY_BATCH * 4));
+    QP_HIP_TRY(l, l->d_gamt.alloc((size_t)QUERY_BATCH * 2));
+    QP_HIP_TRY(l, l->d_gflag.alloc(QUERY_BATCH / 8));
+    QP_HIP_TRY(l, l->d_gnum.alloc(QUERY_BATCH));
+  }
+  for (uint32_t done = 0; done < k;) {
+    const uint32_t nb = std::min(QUERY_BATCH, k - done);
+    QP_HIP_TRY(l, hipMemcpyAsync(l->d_q.p, seqs + done, (size_t)nb * 8, hipMemcpyHostToDevice, s));
+    qpk::ledger_gather(l->t.dev(), l->d_q.p, nb, l->d_qsum.p, l->d_gnum.p, l->d_gamt.as<uint32_t>(), l->d_gacc.p,
+                       l->d_gflag.as<uint8_t>(), s);
+    QP_HIP_TRY(l, hipGetLastError());
+    if (nullifiers)
+      QP_HIP_TRY(l, hipMemcpyAsync(nullifiers + (size_t)done * 4, l->d_qsum.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    if (numbers) QP_HIP_TRY(l, hipMemcpyAsync(numbers + done, l->d_gnum.p, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+    if (amounts)
+      QP_HIP_TRY(l, hipMemcpyAsync(amounts + (size_t)done * 4, l->d_gamt.p, (size_t)nb * 16, hipMemcpyDeviceToHost, s));
+    if (accounts)
+      QP_HIP_TRY(l, hipMemcpyAsync(accounts + (size_t)done * 4, l->d_gacc.p, (size_t)nb * 32, hipMemcpyDeviceToHost, s));
+    if (flags) QP_HIP_TRY(l, hipMemcpyAsync(flags + done, l->d_gflag.p, nb, hipMemcpyDeviceToHost, s));
+    QP_HIP_TRY(l, hipStreamSynchronize(s));
+    done += nb;
+  }
+  return QP_OK;
+}
+
+// seqs[k] all inside the log, or QP_ERR_ARG naming the first that is not
+int check_seqs(qp_ledger *l, const char *fn, const uint64_t *seqs, uint32_t k) {
+  for (uint32_t i = 0; i < k; i++)
+    if (seqs[i] >= l->admitted()) {
+      l->err = std::string(fn) + ": entry " + std::to_string(seqs[i]) + " (position " + std::to_string(i) +
+               ") is outside the log's " + std::to_string(l->admitted());
+      return QP_ERR_ARG;
+    }
+  return QP_OK;
+}
+
+int empty_log(qp_ledger *l, const char *fn) {
+  l->err = std::string(fn) + ": empty log (no transfer has been admitted yet)";
+  return QP_ERR_STATE;
 }
 
 int canonical_keys(qp_ledger *l, const char *fn, const char *what, const uint64_t *keys, uint32_t k) {
@@ -532,6 +648,8 @@ int qp_ledger_reserve(qp_ledger *l, uint64_t new_capacity) {
   } catch (const std::bad_alloc &) {
     return bad_alloc(l, "qp_ledger_reserve");
   }
+  l->hlog.drop();  // the log tree's layout is the capacity's: the next commit rebuilds it
+  l->committed = 0;
   return QP_OK;
 }
 
@@ -658,6 +776,106 @@ int qp_ledger_recount(qp_ledger *l, uint64_t out[6]) {
   QP_HIP_TRY(l, hipMemcpyAsync(out, l->d_audit.p, 48, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(l, hipStreamSynchronize(s));
   return QP_OK;
+}
+
+int qp_ledger_commit_log(qp_ledger *l, uint64_t root_out[4], uint64_t *n_out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_commit_log");
+  if (!l->admitted()) return empty_log(l, "qp_ledger_commit_log");
+  try {
+    if (int rc = device_step(l, commit_log(l))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_commit_log");
+  }
+  if (root_out) memcpy(root_out, l->log_root, 32);
+  if (n_out) *n_out = l->committed;
+  return QP_OK;
+}
+
+int qp_ledger_entries_at(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
+                         uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_entries_at");
+  if (!k) return QP_OK;
+  if (!seqs) {
+    l->err = "qp_ledger_entries_at: null buffer";
+    return QP_ERR_ARG;
+  }
+  if (int rc = check_seqs(l, "qp_ledger_entries_at", seqs, k)) return rc;
+  if (l->ctx) return device_step(l, entries_at_device(l, seqs, k, nullifiers, numbers, amounts, accounts, flags));
+  const ql::HostLedger &h = l->host;
+  for (uint32_t i = 0; i < k; i++) {
+    const size_t at = (size_t)seqs[i];
+    if (nullifiers) memcpy(nullifiers + (size_t)i * 4, &h.nullifier[at * 4], 32);
+    if (numbers) numbers[i] = h.number[at];
+    if (amounts) memcpy(amounts + (size_t)i * 4, &h.amount[at * 4], 16);
+    if (accounts) memcpy(accounts + (size_t)i * 4, &h.account[at * 4], 32);
+    if (flags) flags[i] = h.flags[at];
+  }
+  return QP_OK;
+}
+
+int qp_ledger_receipts(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
+                       uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_receipts");
+  if (!l->admitted()) return empty_log(l, "qp_ledger_receipts");
+  if (k && (!seqs || !siblings || !path_bits || !depth)) {
+    l->err = "qp_ledger_receipts: null buffer";
+    return QP_ERR_ARG;
+  }
+  if (int rc = check_seqs(l, "qp_ledger_receipts", seqs, k)) return rc;
+  try {
+    if (int rc = device_step(l, commit_log(l))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_receipts");
+  }
+  if (root_out) memcpy(root_out, l->log_root, 32);
+  if (n_out) *n_out = l->committed;
+  if (!k) return QP_OK;
+  if (l->ctx) {
+    QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+    return device_step(l, l->log.paths({l->err}, l->ctx->stream, seqs, k, siblings, path_bits, depth, leaves));
+  }
+  for (uint32_t i = 0; i < k; i++)
+    l->hlog.path(seqs[i], siblings + (size_t)i * ql::PATH_SLOTS * 4, path_bits + i, depth + i,
+                 leaves ? leaves + (size_t)i * 4 : nullptr);
+  return QP_OK;
+}
+
+int qp_ledger_roots_at(qp_ledger *l, const uint64_t *ms, uint32_t k, uint64_t *roots_out) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_roots_at");
+  if (!l->admitted()) return empty_log(l, "qp_ledger_roots_at");
+  if (k && (!ms || !roots_out)) {
+    l->err = "qp_ledger_roots_at: null buffer";
+    return QP_ERR_ARG;
+  }
+  for (uint32_t i = 0; i < k; i++)
+    if (!ms[i] || ms[i] > l->admitted()) {
+      l->err = "qp_ledger_roots_at: size " + std::to_string(ms[i]) + " (position " + std::to_string(i) +
+               ") is outside 1.." + std::to_string(l->admitted()) + ", the sizes the log has had";
+      return QP_ERR_ARG;
+    }
+  try {
+    if (int rc = device_step(l, commit_log(l))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_roots_at");
+  }
+  if (!k) return QP_OK;
+  if (l->ctx) {
+    QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
+    return device_step(l, l->log.prefix_roots({l->err}, l->ctx->stream, ms, k, roots_out));
+  }
+  for (uint32_t i = 0; i < k; i++) l->hlog.prefix_root(ms[i], ql::log_node, roots_out + (size_t)i * 4);
+  return QP_OK;
+}
+
+int qp_ledger_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],
+                            uint64_t number, const uint32_t amount[4], const uint64_t account[4], uint8_t flags,
+                            const uint64_t *siblings, uint32_t path_bits, uint32_t depth) {
+  if (!root || !nullifier || !amount || !account || !siblings) return QP_RECEIPT_NULL;
+  return ql::receipt_check(root, n, seq, nullifier, number, amount, account, flags, siblings, path_bits, depth);
 }
 
 int qp_ledger_cast_times(const qp_ledger *l, double ms[2]) {

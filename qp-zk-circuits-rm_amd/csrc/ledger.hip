@@ -4,10 +4,14 @@
 // compaction and the read-only lookups.  Layouts and the home-slot rules:
 // ledger_kernels.h.  Memory-latency-bound throughout: a lane reads 128 bytes of
 // public inputs or does a few dependent slot atomics and 32-byte key reads.
-// Blocks of 256 lanes (LEDGER_BLOCK).
+// Blocks of 256 lanes (LEDGER_BLOCK).  The log commitment's leaf kernel is the
+// exception: VALU-bound, two permutations per lane (poseidon_dev.h).  The audit
+// of a published log reuses the insert, the probes, the recount and the payees'
+// compaction over a table of the audit's own.
 #include "ballot_device.h"
 #include "ledger_kernels.h"
 #include "ledger_table.h"
+#include "poseidon_dev.h"
 
 namespace qpk {
 
@@ -342,6 +346,172 @@ __global__ void __launch_bounds__(256) k_ledger_recount(LedgerDev d, uint32_t co
   const bool pred[2] = {credited, in};
   unsigned long long *const dst[2] = {out, out + 1};
   block_count(pred, dst);
+}
+
+// ---- the log commitment (ledger_kernels.h, ledger_log.h): leaves, gather
+
+// log leaf seq = hash_no_pad of the entry's 14 felts into level 0 of the digest buffer: one lane per
+// entry of [first, end).  The overwrite sponge takes two permutations: felts 0..7 (nullifier, number,
+// amount limbs 0..2) over a zero state, then felts 8..13 (amount limb 3, account, flags) over lanes
+// 0..5 with lanes 6..11 as the first permutation left them.  Both are poseidon_fast.h's forms: the
+// zero-capacity one with all twelve lanes out (what node_digest runs with four), then the general one
+// with lanes 0..3 out.  The state stays non-canonical in between (permute_nc takes any 64-bit lanes);
+// canon on the four lanes stored.  VALU-bound, registers only: no LDS, no scratch.  A number >= p
+// cannot be reached (numbers count transfers); it is not hashed and sets the error word.
+__global__ void __launch_bounds__(256) k_ledger_leaves(LedgerDev d, uint32_t first, uint32_t end,
+                                                       uint64_t *__restrict__ dig, uint32_t *__restrict__ err) {
+  const uint64_t seq = (uint64_t)first + blockIdx.x * blockDim.x + threadIdx.x;
+  if (seq >= end) return;
+  uint64_t s[12], acc[4];
+  load_key(d.nullifier + seq * 4, s);
+  s[4] = d.number[seq];
+  const uint4 a = reinterpret_cast<const uint4 *>(d.amount)[seq];
+  s[5] = a.x, s[6] = a.y, s[7] = a.z;
+  if (s[4] >= ql::P) {
+    atomicOr(err, LEDGER_ERR_NUMBER);
+    return;
+  }
+  s[8] = s[9] = s[10] = s[11] = 0;
+  pf::permute_nc_capz<0xFFFu>(s);
+  load_key(d.account + seq * 4, acc);
+  s[0] = a.w;
+#pragma unroll
+  for (int j = 0; j < 4; j++) s[1 + j] = acc[j];
+  s[5] = d.flags[seq];
+#pragma unroll
+  for (int j = 0; j < 12; j++) s[j] = pf::add_c(s[j], ps::rc_cx(j));
+  pf::rounds<0, 0xFu>(s);
+  ulonglong2 *o = reinterpret_cast<ulonglong2 *>(dig + seq * 4);
+  o[0] = make_ulonglong2(psd::canon(s[0]), psd::canon(s[1]));
+  o[1] = make_ulonglong2(psd::canon(s[2]), psd::canon(s[3]));
+}
+
+// log entries seq[i] < count (the caller checks) into dense arrays: one lane per entry
+__global__ void __launch_bounds__(256) k_ledger_gather(LedgerDev d, const uint64_t *__restrict__ seq, uint32_t k,
+                                                       uint64_t *__restrict__ nullifier, uint64_t *__restrict__ number,
+                                                       uint32_t *__restrict__ amount, uint64_t *__restrict__ account,
+                                                       uint8_t *__restrict__ flags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= k) return;
+  const uint64_t at = seq[i];
+  const ulonglong2 *nul = reinterpret_cast<const ulonglong2 *>(d.nullifier + at * 4);
+  const ulonglong2 *acc = reinterpret_cast<const ulonglong2 *>(d.account + at * 4);
+  ulonglong2 *onul = reinterpret_cast<ulonglong2 *>(nullifier + (uint64_t)i * 4);
+  ulonglong2 *oacc = reinterpret_cast<ulonglong2 *>(account + (uint64_t)i * 4);
+  onul[0] = nul[0], onul[1] = nul[1];
+  oacc[0] = acc[0], oacc[1] = acc[1];
+  reinterpret_cast<uint4 *>(amount)[i] = reinterpret_cast<const uint4 *>(d.amount)[at];
+  number[i] = d.number[at];
+  flags[i] = d.flags[at];
+}
+
+// ---- the audit of a published log (ledger_audit.h has the rules).  Seqs are consecutive across a
+// wave, so the lowest offending lane of a wave's ballot holds the wave's lowest seq and alone sends
+// it: one atomicMin per wave and reason at the most, and the minimum does not depend on the order the
+// waves arrive in.
+
+namespace {
+// true in the lowest lane of the wave whose `bad` is set; every lane of the wave calls it
+__device__ __forceinline__ bool lowest_offender(bool bad) {
+  const uint64_t m = __ballot(bad);
+  return bad && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)m) - 1);
+}
+}  // namespace
+
+// one lane per entry.  number[seq - 1] is a plain load of uploaded data, across a block edge as inside one.
+__global__ void __launch_bounds__(256) k_ledger_audit_screen(LedgerDev d, uint32_t n, LedgerAuditDev *rep) {
+  const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false, unordered = false;
+  if (seq < n) {
+    uint64_t nul[4], acc[4];
+    load_key(d.nullifier + (uint64_t)seq * 4, nul);
+    load_key(d.account + (uint64_t)seq * 4, acc);
+    const uint64_t num = d.number[seq];
+    bad = num >= ql::P || d.flags[seq] > LEDGER_CREDITED;
+#pragma unroll
+    for (int j = 0; j < 4; j++) bad = bad || nul[j] >= ql::P || acc[j] >= ql::P;
+    unordered = seq && num <= d.number[seq - 1];
+  }
+  if (lowest_offender(bad)) atomicMin(&rep->non_canonical, seq);
+  if (lowest_offender(unordered)) atomicMin(&rep->order, seq);
+}
+
+// a launch after the whole-log insert: every nullifier slot word is final (facts 1-3 of table_probe:
+// the slot of a nullifier ends at the lowest seq that carries it, whatever the scheduling), so owner ==
+// seq says "no earlier entry has this nullifier".  One lane per entry; the lanes past n only take part
+// in the wave's ballots and the block's counts.  The flags are read and never written; an entry whose
+// flag says credited goes into the account table and onto its sums, as in k_ledger_resolve.
+__global__ void __launch_bounds__(256) k_ledger_audit_resolve(LedgerDev d, uint32_t n,
+                                                              const uint32_t *__restrict__ stay,
+                                                              LedgerAuditDev *rep) {
+  const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
+  bool credited = false, claimed = false, broken = false;
+  uint32_t owner = LEDGER_EMPTY;
+  if (seq < n) {
+    const uint32_t at = stay[seq];
+    if (at != LEDGER_NO_SLOT) owner = d.nslot[at];
+    credited = d.flags[seq] & LEDGER_CREDITED;
+    if (owner > seq)  // a slot holds the minimum of its nullifier's seqs: defensive, as the probe's bound
+      atomicOr(&rep->ctr.err, 2u);
+    else
+      broken = credited != (owner == seq);
+    d.astay[seq] = LEDGER_NO_SLOT;
+    if (credited && !credit_entry(d, seq, n, &claimed)) atomicOr(&rep->ctr.err, 4u);
+  }
+  if (lowest_offender(broken)) atomicMin(&rep->credit_rule, (unsigned long long)seq << 32 | owner);
+  const bool pred[2] = {credited, claimed};
+  unsigned long long *const dst[2] = {&rep->ctr.credited, &rep->ctr.accounts};
+  block_count(pred, dst);
+}
+
+// one lane per claimed payout i < k <= the payees: the account, the four limb sums and first_seq
+// against payee i.  The sums were added by k_ledger_audit_resolve, launches ago.
+__global__ void __launch_bounds__(256) k_ledger_audit_payouts(LedgerDev d, const uint32_t *__restrict__ payee,
+                                                              uint32_t k, const uint64_t *__restrict__ accounts,
+                                                              const uint64_t *__restrict__ sums,
+                                                              const uint64_t *__restrict__ first_seq,
+                                                              LedgerAuditDev *rep) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool differs = false;
+  if (i < k) {
+    const uint32_t seq = payee[i];
+    const uint64_t at = d.astay[seq];
+    uint64_t want[4], got[4], ws[4], ls[4];
+    load_key(d.account + (uint64_t)seq * 4, want);
+    load_key(accounts + (uint64_t)i * 4, got);
+    load_key(sums + (uint64_t)i * 4, ws);
+    load_key(reinterpret_cast<const uint64_t *>(d.sum) + at * 4, ls);
+    differs = !ql::key_equal(want, got) || first_seq[i] != seq || !ql::sums_equal(ws, ls);
+  }
+  if (lowest_offender(differs)) atomicMin(&rep->payout, i);
+}
+
+void ledger_leaves(const LedgerDev &d, uint32_t first, uint32_t end, uint64_t *dig, LedgerCounters *ctr,
+                   hipStream_t s) {
+  if (first >= end) return;
+  k_ledger_leaves<<<ledger_blocks(end - first), LEDGER_BLOCK, 0, s>>>(d, first, end, dig, &ctr->err);
+}
+
+void ledger_gather(const LedgerDev &d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
+                   uint32_t *amount, uint64_t *account, uint8_t *flags, hipStream_t s) {
+  if (!k) return;
+  k_ledger_gather<<<ledger_blocks(k), LEDGER_BLOCK, 0, s>>>(d, seq, k, nullifier, number, amount, account, flags);
+}
+
+void ledger_audit_screen(const LedgerDev &d, uint32_t n, LedgerAuditDev *rep, hipStream_t s) {
+  if (!n) return;
+  k_ledger_audit_screen<<<ledger_blocks(n), LEDGER_BLOCK, 0, s>>>(d, n, rep);
+}
+
+void ledger_audit_resolve(const LedgerDev &d, uint32_t n, const uint32_t *stay, LedgerAuditDev *rep, hipStream_t s) {
+  if (!n) return;
+  k_ledger_audit_resolve<<<ledger_blocks(n), LEDGER_BLOCK, 0, s>>>(d, n, stay, rep);
+}
+
+void ledger_audit_payouts(const LedgerDev &d, const uint32_t *payee, uint32_t k, const uint64_t *accounts,
+                          const uint64_t *sums, const uint64_t *first_seq, LedgerAuditDev *rep, hipStream_t s) {
+  if (!k) return;
+  k_ledger_audit_payouts<<<ledger_blocks(k), LEDGER_BLOCK, 0, s>>>(d, payee, k, accounts, sums, first_seq, rep);
 }
 
 void ledger_screen(const LedgerScreen &sc, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,

@@ -89,4 +89,37 @@ void ledger_payouts(const LedgerDev &d, const uint32_t *payee, uint32_t k, uint6
 // out[6] (zeroed by the caller) += credited, admitted, the four limb sums over the credited of log [0, count)
 void ledger_recount(const LedgerDev &d, uint32_t count, unsigned long long *out, hipStream_t s);
 
+// ---- the log commitment (ledger_log.h has the definitions): the leaves and the gather.  The levels
+// above level 0, the paths and the prefix roots are the accumulator tree's (acc_kernels.h).
+// bit of the error word: a number >= p in the log (cannot be reached; the leaf is not hashed)
+constexpr uint32_t LEDGER_ERR_NUMBER = 16;
+// log leaves [first, end) into level 0 of the digest buffer dig[seq][4]: leaf seq =
+// hash_no_pad([nullifier[0..4], number, amount[0..4], account[0..4], flags]), 14 felts, two permutations
+void ledger_leaves(const LedgerDev &d, uint32_t first, uint32_t end, uint64_t *dig, LedgerCounters *ctr,
+                   hipStream_t s);
+// log entries seq[i] < count (device; the caller checks the bound) into dense arrays [k][4], [k], [k][4],
+// [k][4], [k]
+void ledger_gather(const LedgerDev &d, const uint64_t *seq, uint32_t k, uint64_t *nullifier, uint64_t *number,
+                   uint32_t *amount, uint64_t *account, uint8_t *flags, hipStream_t s);
+
+// ---- the audit of a published log (ledger_audit.h has the rules).  The log is uploaded into a
+// LedgerDev of its own with fresh tables; the whole-log insert is ledger_insert(d, 0, n, ...), the
+// limb totals ledger_recount, the payees ledger_payee_count / ledger_scan / ledger_payee_write.
+constexpr uint32_t LEDGER_AUDIT_NO_SEQ = 0xFFFFFFFFu;
+struct LedgerAuditDev {
+  unsigned long long credit_rule;  // the lowest offender << 32 | the lowest seq of its nullifier; ~0: none
+  uint32_t non_canonical, order;   // the lowest offender; LEDGER_AUDIT_NO_SEQ: none
+  uint32_t payout, pad;            // the lowest claimed payout that differs; LEDGER_AUDIT_NO_SEQ: none
+  LedgerCounters ctr;              // entries with the credited bit, accounts they claim, the error word
+};
+// canonical felts, flags <= 1, numbers strictly increasing: the lowest offenders into rep
+void ledger_audit_screen(const LedgerDev &d, uint32_t n, LedgerAuditDev *rep, hipStream_t s);
+// after the whole-log insert, a launch of its own: the credit rule's lowest offender; every entry with the
+// credited bit goes into the account table and adds its limbs to the account's sums
+void ledger_audit_resolve(const LedgerDev &d, uint32_t n, const uint32_t *stay, LedgerAuditDev *rep, hipStream_t s);
+// after ledger_payee_write, so a launch later than the one that adds the sums: claimed payout i < k
+// (accounts [k][4], sums [k][4], first_seq [k], device) against payee[i]
+void ledger_audit_payouts(const LedgerDev &d, const uint32_t *payee, uint32_t k, const uint64_t *accounts,
+                          const uint64_t *sums, const uint64_t *first_seq, LedgerAuditDev *rep, hipStream_t s);
+
 }  // namespace qpk

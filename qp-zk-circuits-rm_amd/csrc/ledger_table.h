@@ -71,6 +71,21 @@ QL_HD inline int key_compare(const uint64_t *a, const uint64_t *b) {
     if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
   return 0;
 }
+// Four limb sums name the total sum of s[i] << (96 - 32 i).  Two sets name one total iff their
+// carry-propagated forms are equal: limbs 3..1 reduced to 32 bits, the carries moved up, and the top
+// word with its carry-out.  The audit compares claimed sums with the log's this way, so a claim may
+// give an exact total in any split.
+QL_HD inline bool sums_equal(const uint64_t *a, const uint64_t *b) {
+  uint64_t ca = 0, cb = 0;
+  for (int i = 3; i >= 1; i--) {
+    const uint64_t ta = a[i] + ca, tb = b[i] + cb;  // a carry is below 2^34: t < carry iff the sum wrapped
+    if ((ta & 0xFFFFFFFFull) != (tb & 0xFFFFFFFFull)) return false;
+    ca = (ta >> 32) | ((uint64_t)(ta < ca) << 32);
+    cb = (tb >> 32) | ((uint64_t)(tb < cb) << 32);
+  }
+  const uint64_t ta = a[0] + ca, tb = b[0] + cb;
+  return ta == tb && (ta < ca) == (tb < cb);
+}
 // roots [n][4] sorted by key_compare, each held once: the position of r, or of the first root above it
 QL_HD inline uint32_t root_lower_bound(const uint64_t *roots, uint32_t n, const uint64_t *r) {
   uint32_t lo = 0, hi = n;

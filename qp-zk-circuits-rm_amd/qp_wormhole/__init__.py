@@ -19,7 +19,8 @@ from .verifier import WormholeVerifier, merkle_verify  # noqa: F401,E402
 from .registry import VoterRegistry  # noqa: F401,E402
 from .ballot import (AUDIT_STATUS_TEXT, BALLOT_STATUS_TEXT, AuditReport, BallotBox, BallotReceipt,  # noqa: F401,E402
                      BallotResult, audit_log)
-from .ledger import TRANSFER_STATUS_TEXT, TransferResult, WormholeLedger  # noqa: F401,E402
+from .ledger import (LEDGER_AUDIT_STATUS_TEXT, TRANSFER_STATUS_TEXT, LedgerAuditReport, TransferReceipt,  # noqa: F401,E402
+                     TransferResult, WormholeLedger, audit_ledger_log)
 
 __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorageProof", "PublicCircuitInputs",
            "Witness", "VoteCircuitData", "VotePrivateInputs", "VotePublicInputs", "Prover", "ProofWithPublicInputs", "WormholeProver", "Context", "PolynomialBatch", "QpError", "ifft", "lde", "poseidon_permute", "lib", "header_symbols",
@@ -28,4 +29,5 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "PermutationData", "opening_set", "fri_initial_poly",
            "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BallotReceipt",
            "BALLOT_STATUS_TEXT", "AuditReport", "AUDIT_STATUS_TEXT", "audit_log",
-           "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT"]
+           "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT", "TransferReceipt", "LedgerAuditReport",
+           "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log"]

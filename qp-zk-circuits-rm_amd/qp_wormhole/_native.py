@@ -199,6 +199,15 @@ def lib():
         "qp_ledger_totals_for": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP]),
         "qp_ledger_recount": (ctypes.c_int, [VP, VP]),
         "qp_ledger_cast_times": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double)]),
+        "qp_ledger_commit_log": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_entries_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP, VP, VP, VP]),
+        "qp_ledger_receipts": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP, VP, VP, VP,
+                                              ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_roots_at": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP]),
+        "qp_ledger_receipt_check": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, ctypes.c_uint64, VP, VP,
+                                                   ctypes.c_uint8, VP, ctypes.c_uint32, ctypes.c_uint32]),
+        "qp_ledger_log_audit": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_uint64, VP, VP, VP, VP, VP,
+                                               ctypes.c_uint64, VP, VP, ctypes.c_uint32, VP]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

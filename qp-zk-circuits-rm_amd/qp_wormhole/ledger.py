@@ -22,6 +22,12 @@ know them pays the dummy.
 With a Context (or a device number) the log, the nullifier and account tables
 and the sums live on the device, and the screen runs there too
 (csrc/ledger.hip); with None the same semantics run on the host.
+
+The settler publishes (root, n, payouts): `commit_log` commits the log to a
+Merkle root (the ballot box's kind of tree over a 14-felt leaf), `receipts`
+ties single entries to it, `check_receipt` checks one without a ledger, and
+`audit_ledger_log` checks a published log against the root, the totals, the
+payouts and earlier commitments published beside it.
 """
 import ctypes
 from collections import namedtuple
@@ -49,6 +55,37 @@ TransferResult = namedtuple("TransferResult", "status verify_status number first
 # qp_transfer_result
 RESULT_DTYPE = np.dtype([("status", np.uint32), ("verify_status", np.uint32), ("number", np.uint64),
                          ("first", np.uint64)])
+
+
+# one log entry tied to a published commitment (root, n): amount is the four 32-bit limbs, most
+# significant first (`total` puts them together); siblings are the `depth` digests of the levels where
+# the entry's node was hashed, from the leaf up; path_bits bit j = side of sibling j
+class TransferReceipt(namedtuple("TransferReceipt",
+                                 "nullifier number amount account credited seq siblings path_bits depth root n")):
+    __slots__ = ()
+
+    @property
+    def total(self):
+        """the entry's amount as one exact int"""
+        return _total(self.amount)
+
+
+# qp_ledger_audit_status: the first reason that fires, in this order
+(LEDGER_AUDIT_OK, LEDGER_AUDIT_NON_CANONICAL, LEDGER_AUDIT_ORDER, LEDGER_AUDIT_CREDIT_RULE, LEDGER_AUDIT_TOTALS,
+ LEDGER_AUDIT_PAYOUTS, LEDGER_AUDIT_ROOT, LEDGER_AUDIT_COMMITMENT) = range(8)
+LEDGER_AUDIT_STATUS_TEXT = ("ok", "non-canonical entry", "transfer numbers out of order", "credit rule broken",
+                            "claimed totals differ", "claimed payouts differ", "claimed root differs",
+                            "earlier commitment does not hold")
+# the verdict on a published log: witness = the lowest offender (an entry's seq; for the payouts and
+# the commitments an index into the claim), first = the lowest seq holding the witness's nullifier
+# (credit rule only), None where there is none; root, credited, the exact total and the account count
+# recomputed from the log (zero on a non-canonical one)
+LedgerAuditReport = namedtuple("LedgerAuditReport", "status witness first root credited total accounts")
+# qp_ledger_audit_report
+LEDGER_AUDIT_DTYPE = np.dtype([("status", np.uint32), ("pad", np.uint32), ("witness", np.uint64), ("first", np.uint64),
+                               ("root", np.uint64, 4), ("credited", np.uint64), ("sums", np.uint64, 4),
+                               ("accounts", np.uint64)])
+PATH_SLOTS = 32  # sibling slots of a receipt's path: the log tree is the registry's kind of tree
 
 
 def _felts(v, n, what):
@@ -81,6 +118,108 @@ def _keys(rows, what):
         if len(r) != 4 or any(not 0 <= x < 2**64 for x in r):
             raise ValueError(f"{what} at position {i} must be 4 field elements")
     return np.array(rows, dtype=np.uint64).reshape(len(rows), 4)
+
+
+def _limbs(amounts, n):
+    """amounts as [n][4] uint32 limbs: that array itself, or exact ints split most significant limb first"""
+    if isinstance(amounts, np.ndarray) and amounts.ndim == 2:
+        if amounts.shape != (n, 4):
+            raise ValueError(f"amount limbs of shape {amounts.shape} for {n} entries")
+        return np.ascontiguousarray(amounts, dtype=np.uint32)
+    ints = [int(a) for a in amounts]
+    if len(ints) != n or any(not 0 <= a < 1 << 128 for a in ints):
+        raise ValueError(f"amounts must be {n} ints below 2^128, or [{n}][4] limbs")
+    return np.array([[(a >> (96 - 32 * i)) & 0xFFFFFFFF for i in range(4)] for a in ints], dtype=np.uint32).reshape(n, 4)
+
+
+def _sum_words(v):
+    """four words that name a total (sum of words[i] << (96 - 32 i)): limb sums as they are, or an
+    exact int split with the top word taking what is above 2^96"""
+    if isinstance(v, (int, np.integer)):
+        t = int(v)
+        if not 0 <= t < 1 << 160:
+            raise ValueError("a total is an int in [0, 2^160)")
+        return [t >> 96, (t >> 64) & 0xFFFFFFFF, (t >> 32) & 0xFFFFFFFF, t & 0xFFFFFFFF]
+    w = [int(x) for x in v]
+    if len(w) != 4 or any(not 0 <= x < 2**64 for x in w):
+        raise ValueError("limb sums are four values that fit 64 bits")
+    return w
+
+
+def _ledger_log_arrays(entries):
+    """(nullifiers [n][4], numbers [n], amounts [n][4] u32, accounts [n][4], flags [n] u8) of a published
+    log: the 5-tuple `WormholeLedger.entries()` returns (exact-int amounts, credited bools), or the same
+    with [n][4] limbs and/or a uint8 flags array"""
+    entries = tuple(entries)
+    if len(entries) != 5:
+        raise ValueError("a log is (nullifiers, numbers, amounts, accounts, credited or flags)")
+    nul, num, amt, acc, fl = entries
+    nul = np.ascontiguousarray(nul, dtype=np.uint64).reshape(-1, 4)
+    num = np.ascontiguousarray(num, dtype=np.uint64).reshape(-1)
+    acc = np.ascontiguousarray(acc, dtype=np.uint64).reshape(-1, 4)
+    fl = np.asarray(fl)
+    fl = fl.astype(np.uint8) * FLAG_CREDITED if fl.dtype == bool else fl.astype(np.uint8)
+    fl = np.ascontiguousarray(fl).reshape(-1)
+    n = len(num)
+    amt = _limbs(amt, n)
+    if not len(nul) == len(acc) == len(fl) == n:
+        raise ValueError(f"a log of {len(nul)} nullifiers, {n} numbers, {len(acc)} accounts and {len(fl)} flags")
+    return nul, num, amt, acc, fl
+
+
+def audit_ledger_log(ctx_or_none, entries, root=None, totals=None, payouts=None, commitments=()):
+    """Audits a published transfer log (`entries`: what `WormholeLedger.entries()`
+    returned) against what was published beside it, each optional: `root` (4
+    felts); `totals` = (credited, total) with the total an exact int or four limb
+    sums; `payouts` as `WormholeLedger.payouts()` returned them, either form;
+    earlier `commitments` [(root_i, n_i), ...].  Returns a LedgerAuditReport whose
+    status is the first reason that fires (LEDGER_AUDIT_STATUS_TEXT), with the
+    lowest offender as the witness.  With a Context the audit runs on the device
+    (csrc/ledger.hip), with None on the host; it needs no ledger and does not alter
+    the log."""
+    nul, num, amt, acc, fl = _ledger_log_arrays(entries)
+    r = None if root is None else np.array([int(x) for x in root], dtype=np.uint64)
+    if r is not None and r.shape != (4,):
+        raise ValueError("root is 4 field elements")
+    t = None
+    if totals is not None:
+        credited, total = totals
+        t = np.array([int(credited)] + _sum_words(total), dtype=np.uint64)
+    pa = ps = pf = None
+    npay = 0
+    if payouts is not None:
+        if isinstance(payouts, tuple) and len(payouts) == 3 and isinstance(payouts[0], np.ndarray):
+            # the raw form: accounts [k][4], limb sums [k][4], first_seq [k], taken as the arrays they are
+            a, s, f = (np.asarray(x) for x in payouts)
+            npay = len(f)
+            if not (a.shape == s.shape == (npay, 4) and f.shape == (npay,)
+                    and a.dtype == s.dtype == f.dtype == np.uint64):
+                raise ValueError("raw payouts are uint64 arrays (accounts [k][4], sums [k][4], first_seq [k])")
+            pa, ps, pf = (np.ascontiguousarray(x) if npay else np.zeros_like(x, shape=(1,) + x.shape[1:])
+                          for x in (a, s, f))
+        else:
+            rows = list(payouts)
+            npay = len(rows)
+            pa = np.zeros((max(npay, 1), 4), np.uint64)
+            ps = np.zeros((max(npay, 1), 4), np.uint64)
+            pf = np.zeros(max(npay, 1), np.uint64)
+            for i, (a, s, f) in enumerate(rows):
+                pa[i], ps[i], pf[i] = _account_felts(a), _sum_words(s), int(f)
+    commitments = list(commitments)
+    cr = np.array([[int(x) for x in c[0]] for c in commitments], dtype=np.uint64).reshape(len(commitments), 4)
+    cn = np.array([int(c[1]) for c in commitments], dtype=np.uint64)
+    out = np.zeros(1, LEDGER_AUDIT_DTYPE)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    rc = lib().qp_ledger_log_audit(None if ctx_or_none is None else ctx_or_none.h, nul.ctypes.data, num.ctypes.data,
+                                   amt.ctypes.data, acc.ctypes.data, fl.ctypes.data, len(num), ptr(r), ptr(t), ptr(pa),
+                                   ptr(ps), ptr(pf), npay, cr.ctypes.data, cn.ctypes.data, len(commitments),
+                                   out.ctypes.data)
+    if rc:
+        raise QpError(rc, lib().qp_ledger_last_error(None).decode())
+    o = out[0]
+    none = lambda v: None if int(v) == NOT_FOUND else int(v)  # noqa: E731
+    return LedgerAuditReport(int(o["status"]), none(o["witness"]), none(o["first"]), [int(x) for x in o["root"]],
+                             int(o["credited"]), _total(o["sums"]), int(o["accounts"]))
 
 
 class WormholeLedger:
@@ -296,6 +435,99 @@ class WormholeLedger:
         out = np.zeros(6, np.uint64)
         self._check(lib().qp_ledger_recount(self.h, out.ctypes.data))
         return int(out[0]), int(out[1]), _total(out[2:])
+
+    # ---- the log commitment: what the settler publishes, and the exit accounts' receipts
+    def commit_log(self):
+        """(root, n): the commitment to log entries [0, n), n = admitted.  Brings the
+        log tree up to date (only the new entries are hashed); refused on an empty
+        log.  The settler publishes (root, n, payouts)."""
+        root, n = np.zeros(4, np.uint64), ctypes.c_uint64()
+        self._check(lib().qp_ledger_commit_log(self.h, root.ctypes.data, ctypes.byref(n)))
+        return [int(x) for x in root], n.value
+
+    @property
+    def log_root(self):
+        return self.commit_log()[0]
+
+    @property
+    def log_size(self):
+        return self.commit_log()[1]
+
+    def roots_at(self, ms):
+        """Per m in `ms` (each 1..admitted) the root the log had at m entries: the
+        commitment (root, m) the ledger gave, or would have given, then.  Commits
+        first, as `receipts` does."""
+        m = np.array([int(x) for x in ms], dtype=np.uint64).reshape(-1)
+        out = np.zeros((len(m), 4), np.uint64)
+        self._check(lib().qp_ledger_roots_at(self.h, m.ctypes.data, len(m), out.ctypes.data))
+        return [[int(x) for x in r] for r in out]
+
+    def root_at(self, m):
+        return self.roots_at([m])[0]
+
+    def entries_at(self, seqs):
+        """The log entries at the indices `seqs` (any order), as `entries` gives them:
+        (nullifiers [k][4], numbers [k], amounts [k] exact ints, accounts [k][4],
+        credited [k] bool)."""
+        nul, num, amt, acc, fl = self._entries_at(np.array([int(x) for x in seqs], dtype=np.uint64).reshape(-1))
+        return nul, num, [_total(a) for a in amt], acc, (fl & FLAG_CREDITED) != 0
+
+    def _entries_at(self, s):
+        k = len(s)
+        nul, acc = np.zeros((k, 4), np.uint64), np.zeros((k, 4), np.uint64)
+        num, amt, fl = np.zeros(k, np.uint64), np.zeros((k, 4), np.uint32), np.zeros(k, np.uint8)
+        self._check(lib().qp_ledger_entries_at(self.h, s.ctypes.data, k, nul.ctypes.data, num.ctypes.data,
+                                               amt.ctypes.data, acc.ctypes.data, fl.ctypes.data))
+        return nul, num, amt, acc, fl
+
+    def receipts(self, seqs):
+        """One TransferReceipt per log index in `seqs`, all under one (root, n): the
+        commitment after this call's own commit."""
+        s = np.array([int(x) for x in seqs], dtype=np.uint64).reshape(-1)
+        k = len(s)
+        sib = np.zeros((k, PATH_SLOTS, 4), np.uint64)
+        bits, depth = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        root, n = np.zeros(4, np.uint64), ctypes.c_uint64()
+        self._check(lib().qp_ledger_receipts(self.h, s.ctypes.data, k, sib.ctypes.data, bits.ctypes.data,
+                                             depth.ctypes.data, None, root.ctypes.data, ctypes.byref(n)))
+        nul, num, amt, acc, fl = self._entries_at(s)
+        root = [int(x) for x in root]
+        return [TransferReceipt([int(x) for x in nul[i]], int(num[i]), [int(x) for x in amt[i]],
+                                [int(x) for x in acc[i]], bool(fl[i] & FLAG_CREDITED), int(s[i]),
+                                sib[i, :depth[i]].tolist(), int(bits[i]), int(depth[i]), root, n.value)
+                for i in range(k)]
+
+    def receipt_for(self, nullifier):
+        """The receipt of the credited entry with this nullifier; None if it was never admitted."""
+        seq = self.find([nullifier])[0]
+        return None if seq is None else self.receipts([seq])[0]
+
+    @staticmethod
+    def check_receipt(r, root=None, n=None):
+        """True iff receipt `r` holds under the published commitment (root, n), which
+        default to the pair the receipt names.  A receipt is valid only under the
+        (root, n) it was made under.  Needs no ledger and no device."""
+        root = r.root if root is None else root
+        n = r.n if n is None else n
+        try:
+            sib = np.zeros((PATH_SLOTS, 4), np.uint64)
+            if r.siblings:
+                sib[:len(r.siblings)] = np.array([[int(x) for x in d] for d in r.siblings], dtype=np.uint64)
+            rt = np.array([int(x) for x in root], dtype=np.uint64)
+            nul = np.array([int(x) for x in r.nullifier], dtype=np.uint64)
+            acc = np.array([int(x) for x in r.account], dtype=np.uint64)
+            amt = np.array([int(x) for x in r.amount], dtype=np.uint64)
+            if rt.shape != (4,) or nul.shape != (4,) or acc.shape != (4,) or amt.shape != (4,) or (amt >> 32).any():
+                return False
+            amt = amt.astype(np.uint32)
+            for v, bound in ((n, 2**64), (r.seq, 2**64), (r.number, 2**64), (r.path_bits, 2**32), (r.depth, 2**32)):
+                if not 0 <= int(v) < bound:
+                    return False
+        except (OverflowError, ValueError, TypeError, IndexError):
+            return False  # a value that fits no field of a receipt
+        return lib().qp_ledger_receipt_check(rt.ctypes.data, int(n), int(r.seq), nul.ctypes.data, int(r.number),
+                                             amt.ctypes.data, acc.ctypes.data, 1 if r.credited else 0, sib.ctypes.data,
+                                             int(r.path_bits), int(r.depth)) == 0
 
     def cast_times(self):
         """Device times of the last cast (ms): upload, screen to credit."""
