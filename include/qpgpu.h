@@ -1069,6 +1069,57 @@ int qp_merkle_verify(qp_ctx *ctx, const uint64_t *leaves, uint32_t width, const 
                      const uint64_t *siblings, uint32_t nsib, const uint64_t *cap,
                      uint32_t cap_height, uint32_t n, uint8_t *ok_out);
 
+/* ---- the input screen: prove a batch around its bad inputs --------------------
+ * qp_prover_prove_wormhole_inputs fails as a whole on one inconsistent input and
+ * names only the lowest.  The screen decides per input what the Wormhole circuit
+ * decides (the constraints of csrc/wormhole.cpp, which restate wormhole/circuit/
+ * src/{nullifier,unspendable_account,storage_proof/mod}.rs), without building a
+ * witness: an input's status is the first of these checks that fails, in this
+ * order, and `witness` says where:                                             */
+typedef enum {
+    QP_INPUT_OK = 0,             /* the circuit is satisfiable by this input; witness 0 */
+    QP_INPUT_FIELD_RANGE = 1,    /* a 32-byte digest has an 8-byte chunk >= p (commit refuses these); witness = the
+                                    lowest of 0 nullifier, 1 unspendable account, 2 root hash, 3 funding account,
+                                    4 exit account */
+    QP_INPUT_PROOF_TOO_LONG = 2, /* num_nodes > 20; witness = num_nodes */
+    QP_INPUT_NODE_TOO_LARGE = 3, /* a node longer than 752 bytes (188 felts of 4 bytes); witness = the lowest such node */
+    QP_INPUT_NULLIFIER = 4,      /* nullifier != H(H("~nullif~" || secret || transfer_count)); witness 0 */
+    QP_INPUT_UNSPENDABLE = 5,    /* unspendable account != H(H("wormhole" || secret)); witness 0 */
+    QP_INPUT_STORAGE_NODE = 6,   /* some node i < num_nodes does not hash (its 188 felts, zero-padded) to the root
+                                    (i = 0) or to the digest found in node i - 1; witness = the lowest such i */
+    QP_INPUT_STORAGE_LEAF = 7    /* num_nodes < 20 and felts 1..3 of the leaf hash differ from felts 1..3 of the
+                                    digest found in the last node (of the root when num_nodes = 0); witness = num_nodes */
+} qp_input_status;
+/* The circuit's quirks are part of the definition: felt 0 of the leaf hash is
+ * not compared, with 20 nodes the leaf is not checked at all, the digest found
+ * in a node is zero when its hex index / 8 is 180 or more, the exit account is
+ * unconstrained.  Statuses 1-3 are decided on the host.
+ * screens in[0..n): status[n], witness[n].  With a context the hashes run on the
+ * device, on the context's stream: one upload, two launches, one download; the
+ * call allocates and frees its buffers.  ctx == NULL: the same rules in host
+ * C++.  QP_OK: the screen ran, whatever it found.  QP_ERR_ARG for the whole
+ * call: a null array, or an input whose nodes / node_lens / indices is null
+ * with num_nodes > 0, or a null node with a length: programming errors, not bad
+ * inputs.  zk_randomness is not read.  n == 0: QP_OK.                          */
+int qp_wormhole_inputs_screen(qp_ctx *ctx /* NULL: host */, const qp_wormhole_inputs *in, uint32_t n,
+                              uint32_t *status /* [n] */, uint32_t *witness /* [n] */);
+/* one line of text for a qp_input_status (a static string; "unknown input status" beyond the enum) */
+const char *qp_input_status_text(uint32_t status);
+/* the screen (device path, the prover's context), then qp_prover_prove_wormhole_inputs' machinery,
+ * unchanged, over the inputs with status 0, gathered in their order into dense batches of at most
+ * max_batch: proof i at out + i * stride, the row of its ORIGINAL index, lens[i] its length; a bad
+ * input gets lens[i] = 0 and its row is left alone.  QP_OK when the call ran, however many inputs
+ * were bad; with no good input no witness or proving kernel is launched.  If an input the screen
+ * passed still meets a witness conflict the call fails with QP_ERR_WITNESS and "input screen and
+ * circuit disagree" before the prover's message: a bug in the screen, never hidden.  lens may be
+ * NULL; status and witness may not.                                           */
+int qp_prover_prove_wormhole_inputs_status(qp_prover *p, const qp_wormhole_inputs *in, uint32_t n, uint8_t *out,
+                                           size_t stride, size_t *lens, uint32_t *status, uint32_t *witness);
+/* times of this thread's last device-path qp_wormhole_inputs_screen (ms): [0] host checks and
+ * packing (wall), HIP-event times of [1] the upload, [2] the node kernel, [3] the resolve kernel;
+ * all 0 after a host-path call.  Diagnostic entry point (tools/screen_bench.py). */
+int qp_wormhole_inputs_screen_times(double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1225,6 +1225,65 @@ int qp_prover_prove_wormhole_inputs(qp_prover *P, const qp_wormhole_inputs *in, 
   }
 }
 
+// The screen (input_screen.cpp, the prover's context), then prove_inputs, unchanged, over the inputs it
+// passed: dense batches of at most max_batch in their order.  A batch whose inputs are neighbours in
+// the caller's array is proven in place; any other through a gathered copy of the structs and a
+// staging buffer, its proofs copied to the rows of their original indices.
+int qp_prover_prove_wormhole_inputs_status(qp_prover *P, const qp_wormhole_inputs *in, uint32_t n, uint8_t *out,
+                                           size_t stride, size_t *lens, uint32_t *status, uint32_t *witness) {
+  if (!P || !in || !out || !n || !status || !witness) return QP_ERR_ARG;
+  if (P->circuit->kind != qp_circuit::WORMHOLE) {
+    P->ctx->err = "prover circuit is not the Wormhole circuit";
+    return QP_ERR_ARG;
+  }
+  if (stride < P->proof_len) {
+    P->ctx->err = "output stride smaller than the proof size";
+    return QP_ERR_ARG;
+  }
+  int rc = qp_wormhole_inputs_screen(P->ctx, in, n, status, witness);
+  if (rc) return rc;
+  try {
+    std::vector<uint32_t> good;
+    for (uint32_t i = 0; i < n; i++) {
+      if (lens) lens[i] = 0;
+      if (status[i] == 0) good.push_back(i);
+    }
+    if (good.empty()) return QP_OK;
+    TRY(hipSetDevice(P->ctx->device));
+    std::vector<qp_wormhole_inputs> dense;
+    std::vector<uint8_t> stage;
+    std::vector<size_t> stage_lens;
+    for (size_t done = 0; done < good.size();) {
+      const uint32_t nb = (uint32_t)std::min<size_t>(P->max_batch, good.size() - done);
+      const uint32_t first = good[done];
+      const bool in_place = good[done + nb - 1] - first == nb - 1;
+      if (in_place) {
+        rc = prove_inputs(P, wormhole_fill, (const uint8_t *)(in + first), sizeof(qp_wormhole_inputs), nb,
+                          out + (size_t)first * stride, stride, lens ? lens + first : nullptr);
+      } else {
+        dense.resize(nb);
+        stage.resize((size_t)nb * P->proof_len);
+        stage_lens.assign(nb, 0);
+        for (uint32_t b = 0; b < nb; b++) dense[b] = in[good[done + b]];
+        rc = prove_inputs(P, wormhole_fill, (const uint8_t *)dense.data(), sizeof(qp_wormhole_inputs), nb, stage.data(),
+                          P->proof_len, stage_lens.data());
+        for (uint32_t b = 0; b < nb && !rc; b++) {
+          memcpy(out + (size_t)good[done + b] * stride, stage.data() + (size_t)b * P->proof_len, stage_lens[b]);
+          if (lens) lens[good[done + b]] = stage_lens[b];
+        }
+      }
+      if (rc == QP_ERR_WITNESS)
+        P->ctx->err = "input screen and circuit disagree: " + P->ctx->err + " (proofs are numbered among the " +
+                      std::to_string(nb) + " inputs the screen passed from input " + std::to_string(first) + " on)";
+      if (rc) return rc;
+      done += nb;
+    }
+    return QP_OK;
+  } catch (const std::bad_alloc &) {
+    return QP_ERR_OOM;
+  }
+}
+
 int qp_prover_prove_voting_inputs(qp_prover *P, const qp_voting_inputs *in, uint32_t nproofs, uint8_t *out,
                                   size_t stride, size_t *lens) {
   if (!P || !in || !out || !nproofs) return QP_ERR_ARG;

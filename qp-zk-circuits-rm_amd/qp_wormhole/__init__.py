@@ -21,6 +21,7 @@ from .ballot import (AUDIT_STATUS_TEXT, BALLOT_STATUS_TEXT, AuditReport, BallotB
                      BallotResult, audit_log)
 from .ledger import (LEDGER_AUDIT_STATUS_TEXT, TRANSFER_STATUS_TEXT, LedgerAuditReport, TransferReceipt,  # noqa: F401,E402
                      TransferResult, WormholeLedger, audit_ledger_log)
+from .screen import INPUT_STATUS_TEXT, InputStatus, screen_inputs  # noqa: F401,E402
 
 __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorageProof", "PublicCircuitInputs",
            "Witness", "VoteCircuitData", "VotePrivateInputs", "VotePublicInputs", "Prover", "ProofWithPublicInputs", "WormholeProver", "Context", "PolynomialBatch", "QpError", "ifft", "lde", "poseidon_permute", "lib", "header_symbols",
@@ -30,4 +31,4 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BallotReceipt",
            "BALLOT_STATUS_TEXT", "AuditReport", "AUDIT_STATUS_TEXT", "audit_log",
            "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT", "TransferReceipt", "LedgerAuditReport",
-           "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log"]
+           "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log", "INPUT_STATUS_TEXT", "InputStatus", "screen_inputs"]

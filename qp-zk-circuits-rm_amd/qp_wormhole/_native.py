@@ -143,6 +143,12 @@ def lib():
                                                            ctypes.POINTER(ctypes.c_size_t)]),
         "qp_prover_prove_voting_inputs": (ctypes.c_int, [VP, VP, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                                          ctypes.POINTER(ctypes.c_size_t)]),
+        "qp_wormhole_inputs_screen": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, VP]),
+        "qp_input_status_text": (ctypes.c_char_p, [ctypes.c_uint32]),
+        "qp_prover_prove_wormhole_inputs_status": (ctypes.c_int, [VP, VP, ctypes.c_uint32, ctypes.c_char_p,
+                                                                  ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                                                  VP, VP]),
+        "qp_wormhole_inputs_screen_times": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)]),
         "qp_prover_prove_aggregation": (ctypes.c_int, [VP, VP, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
                                                        ctypes.POINTER(ctypes.c_size_t)]),
         "qp_registry_new": (ctypes.c_int, [VP, U64P, ctypes.c_uint64, PP]),

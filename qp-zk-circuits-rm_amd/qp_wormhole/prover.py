@@ -97,13 +97,38 @@ class Prover:
                            lambda out, lens: fn(self.h, ctypes.cast(arr, ctypes.c_void_p), nb, out, self.proof_size,
                                                 lens))
 
-    def prove_inputs(self, inputs):
+    def prove_inputs(self, inputs, on_bad="raise"):
         """End to end: commit(inputs) + prove() for a list of CircuitInputs (Wormhole)
         or VoteCircuitData (voting) -- commit on the host pool, witness generation on
-        the device (qp_prover_prove_{wormhole,voting}_inputs)."""
-        if not inputs:
-            return []
-        return self.prove_inputs_array(self.inputs_array(inputs), len(inputs))
+        the device (qp_prover_prove_{wormhole,voting}_inputs).
+
+        on_bad="raise": one inconsistent input fails the whole call (QpError naming the
+        lowest).  on_bad="skip" (Wormhole only): the inputs are screened on the device
+        first (qp_prover_prove_wormhole_inputs_status), the good ones proven, and the
+        call returns (proofs, statuses): proofs[i] the bytes or None for a bad input,
+        statuses[i] an InputStatus(status, witness)."""
+        if on_bad == "raise":
+            if not inputs:
+                return []
+            return self.prove_inputs_array(self.inputs_array(inputs), len(inputs))
+        if on_bad != "skip":
+            raise ValueError(f"on_bad must be 'raise' or 'skip', not {on_bad!r}")
+        if self.circuit.kind != "wormhole":
+            raise ValueError("on_bad='skip' screens Wormhole inputs only")
+        from .screen import InputStatus
+        nb = len(inputs)
+        if not nb:
+            return [], []
+        arr = self.inputs_array(inputs)
+        status, witness = np.zeros(nb, np.uint32), np.zeros(nb, np.uint32)
+        with self._lock:
+            out, lens = self._out_buffers(nb)
+            self.ctx.check(lib().qp_prover_prove_wormhole_inputs_status(
+                self.h, ctypes.cast(arr, ctypes.c_void_p), nb, out, self.proof_size, lens, status.ctypes.data,
+                witness.ctypes.data), "qp_prover_prove_wormhole_inputs_status")
+            mv, ps = self._mv, self.proof_size
+            proofs = [mv[i * ps:i * ps + lens[i]].tobytes() if status[i] == 0 else None for i in range(nb)]
+        return proofs, [InputStatus(int(s), int(w)) for s, w in zip(status, witness)]
 
     def prove_aggregation(self, verifier_only: bytes, chunks, zk_randomness=None):
         """aggregate_chunk (tree.rs:106-143) for every chunk of inner proofs as one
