@@ -865,6 +865,62 @@ int qp_ledger_log_audit(qp_ctx *ctx /* NULL: host */, const uint64_t *nullifiers
                         const uint64_t *commit_roots, const uint64_t *commit_ns, uint32_t ncommit,
                         qp_ledger_audit_report *out);
 
+/* ---- reopening a ledger from its published log --------------------------------
+ * With a context the ledger's only copy of the nullifier set, the account table
+ * and the sums is in device memory; a settler whose process died counts on from
+ * the log.  The arguments of qp_ledger_new with their refusals, the log in the
+ * layout qp_ledger_entries returns and qp_ledger_log_audit takes, and cast_count,
+ * the number the next transfer takes.  QP_ERR_ARG unless capacity >= max(n, 1)
+ * and cast_count > numbers[n - 1]; n == 0 is allowed with any cast_count and
+ * gives what qp_ledger_new gives, plus the counter.  Runs the audit's reasons 1-3
+ * (NON_CANONICAL, ORDER, CREDIT_RULE) and ROOT when expect_root is given, on the
+ * new ledger's own buffers; a failing audit is QP_ERR_FORMAT, leaves no ledger,
+ * and qp_ledger_last_error(NULL) names the reason and the witness.  A failed HIP
+ * step: QP_ERR_HIP, no ledger.  *out is written on QP_OK only.  The restored
+ * ledger keeps the log, laid out for `capacity`, a nullifier table and an account
+ * table for `capacity`, the sums of the entries whose credited bit is set and
+ * each entry's account slot: cast = cast_count, admitted = n, credited and
+ * accounts as the log gives them; from there it is an ordinary ledger.  With
+ * expect_root the log tree is built by the ledger's own first commit and kept, so
+ * a qp_ledger_commit_log that follows returns (expect_root, n) with nothing
+ * launched; without it nothing is hashed until the first commit.  Device: one
+ * upload of the log, the audit's screen, a synchronise (a non-canonical log ends
+ * there), the whole-log insert, the audit's resolve, then the leaves and the tree
+ * when a root is expected.                                                      */
+int qp_ledger_restore(qp_ctx *ctx /* NULL: host */, const uint64_t *roots, uint32_t nroots,
+                      const uint64_t *padding_pis /* [16] or NULL */, uint64_t capacity,
+                      const uint64_t *nullifiers, const uint64_t *numbers, const uint32_t *amounts,
+                      const uint64_t *accounts, const uint8_t *flags, uint64_t n, uint64_t cast_count,
+                      const uint64_t *expect_root /* NULL: none */, qp_ledger **out);
+
+/* ---- payout rounds --------------------------------------------------------------
+ * qp_ledger_payouts is cumulative since the ledger opened; a settler pays per
+ * round, per published commitment (root_k, n_k): round k pays the log entries
+ * [n_{k-1}, n_k).  Only entries with m0 <= seq < m1 and flags bit 0 set count;
+ * the flags are trusted, as qp_ledger_payouts and qp_ledger_recount trust them
+ * (the audit is what checks flags).  An account credited before m0 and again
+ * inside the range appears with its in-range sums and its in-range first_seq.
+ * The rounds of consecutive ranges add up, account by account, to the cumulative
+ * payouts, and [0, admitted) gives those.  With a context the range is credited
+ * into a scratch account table of the call's own (the power of two >= 2 (m1 -
+ * m0) slots) and the owners are compacted in log order; the ledger's tables, log
+ * and tree are only read.                                                        */
+/* the accounts credited by log entries [m0, m1), 0 <= m0 <= m1 <= admitted: one row per account with
+ * a credited entry in the range: account, the four limb sums over those entries, first_seq = the
+ * lowest such seq; rows in first_seq order.  *count = the number of rows, always written; at most
+ * cap rows are stored (cap == 0 with null arrays: a sizing call).  The ledger is not changed.
+ * m0 == m1: *count = 0.  QP_ERR_ARG, nothing stored: m0 > m1, m1 > admitted, a null count, cap > 0
+ * with a null array.                                                                             */
+int qp_ledger_payouts_between(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t cap, uint64_t *accounts,
+                              uint64_t *sums, uint64_t *first_seq, uint64_t *count);
+/* the same over a published log (accounts_log [n][4], amounts [n][4], flags [n], 1 <= n <= 2^31), no
+ * ledger needed; ctx == NULL: host.  Only the entries of [m0, m1) are read (with a context: uploaded):
+ * a non-canonical account or flags > 1 among them is QP_ERR_ARG, as the range errors above; the
+ * reason is qp_ledger_last_error(NULL)'s.                                                        */
+int qp_ledger_log_payouts_between(qp_ctx *ctx, const uint64_t *accounts_log, const uint32_t *amounts,
+                                  const uint8_t *flags, uint64_t n, uint64_t m0, uint64_t m1, uint64_t cap,
+                                  uint64_t *accounts, uint64_t *sums, uint64_t *first_seq, uint64_t *count);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

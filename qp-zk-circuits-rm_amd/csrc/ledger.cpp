@@ -8,6 +8,10 @@
 // The log commitment (commit_log, receipts, entries_at, roots_at and the
 // receipt check: ledger_log.h) is brought up to date on demand; a cast does
 // not touch it, and the tree is allocated by the first commit only.
+// qp_ledger_restore reopens a ledger from a published log through the audit's
+// passes (ledger_audit.h) over the new ledger's own buffers;
+// qp_ledger_payouts_between is a payout round over the ledger's log
+// (ledger_rounds.h; the device launches are ledger_rounds.cpp's).
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <algorithm>
@@ -18,9 +22,11 @@
 #include <vector>
 #include "acc_tree.h"
 #include "ctx.h"
+#include "ledger_audit.h"
 #include "ledger_audit_device.h"
 #include "ledger_kernels.h"
 #include "ledger_log.h"
+#include "ledger_rounds.h"
 #include "ledger_table.h"
 #include "verifier.h"
 
@@ -437,6 +443,72 @@ int commit_log(qp_ledger *l) {
   return QP_OK;
 }
 
+// The device half of a restore, over the fresh ledger's own log and tables (sized for its capacity):
+// one upload of the log; the audit's screen; a synchronise, where a non-canonical log ends (*canonical
+// false, nothing inserted or hashed); the whole-log insert into the nullifier table; the audit's
+// resolve, a launch of its own, which reads the final slot words for the credit rule and credits the
+// flagged entries into the account table and the sums.  What those launches leave is a live ledger's
+// state (both tables, astay, the sums), so no kernel of the restore's own is needed; the counts go from
+// the audit's report into the ledger's counters.  The root, when one is expected, is the restored
+// ledger's own commit afterwards.
+int restore_device(qp_ledger *l, const ql::AuditLog &g, ql::AuditFacts &f, bool *canonical) {
+  qp_ctx *c = l->ctx;
+  hipStream_t s = c->stream;
+  const uint64_t n = g.n;
+  const qpk::LedgerDev d = l->t.dev();
+  DevBuf d_rep, d_stay;
+  *canonical = false;
+  QP_HIP_TRY(l, hipSetDevice(c->device));
+  QP_HIP_TRY(l, d_rep.alloc((sizeof(qpk::LedgerAuditDev) + 7) / 8));
+  QP_HIP_TRY(l, d_stay.alloc((size_t)((n + 1) / 2)));
+  QP_HIP_TRY(l, hipMemcpyAsync(d.nullifier, g.nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(d.number, g.numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(d.amount, g.amounts, (size_t)n * 16, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(d.account, g.accounts, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(d.flags, g.flags, (size_t)n, hipMemcpyHostToDevice, s));
+  qpk::LedgerAuditDev *rep = d_rep.as<qpk::LedgerAuditDev>();
+  qpk::LedgerAuditDev h;
+  memset(&h, 0, sizeof h);
+  h.credit_rule = ~0ull;
+  h.non_canonical = h.order = h.payout = qpk::LEDGER_AUDIT_NO_SEQ;
+  QP_HIP_TRY(l, hipMemcpyAsync(rep, &h, sizeof h, hipMemcpyHostToDevice, s));
+  qpk::ledger_audit_screen(d, (uint32_t)n, rep, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  if (h.non_canonical != qpk::LEDGER_AUDIT_NO_SEQ) {
+    f.non_canonical = h.non_canonical;
+    return QP_OK;
+  }
+  qpk::ledger_insert(d, 0, (uint32_t)n, d_stay.as<uint32_t>(), &rep->ctr, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  qpk::ledger_audit_resolve(d, (uint32_t)n, d_stay.as<uint32_t>(), rep, s);
+  QP_HIP_TRY(l, hipGetLastError());
+  QP_HIP_TRY(l, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  if (int rc = error_word(l, "qp_ledger_restore", h.ctr.err)) return rc;
+  if (h.ctr.credited > n || h.ctr.accounts > h.ctr.credited) {
+    l->err = "qp_ledger_restore: the resolve counted more credited entries or accounts than the log has (an internal "
+             "invariant broke)";
+    return QP_ERR_HIP;
+  }
+  if (h.order != qpk::LEDGER_AUDIT_NO_SEQ) f.order = h.order;
+  if (h.credit_rule != ~0ull) {
+    f.credit_rule = h.credit_rule >> 32;
+    f.first = h.credit_rule & 0xFFFFFFFFu;
+  }
+  f.credited = h.ctr.credited;
+  f.accounts = h.ctr.accounts;
+  const qpk::LedgerCounters now{h.ctr.credited, h.ctr.accounts, 0, 0};
+  QP_HIP_TRY(l, hipMemcpyAsync(l->d_ctr.p, &now, sizeof now, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(l, hipStreamSynchronize(s));
+  l->count = n;
+  l->credited = now.credited;
+  l->accounts = now.accounts;
+  *canonical = true;
+  return QP_OK;
+}
+
 int entries_at_device(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
                       uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
   hipStream_t s = l->ctx->stream;
@@ -736,6 +808,37 @@ int qp_ledger_payouts(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accoun
   return QP_OK;
 }
 
+int qp_ledger_payouts_between(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t cap, uint64_t *accounts, uint64_t *sums,
+                              uint64_t *first_seq, uint64_t *count) {
+  if (!l) return QP_ERR_ARG;
+  if (l->dead) return dead_ledger(l, "qp_ledger_payouts_between");
+  const std::string why = ql::round_refusal(l->admitted(), m0, m1, cap, accounts, sums, first_seq, count);
+  if (!why.empty()) {
+    l->err = "qp_ledger_payouts_between: " + why;
+    return QP_ERR_ARG;
+  }
+  if (m0 == m1) {
+    *count = 0;
+    return QP_OK;
+  }
+  try {
+    if (l->ctx) {
+      const qpk::LedgerDev d = l->t.dev();
+      const int rc = qla::rounds_device(l->ctx, l->err, d.account + m0 * 4, d.amount + m0 * 4, d.flags + m0, m1 - m0, m0,
+                                        cap, accounts, sums, first_seq, count);
+      if (rc) l->err = "qp_ledger_payouts_between: " + l->err;
+      return rc == QP_ERR_OOM ? rc : device_step(l, rc);  // the scratch is the call's own: the ledger stands
+    }
+    const ql::HostLedger &h = l->host;
+    ql::RoundRows rows;
+    ql::round_payouts_host(h.account.data(), h.amount.data(), h.flags.data(), m0, m1, rows);
+    ql::round_store(rows, cap, accounts, sums, first_seq, count);
+    return QP_OK;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, "qp_ledger_payouts_between");
+  }
+}
+
 int qp_ledger_totals_for(qp_ledger *l, const uint64_t *accounts, uint32_t k, uint64_t *sums, uint8_t *found) {
   if (!l) return QP_ERR_ARG;
   if (l->dead) return dead_ledger(l, "qp_ledger_totals_for");
@@ -869,6 +972,61 @@ int qp_ledger_roots_at(qp_ledger *l, const uint64_t *ms, uint32_t k, uint64_t *r
   }
   for (uint32_t i = 0; i < k; i++) l->hlog.prefix_root(ms[i], ql::log_node, roots_out + (size_t)i * 4);
   return QP_OK;
+}
+
+int qp_ledger_restore(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const uint64_t *padding_pis, uint64_t capacity,
+                      const uint64_t *nullifiers, const uint64_t *numbers, const uint32_t *amounts,
+                      const uint64_t *accounts, const uint8_t *flags, uint64_t n, uint64_t cast_count,
+                      const uint64_t *expect_root, qp_ledger **out) {
+  if (!out) return QP_ERR_ARG;
+  auto refuse = [c](int rc, const std::string &why) {
+    qla::set_ledgerless_error(c, "qp_ledger_restore: " + why);
+    return rc;
+  };
+  if (n && (!nullifiers || !numbers || !amounts || !accounts || !flags)) return refuse(QP_ERR_ARG, "null log buffer");
+  if (expect_root && (!n || !ql::canonical(expect_root, 4)))
+    return refuse(QP_ERR_ARG, n ? "the expected root is not four canonical field elements" : "an empty log has no root");
+  try {
+    const std::string why = ql::restore_refusal(numbers, n, capacity, cast_count);
+    if (!why.empty()) return refuse(QP_ERR_ARG, why);
+    qp_ledger *fresh = nullptr;
+    int rc = qp_ledger_new(c, roots, nroots, padding_pis, capacity, &fresh);
+    if (rc) return rc;  // qp_ledger_new left its reason
+    std::unique_ptr<qp_ledger, void (*)(qp_ledger *)> l(fresh, qp_ledger_free);
+    l->cast = cast_count;
+    if (!n) {
+      *out = l.release();
+      return QP_OK;
+    }
+    ql::AuditLog g;
+    g.nullifiers = nullifiers, g.numbers = numbers, g.amounts = amounts, g.accounts = accounts, g.flags = flags, g.n = n;
+    ql::AuditFacts f;
+    ql::AuditReport r;
+    bool canonical = false;
+    if (c) {
+      if ((rc = restore_device(l.get(), g, f, &canonical))) return refuse(rc, l->err);
+    } else {
+      ql::HostLog unused;  // the tree comes from the restored ledger's own commit below
+      canonical = ql::audit_facts_host(g, ql::AuditClaims(), l->host, unused, f, capacity, false);
+    }
+    if (!canonical) {
+      ql::audit_non_canonical(f.non_canonical, r);
+    } else {
+      ql::restore_verdict(f, n, nullptr, r);
+      if (r.status == ql::AUDIT_OK && expect_root) {
+        // The leaves and the tree, laid out for the capacity: the restored ledger's own first commit.
+        // The tree is kept, so a commit_log() that follows returns this pair with nothing launched.
+        if ((rc = commit_log(l.get()))) return refuse(rc, l->err);
+        memcpy(f.root, l->log_root, 32);
+        ql::restore_verdict(f, n, expect_root, r);
+      }
+    }
+    if (r.status != ql::AUDIT_OK) return refuse(QP_ERR_FORMAT, ql::audit_failure_text(r));
+    *out = l.release();
+    return QP_OK;
+  } catch (const std::bad_alloc &) {
+    return refuse(QP_ERR_OOM, "out of host memory");
+  }
 }
 
 int qp_ledger_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4],

@@ -7,9 +7,12 @@
 // Blocks of 256 lanes (LEDGER_BLOCK).  The log commitment's leaf kernel is the
 // exception: VALU-bound, two permutations per lane (poseidon_dev.h).  The audit
 // of a published log reuses the insert, the probes, the recount and the payees'
-// compaction over a table of the audit's own.
+// compaction over a table of the audit's own; a restore runs the audit's screen,
+// insert and resolve over the new ledger's tables; a payout round credits a
+// range of the log into a scratch account table and reuses the same compaction.
 #include "ballot_device.h"
 #include "ledger_kernels.h"
+#include "ledger_rounds.h"
 #include "ledger_table.h"
 #include "poseidon_dev.h"
 
@@ -484,6 +487,30 @@ __global__ void __launch_bounds__(256) k_ledger_audit_payouts(LedgerDev d, const
     differs = !ql::key_equal(want, got) || first_seq[i] != seq || !ql::sums_equal(ws, ls);
   }
   if (lowest_offender(differs)) atomicMin(&rep->payout, i);
+}
+
+// ---- payout rounds (ledger_rounds.h has the rule).  v is a view of log entries [m0, m1) with a
+// scratch account table of the call's own: v.account, v.amount and v.flags point at entry m0 and are
+// only read; v.aslot (all empty), v.sum (zero) and v.astay belong to the call; a lane's index j = seq -
+// m0 is what the slot words hold.  One lane per entry of the range.  A credited lane is credit_entry
+// over the view: the ledger's probe (facts 1-3 of table_probe with limit = k <= S / 2, so the slot of an
+// account ends at the lowest j credited to it in the range, by an agent-scope atomicMin), then four
+// 64-bit atomicAdds onto the sums of the slot where the key stays.  Nothing reads a slot word or a sum
+// in this launch: the owners are compacted by k_ledger_payee_count / k_ledger_scan /
+// k_ledger_payee_write over the view and gathered by k_ledger_payouts, launches later.
+__global__ void __launch_bounds__(256) k_ledger_round_credit(LedgerDev v, uint32_t k, uint32_t *__restrict__ err) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= k) return;
+  bool claimed;
+  if (!ql::round_credits(v.flags[j]))
+    v.astay[j] = LEDGER_NO_SLOT;
+  else if (!credit_entry(v, j, k, &claimed))
+    atomicOr(err, 4u);  // the probe ran out of slots: cannot be reached
+}
+
+void ledger_round_credit(const LedgerDev &v, uint32_t k, uint32_t *err, hipStream_t s) {
+  if (!k) return;
+  k_ledger_round_credit<<<ledger_blocks(k), LEDGER_BLOCK, 0, s>>>(v, k, err);
 }
 
 void ledger_leaves(const LedgerDev &d, uint32_t first, uint32_t end, uint64_t *dig, LedgerCounters *ctr,

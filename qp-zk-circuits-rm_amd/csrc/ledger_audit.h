@@ -2,8 +2,10 @@
 // eight statuses and their witnesses, the verdict both paths share, and the host
 // path itself (HostLedger's probes give the owner of a nullifier, the account
 // sums and the payees; HostLog the root and the prefix roots).  Plain C++ next
-// to ledger_log.h (no HIP).  Included by ledger_audit.cpp and the stand-alone
-// check tools/ledger_log_check.cpp.
+// to ledger_log.h (no HIP).  Included by ledger_audit.cpp, by ledger.cpp
+// (qp_ledger_restore runs reasons 1-3 and the root on the ledger it builds) and
+// by the stand-alone checks tools/ledger_log_check.cpp and
+// tools/ledger_restore_check.cpp.
 //
 // Definitions (DESIGN §14 and qpgpu.h state the same):
 //   A published log is what qp_ledger_entries returns: nullifiers[n][4],
@@ -168,14 +170,17 @@ inline void audit_screen_host(const AuditLog &g, AuditFacts &f) {
 // nullifier table in seq order, so a slot's owner is the lowest seq of its nullifier; the flags are
 // read and never written, and an entry whose flag says credited is credited.  Afterwards `led` holds
 // both tables, the sums and the payees of that log, and `log` the log tree over [0, n).  false: the
-// log is not canonical (f.non_canonical is set, nothing else was done).
-inline bool audit_facts_host(const AuditLog &g, const AuditClaims &c, HostLedger &led, HostLog &log, AuditFacts &f) {
+// log is not canonical (f.non_canonical is set, nothing else was done).  A restore opens `led` for the
+// new ledger's capacity >= n, and then `led` is the ledger of that log; it leaves the tree out
+// (want_root false: `log` is not touched and f.root stays zero) and commits the ledger it got.
+inline bool audit_facts_host(const AuditLog &g, const AuditClaims &c, HostLedger &led, HostLog &log, AuditFacts &f,
+                             uint64_t capacity = 0, bool want_root = true) {
   f = AuditFacts();
   audit_screen_host(g, f);
   if (f.non_canonical != AUDIT_NONE) return false;
   const uint64_t n = g.n;
   led = HostLedger();
-  led.open(n);
+  led.open(capacity ? capacity : n);
   led.nullifier.assign(g.nullifiers, g.nullifiers + n * 4);
   led.number.assign(g.numbers, g.numbers + n);
   led.amount.assign(g.amounts, g.amounts + n * 4);
@@ -206,6 +211,7 @@ inline bool audit_facts_host(const AuditLog &g, const AuditClaims &c, HostLedger
         f.payout = i;
     }
   }
+  if (!want_root) return true;
   log.open(n);
   log.leaves(g.nullifiers, g.numbers, g.amounts, g.accounts, g.flags, 0, n);
   log.append(n, log_node);
@@ -220,6 +226,47 @@ inline void audit_host(const AuditLog &g, const AuditClaims &c, AuditReport &r) 
   AuditFacts f;
   if (!audit_facts_host(g, c, led, log, f)) return audit_non_canonical(f.non_canonical, r);
   audit_verdict(f, g.n, c, [&log](uint32_t, uint64_t m, uint64_t out[4]) { log.prefix_root(m, log_node, out); }, r);
+}
+
+// ---- qp_ledger_restore: a ledger reopened from a published log.  It runs the audit's reasons 1-3 on
+// the new ledger's own buffers, and 6 (the root) when one is expected; the claims of reasons 4, 5 and 7
+// are not part of a restore.
+
+// what a restore refuses beside a failing audit: "" when (capacity, cast_count) fit the log
+inline std::string restore_refusal(const uint64_t *numbers, uint64_t n, uint64_t capacity, uint64_t cast_count) {
+  if (n > MAX_CAPACITY) return "a log of " + std::to_string(n) + " entries: a ledger holds at most 2^31";
+  if (!capacity || capacity > MAX_CAPACITY || capacity < n)
+    return "capacity " + std::to_string(capacity) + " for a log of " + std::to_string(n) +
+           " entries: it must hold them (and at least one) and be at most 2^31";
+  if (n && cast_count <= numbers[n - 1])
+    return "cast_count " + std::to_string(cast_count) + " is not above the log's last transfer number " +
+           std::to_string(numbers[n - 1]);
+  return "";
+}
+
+// the verdict of a restore from the facts of a canonical log; root: the expected root, with f.root the
+// restored ledger's commitment, or null
+inline void restore_verdict(const AuditFacts &f, uint64_t n, const uint64_t *root, AuditReport &r) {
+  AuditClaims c;
+  c.root = root;
+  audit_verdict(f, n, c, [](uint32_t, uint64_t, uint64_t *) {}, r);
+}
+
+// the words qp_wormhole.LEDGER_AUDIT_STATUS_TEXT has for a status
+inline const char *audit_status_text(uint32_t status) {
+  static const char *const text[] = {"ok", "non-canonical entry", "transfer numbers out of order", "credit rule broken",
+                                     "claimed totals differ", "claimed payouts differ", "claimed root differs",
+                                     "earlier commitment does not hold"};
+  return status <= AUDIT_COMMITMENT ? text[status] : "unknown status";
+}
+
+// the reason and the witness of a failing audit, for a refusal's message
+inline std::string audit_failure_text(const AuditReport &r) {
+  std::string s = std::string("the log fails its audit: ") + audit_status_text(r.status);
+  if (r.witness != AUDIT_NONE) s += " (entry " + std::to_string(r.witness);
+  if (r.first != AUDIT_NONE) s += ", its nullifier first at entry " + std::to_string(r.first);
+  if (r.witness != AUDIT_NONE) s += ")";
+  return s;
 }
 
 }  // namespace ql

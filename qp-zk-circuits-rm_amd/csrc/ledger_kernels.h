@@ -121,5 +121,17 @@ void ledger_audit_resolve(const LedgerDev &d, uint32_t n, const uint32_t *stay, 
 // (accounts [k][4], sums [k][4], first_seq [k], device) against payee[i]
 void ledger_audit_payouts(const LedgerDev &d, const uint32_t *payee, uint32_t k, const uint64_t *accounts,
                           const uint64_t *sums, const uint64_t *first_seq, LedgerAuditDev *rep, hipStream_t s);
+// A restore (ledger_audit.h) is the audit's launches over the new ledger's own LedgerDev, whose tables
+// are sized for its capacity: ledger_audit_screen, ledger_insert(d, 0, n, ...), ledger_audit_resolve.
+// What they leave (both tables, astay, the sums, rep->ctr's counts) is a live ledger's state.
+
+// ---- payout rounds (ledger_rounds.h has the rule): the accounts credited by log entries [m0, m1).
+// A round's view v: account, amount and flags point at entry m0 of a log (read only); aslot [mask + 1]
+// (all empty), sum [mask + 1][4] (zero) and astay [k] are scratch of the call, mask + 1 = the power of
+// two >= 2 k; nullifier, number and nslot are null and never touched.  Indices are j = seq - m0.
+// every credited entry j < k into the view's account table, its limbs onto the slot's sums; *err |= 4 if
+// a probe found no slot.  The owners and the rows come from ledger_payee_count / ledger_scan /
+// ledger_payee_write / ledger_payouts over the same view, in later launches.
+void ledger_round_credit(const LedgerDev &v, uint32_t k, uint32_t *err, hipStream_t s);
 
 }  // namespace qpk

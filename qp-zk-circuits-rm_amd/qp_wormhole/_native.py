@@ -214,6 +214,13 @@ def lib():
                                                    ctypes.c_uint8, VP, ctypes.c_uint32, ctypes.c_uint32]),
         "qp_ledger_log_audit": (ctypes.c_int, [VP, VP, VP, VP, VP, VP, ctypes.c_uint64, VP, VP, VP, VP, VP,
                                                ctypes.c_uint64, VP, VP, ctypes.c_uint32, VP]),
+        "qp_ledger_restore": (ctypes.c_int, [VP, VP, ctypes.c_uint32, VP, ctypes.c_uint64, VP, VP, VP, VP, VP,
+                                             ctypes.c_uint64, ctypes.c_uint64, VP, PP]),
+        "qp_ledger_payouts_between": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP,
+                                                     ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_log_payouts_between": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_uint64, ctypes.c_uint64,
+                                                         ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP,
+                                                         ctypes.POINTER(ctypes.c_uint64)]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

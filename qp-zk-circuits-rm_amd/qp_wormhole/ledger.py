@@ -28,6 +28,11 @@ Merkle root (the ballot box's kind of tree over a 14-felt leaf), `receipts`
 ties single entries to it, `check_receipt` checks one without a ledger, and
 `audit_ledger_log` checks a published log against the root, the totals, the
 payouts and earlier commitments published beside it.
+
+A settler pays per round, per commitment (root_k, n_k): `payouts_between(n_{k-1},
+n_k)` is what round k pays, `ledger_log_payouts` the same from the published log
+alone.  `WormholeLedger.restore` reopens a ledger from its published log, so a
+settler whose process died counts on with the nullifier set it had.
 """
 import ctypes
 from collections import namedtuple
@@ -222,6 +227,41 @@ def audit_ledger_log(ctx_or_none, entries, root=None, totals=None, payouts=None,
                              int(o["credited"]), _total(o["sums"]), int(o["accounts"]))
 
 
+def _round_rows(call, m0, m1, raw):
+    """the rows of a payout round in one call (a range has at most m1 - m0 accounts, so no sizing call,
+    which would run the round twice); call(cap, accounts, sums, first_seq, count) raises on a refusal"""
+    room = max(m1 - m0, 0) if m1 <= MAX_CAPACITY else 0  # a range the call refuses: no buffers
+    acc, sums, seq = np.zeros((room, 4), np.uint64), np.zeros((room, 4), np.uint64), np.zeros(room, np.uint64)
+    count = ctypes.c_uint64()
+    call(room, acc.ctypes.data, sums.ctypes.data, seq.ctypes.data, ctypes.byref(count))
+    k = count.value
+    acc, sums, seq = acc[:k].copy(), sums[:k].copy(), seq[:k].copy()
+    if raw:
+        return acc, sums, seq
+    return [(acc[i].astype("<u8").tobytes(), _total(sums[i]), int(seq[i])) for i in range(k)]
+
+
+def ledger_log_payouts(ctx_or_none, entries, m0=0, m1=None, raw=False):
+    """What the round [m0, m1) of a published transfer log pays (`entries`: what
+    `WormholeLedger.entries()` returned; m1=None: to the end), as
+    `WormholeLedger.payouts_between` gives it: [(account 32 bytes, exact total,
+    first_seq)] over the credited entries of the range, in first_seq order.  An
+    auditor compares it with the list the settler published for the commitment
+    (root_k, n_k), m0 = n_{k-1}, m1 = n_k.  The flags are trusted: `audit_ledger_log`
+    is what checks them.  With a Context the range alone is uploaded and credited on
+    the device, with None on the host; needs no ledger."""
+    _, _, amt, acc, fl = _ledger_log_arrays(entries)
+    n = len(fl)
+    m0, m1 = int(m0), n if m1 is None else int(m1)
+
+    def call(cap, a, s, f, count):
+        rc = lib().qp_ledger_log_payouts_between(None if ctx_or_none is None else ctx_or_none.h, acc.ctypes.data,
+                                                 amt.ctypes.data, fl.ctypes.data, n, m0, m1, cap, a, s, f, count)
+        if rc:
+            raise QpError(rc, lib().qp_ledger_last_error(None).decode())
+    return _round_rows(call, m0, m1, raw)
+
+
 class WormholeLedger:
     def __init__(self, ctx_or_device, roots, padding=None, verifier=None, capacity=None):
         """roots: the accepted storage roots, 1 to 4096 digests of 4 canonical felts.
@@ -251,6 +291,51 @@ class WormholeLedger:
         if rc:
             raise QpError(rc, lib().qp_ledger_last_error(None).decode())
         self.h = h
+
+    @classmethod
+    def restore(cls, ctx_or_none, roots, entries, cast_count=None, padding=None, verifier=None, capacity=None,
+                root=None):
+        """Reopens a ledger from its published log (`entries`: what `entries()`
+        returned) and continues from it: the arguments of the constructor,
+        `cast_count` = the number the next transfer takes (None: the log's last
+        number + 1, 0 for an empty log), `capacity` (None: the default, or what the
+        log needs), `root` = the log's published root, checked if given.  The log is
+        audited first (canonical entries, increasing numbers, the credit rule, the
+        root); a log that fails raises ValueError with the reason
+        (LEDGER_AUDIT_STATUS_TEXT) and the witness.  The restored ledger has the
+        nullifier set, the account totals and the log of the ledger that published
+        it: a repeat of an old transfer is a double spend naming the original."""
+        nul, num, amt, acc, fl = _ledger_log_arrays(entries)
+        n = len(num)
+        roots = list(roots)
+        if not 1 <= len(roots) <= MAX_ROOTS:
+            raise ValueError(f"{len(roots)} accepted roots: a ledger needs 1 to {MAX_ROOTS}")
+        r = np.concatenate([_felts(x, 4, "a root") for x in roots])
+        pad = None if padding is None else _felts(padding, NPI, "padding")
+        capacity = max(DEFAULT_CAPACITY, n) if capacity is None else int(capacity)
+        if cast_count is None:
+            cast_count = int(num[-1]) + 1 if n else 0
+        expect = None if root is None else _felts(root, 4, "root")
+        self = cls.__new__(cls)
+        self.verifier = verifier
+        self.h = self._own_ctx = None
+        if ctx_or_none is None or isinstance(ctx_or_none, Context):
+            self.ctx = ctx_or_none
+        else:
+            self.ctx = self._own_ctx = Context(int(ctx_or_none))
+        h = ctypes.c_void_p()
+        rc = lib().qp_ledger_restore(None if self.ctx is None else self.ctx.h, r.ctypes.data, len(roots),
+                                     None if pad is None else pad.ctypes.data, capacity, nul.ctypes.data,
+                                     num.ctypes.data, amt.ctypes.data, acc.ctypes.data, fl.ctypes.data, n,
+                                     int(cast_count), None if expect is None else expect.ctypes.data, ctypes.byref(h))
+        if rc:
+            why = lib().qp_ledger_last_error(None).decode()
+            self.free()
+            if rc == 6:  # QP_ERR_FORMAT: the log fails its audit
+                raise ValueError(why)
+            raise QpError(rc, why)
+        self.h = h
+        return self
 
     @staticmethod
     def padding_of(aggregator):
@@ -417,6 +502,20 @@ class WormholeLedger:
         if raw:
             return acc, sums, seq
         return [(acc[i].astype("<u8").tobytes(), _total(sums[i]), int(seq[i])) for i in range(k)]
+
+    def payouts_between(self, m0, m1, raw=False):
+        """What the round of log entries [m0, m1) pays (0 <= m0 <= m1 <= admitted):
+        [(account 32 bytes, exact total, first_seq)] over the credited entries of
+        the range alone, in first_seq order; an account credited before m0 and again
+        inside appears with its in-range total and first_seq (raw=True: the arrays
+        accounts [k][4], limb sums [k][4], first_seq [k]).  A settler publishes
+        (root_k, n_k, payouts_between(n_{k-1}, n_k)) per commitment; the rounds add
+        up to `payouts()`.  The ledger is not changed."""
+        m0, m1 = int(m0), int(m1)
+
+        def call(cap, a, s, f, count):
+            self._check(lib().qp_ledger_payouts_between(self.h, m0, m1, cap, a, s, f, count))
+        return _round_rows(call, m0, m1, raw)
 
     def totals_for(self, accounts):
         """Per account (32 bytes or 4 felts) its exact total, or None if it was never credited."""

@@ -23,6 +23,15 @@ commitments, its arguments being arrays made beforehand; device beside host
 (--host-reps runs: the host path hashes three permutations per entry on one
 thread), results compared.
 
+Restore and payout rounds (`--only-restore` for these rows alone, key
+`restore_rounds`), on a log of N entries, a quarter of them double spends:
+`restore` with and without an expected root beside the only alternative there
+was, cast_public of the rebuilt public inputs into a fresh ledger plus
+commit_log (which needs each entry's storage root: a published log does not
+carry it); payouts_between of the last 256, the last 65536 and the whole log
+beside the cumulative payouts(); the log-only form of the last 65536.  The host
+path's root-expected restore runs on the first 2^16 entries (scaled).
+
 Last, with --parent-lib FILE (the parent commit's libqpgpu.so), the path this
 work must not disturb: the six cast_public rows, device and host path, on the
 parent's library and on this one, both loaded into this process through plain
@@ -33,7 +42,7 @@ every row; the figures are written first, then a miss fails the run.
 Writes one JSON object (default profiles/ledger_bench.json) stamped with the
 library hash (tools/libhash.py).  Needs an MI355X: without a device it fails.
 
-  python tools/ledger_bench.py [--log-n 20] [--reps 5] [--proofs 256] [--only-log] [--parent-lib FILE] [--out FILE]
+  python tools/ledger_bench.py [--log-n 20] [--reps 5] [--proofs 256] [--only-log] [--only-restore] [--parent-lib FILE] [--out FILE]
 """
 import argparse
 import json
@@ -266,6 +275,73 @@ def ab_cast_public(parent_path, this_path, n, reps):
             "all_medians_inside_parent_range": not misses}, misses
 
 
+def restore_rounds(qp, ctx, pis, reps, root_n=None):
+    """On one path, over the log the stream `pis` leaves (the publisher is a ledger of the same path):
+    `restore` with and without an expected root; the only way back to a live ledger before restore
+    existed: cast_public of the rebuilt public inputs into a fresh ledger, plus commit_log (it needs
+    each entry's storage root, which a published log does not carry: the stream's own are used);
+    payouts_between of the last 256, the last 65536 and the whole log beside the cumulative payouts();
+    and the log-only form of the last 65536.  Wall medians of `reps` runs after one warm-up.  root_n:
+    the root-expected restore (and the alternative, which commits) on the first root_n entries only,
+    for the host path, which hashes three permutations per entry on one thread."""
+    n_pis = len(pis)
+    led = qp.WormholeLedger(ctx, ROOTS, capacity=n_pis)
+    led.cast_public(pis, reserve=False, raw=True)
+    n = led.admitted
+    entries = led._entries_at(np.arange(n, dtype=np.uint64))  # the arrays the ABI takes, made beforehand
+    root_n = n if root_n is None else min(root_n, n)
+    root_at = led.root_at(root_n)
+    cast_count = led.cast_count
+    want = (led.payouts(raw=True), led.recount())
+    short = tuple(a[:root_n] for a in entries)
+    short_pis = pis[:root_n]  # every transfer of the stream is admitted, so entry i is transfer i
+    assert n == n_pis and (entries[0][:root_n] == short_pis[:, 0:4]).all()
+    t = {k: [] for k in ("restore", "restore_with_root", "recast_and_commit", "payouts_between_last_256",
+                         "payouts_between_last_65536", "payouts_between_whole", "payouts_cumulative",
+                         "log_payouts_last_65536")}
+
+    def timed(key, fn):
+        t0 = time.perf_counter()
+        out = fn()
+        t[key].append(time.perf_counter() - t0)
+        return out
+    last = None
+    for _ in range(reps + 1):
+        again = timed("restore", lambda: qp.WormholeLedger.restore(ctx, ROOTS, entries, cast_count=cast_count, capacity=n))
+        got = (again.payouts(raw=True), again.recount())
+        assert all((a == b).all() for a, b in zip(got[0], want[0])) and got[1] == want[1]
+        again.free()
+        again = timed("restore_with_root", lambda: qp.WormholeLedger.restore(ctx, ROOTS, short, capacity=root_n,
+                                                                              root=root_at))
+        assert again.commit_log() == (root_at, root_n)
+        again.free()
+
+        def recast():
+            fresh = qp.WormholeLedger(ctx, ROOTS, capacity=root_n)
+            fresh.cast_public(short_pis, reserve=False, raw=True)
+            return fresh, fresh.commit_log()
+        fresh, pair = timed("recast_and_commit", recast)
+        assert pair == (root_at, root_n)
+        fresh.free()
+        rows = {}
+        for key, m0 in (("payouts_between_last_256", n - 256), ("payouts_between_last_65536", n - 65536),
+                        ("payouts_between_whole", 0)):
+            rows[key] = timed(key, lambda: led.payouts_between(m0, n, raw=True))
+        # after the warm-up the ledger keeps its payee list, so these are the gathers alone; the first call's
+        # compaction of the whole log is full_log's `payouts` row
+        cumulative = timed("payouts_cumulative", lambda: led.payouts(raw=True))
+        assert all((a == b).all() for a, b in zip(rows["payouts_between_whole"], cumulative))
+        log_rows = timed("log_payouts_last_65536", lambda: qp.ledger_log_payouts(ctx, entries, n - 65536, n, raw=True))
+        assert all((a == b).all() for a, b in zip(log_rows, rows["payouts_between_last_65536"]))
+        last = ([x.tolist() for x in rows["payouts_between_last_256"]], len(rows["payouts_between_last_65536"][2]),
+                len(cumulative[2]), root_at)
+    led.free()
+    rec = {k: _stats(v[1:]) for k, v in t.items()}
+    rec.update({"entries": n, "root_entries": root_n, "accounts": last[2], "accounts_last_65536": last[1],
+                "accounts_last_256": len(last[0][2])})
+    return rec, last
+
+
 def real_proofs(qp, ctx, nproofs, reps):
     """`cast` of real Wormhole proofs on both paths beside `verify_batch` alone"""
     from qp_wormhole.prover import _verifier_only
@@ -308,6 +384,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ledger_bench.json"))
     ap.add_argument("--only-log", action="store_true",
                     help="only the log commitment's rows (and the A/B, if asked for), merged into an existing --out file")
+    ap.add_argument("--only-restore", action="store_true",
+                    help="only the restore and payout-round rows (and the A/B, if asked for), merged into an existing --out file")
     ap.add_argument("--parent-lib", help="the parent commit's libqpgpu.so: the cast_public rows on both libraries")
     a = ap.parse_args()
     import qp_wormhole as qp
@@ -316,19 +394,37 @@ def main():
     ctx = qp.Context(0)
     n = 1 << a.log_n
     out = {"library": lib_sha16(), "transfers": n, "accounts": ACCOUNTS, "reps": a.reps, "cast_public": []}
-    if a.only_log and os.path.exists(a.out):
+    if (a.only_log or a.only_restore) and os.path.exists(a.out):
         with open(a.out) as f:
             out = json.load(f)
-    pis = make_stream(np.random.default_rng(1), n + 256 + 65536, (n + 256 + 65536) // 4)
-    dev, dlast = log_commitment(qp, ctx, pis, n, a.reps)
-    host, hlast = log_commitment(qp, None, pis, n, a.host_reps)
-    out["log_commitment"] = {"library": lib_sha16(), "stream": "quarter_doubles", "device": dev, "host": host,
-                             "results_equal": dlast == hlast,
-                             "device_wall_over_host_wall": {k: dev[k]["median"] / host[k]["median"] for k in dev
-                                                            if isinstance(dev[k], dict)}}
-    print(json.dumps(out["log_commitment"]), flush=True)
-    assert dlast == hlast
-    for name, doubles in (() if a.only_log else (("distinct", 0), ("quarter_doubles", n // 4))):
+    if not a.only_log:
+        pis = make_stream(np.random.default_rng(1), n, n // 4)
+        dev, dlast = restore_rounds(qp, ctx, pis, a.reps)
+        host, hlast = restore_rounds(qp, None, pis, a.reps, root_n=1 << 16)
+        out["restore_rounds"] = {
+            "library": lib_sha16(), "stream": "quarter_doubles", "device": dev, "host": host,
+            "what": "wall of one call (perf_counter), medians of reps runs after one warm-up; the log's arrays are "
+                    "made before the timed calls; host.restore_with_root and host.recast_and_commit are scaled: the "
+                    "first host.root_entries entries only; recast_and_commit needs each entry's storage root, which "
+                    "a published log does not carry; payouts_cumulative is the gathers alone (the payee list is "
+                    "kept from the warm-up; full_log.payouts is a first call)",
+            "results_equal": dlast[:3] == hlast[:3],
+            "device_wall_over_host_wall": {k: dev[k]["median"] / host[k]["median"] for k in dev
+                                           if isinstance(dev[k], dict) and k not in ("restore_with_root",
+                                                                                     "recast_and_commit")}}
+        print(json.dumps(out["restore_rounds"]), flush=True)
+        assert dlast[:3] == hlast[:3]
+    if not a.only_restore:
+        pis = make_stream(np.random.default_rng(1), n + 256 + 65536, (n + 256 + 65536) // 4)
+        dev, dlast = log_commitment(qp, ctx, pis, n, a.reps)
+        host, hlast = log_commitment(qp, None, pis, n, a.host_reps)
+        out["log_commitment"] = {"library": lib_sha16(), "stream": "quarter_doubles", "device": dev, "host": host,
+                                 "results_equal": dlast == hlast,
+                                 "device_wall_over_host_wall": {k: dev[k]["median"] / host[k]["median"] for k in dev
+                                                                if isinstance(dev[k], dict)}}
+        print(json.dumps(out["log_commitment"]), flush=True)
+        assert dlast == hlast
+    for name, doubles in (() if a.only_log or a.only_restore else (("distinct", 0), ("quarter_doubles", n // 4))):
         pis = make_stream(np.random.default_rng(1), n, doubles)
         for batch in (256, 65536, n):
             dev, dlast = cast_stream(qp.WormholeLedger, ctx, pis, batch, a.reps)
@@ -344,7 +440,7 @@ def main():
             out["full_log"] = {"device": dev, "host": host, "results_equal": dlast == hlast}
             print(json.dumps(out["full_log"]), flush=True)
             assert dlast == hlast
-    if a.proofs and not a.only_log:
+    if a.proofs and not a.only_log and not a.only_restore:
         out["real_proofs"] = real_proofs(qp, ctx, a.proofs, a.reps)
         print(json.dumps(out["real_proofs"]), flush=True)
     misses = []
