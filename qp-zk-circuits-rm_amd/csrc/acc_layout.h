@@ -2,14 +2,15 @@
 // that the voter registry (eligibility) and the ballot box (its log) both keep
 // (acc_kernels.h has the convention): the level table, the layout reserved for
 // a capacity, the dirty ranges of an append, the shape rule of a path, the tree
-// in host memory, and the sorted batch of a registry's replace.  Plain C++ (no
-// HIP, no hash): tools/acc_layout_check.cpp runs it under the sanitizers.
+// in host memory, the walk that checks a receipt, and the sorted batch of a
+// registry's replace.  Plain C++ (no HIP, no hash): tools/acc_layout_check.cpp runs it under the sanitizers.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
 #include <numeric>
 #include <vector>
+#include "slot_table.h"
 
 namespace qpk {
 
@@ -155,6 +156,39 @@ struct HostTree {
     }
   }
 };
+
+// qp_receipt_status (qpgpu.h)
+enum : int { RECEIPT_OK = 0, RECEIPT_SHAPE = 1, RECEIPT_ROOT = 2, RECEIPT_NON_CANONICAL = 3, RECEIPT_NULL = 4 };
+
+// The receipt of leaf seq (its digest `leaf`) against a commitment (root, n), siblings
+// [ACC_PATH_SLOTS][4] in HostTree::path's layout: RECEIPT_OK or the first reason found, in this
+// order: a felt >= p in the root or the siblings, the shape, the root.  The shape comes from (seq, n),
+// never from the receipt: (depth, side bits) is the route from the root to one node of the tree,
+// path_levels yields the routes of level-0 nodes only, and a receipt that says otherwise is
+// rejected, so a node cannot be offered as a leaf.  hash(left, right, out): the node hash.
+template <class NodeHash>
+int receipt_walk(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t leaf[4], const uint64_t *siblings,
+                 uint32_t path_bits, uint32_t depth, NodeHash hash) {
+  if (!qst::canonical(root, 4) || !qst::canonical(siblings, ACC_PATH_SLOTS * 4)) return RECEIPT_NON_CANONICAL;
+  if (!n || n > ACC_MAX_LEAVES || seq >= n) return RECEIPT_SHAPE;
+  const uint32_t m = path_levels(seq, n);
+  uint32_t d = 0, bits = 0;
+  for (uint32_t l = 0; l < 32; l++)
+    if (m >> l & 1) bits |= (uint32_t)((seq >> l) & 1) << d++;
+  if (d != depth || bits != path_bits) return RECEIPT_SHAPE;
+  for (uint32_t i = d * 4; i < ACC_PATH_SLOTS * 4; i++)
+    if (siblings[i]) return RECEIPT_SHAPE;  // the slots above the depth hold the zero digest
+  uint64_t cur[4];
+  memcpy(cur, leaf, 32);
+  for (uint32_t i = 0; i < d; i++) {
+    const uint64_t *s = siblings + i * 4;
+    if (bits >> i & 1)
+      hash(s, cur, cur);
+    else
+      hash(cur, s, cur);
+  }
+  return memcmp(cur, root, 32) ? RECEIPT_ROOT : RECEIPT_OK;
+}
 
 // the order that sorts a replace batch by leaf index: order[b] = position in
 // idx[] of the b-th smallest index.  false when an index is >= n (*bad = its

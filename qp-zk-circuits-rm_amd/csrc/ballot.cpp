@@ -565,7 +565,7 @@ int qp_ballot_box_find(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k,
         return QP_ERR_ARG;
       }
   if (!b->ctx) {
-    for (uint32_t i = 0; i < k; i++) seq_out[i] = qb::find(b->host, nullifiers + (size_t)i * 4);
+    for (uint32_t i = 0; i < k; i++) seq_out[i] = b->host.find(nullifiers + (size_t)i * 4);
     return QP_OK;
   }
   try {
@@ -611,7 +611,7 @@ int qp_ballot_box_receipts(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, u
   if (!k) return QP_OK;
   if (b->ctx) return device_step(b, receipts_device(b, seqs, k, siblings, path_bits, depth, leaves));
   for (uint32_t i = 0; i < k; i++)
-    b->hlog.path(seqs[i], siblings + (size_t)i * qb::PATH_SLOTS * 4, path_bits + i, depth + i,
+    b->hlog.path(seqs[i], siblings + (size_t)i * qb::ACC_PATH_SLOTS * 4, path_bits + i, depth + i,
                  leaves ? leaves + (size_t)i * 4 : nullptr);
   return QP_OK;
 }

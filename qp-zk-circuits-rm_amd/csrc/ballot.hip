@@ -3,63 +3,14 @@
 // one or a few dependent slot atomics and 32-byte key reads; no arithmetic to
 // speak of.  The log commitment's leaf kernel is the exception: VALU-bound, one
 // permutation per lane (merkle_node.h), like registry.hip's.
-#include "ballot_device.h"
 #include "ballot_kernels.h"
 #include "merkle_node.h"
+#include "slot_table_device.h"
 
 namespace qpk {
 
 namespace {
-// The probe of log entry seq (the log holds `limit` entries): returns the slot
-// where it stays, BALLOT_NO_SLOT if S slots were tried (see fact 3 below).
-//
-// Why the table is correct:
-// 1. A slot's nullifier never changes once the slot is claimed: a claimed slot
-//    holds a seq, and the only later write to it is an atomicMin by a lane
-//    whose own nullifier equals log[seq]'s, so the word only ever moves to
-//    another entry with the same nullifier.  A lane passes a slot only if the
-//    nullifier there differs from its own, which therefore stays true.  So all
-//    entries with one nullifier probe the same chain and stop at the same slot
-//    whatever the interleaving, and the slot ends at the minimum of their
-//    seqs: the lowest ballot number, since seq is monotone in the number.
-// 2. The keys a lane compares against are in the log, which the host uploaded
-//    before this launch (entries of this batch included).  A lane reads nothing
-//    that a lane of the same launch wrote, except the slot word, and that only
-//    through agent-scope atomics (load, compare-and-swap, min), which are
-//    performed at the device's coherence point and not in an XCD's own L2.
-//    That is why the key is not stored in the slot: a plain load does not see
-//    another XCD's plain store of the same launch.  No fences, no flags, no
-//    spin: no lane waits on another lane.
-// 3. The host keeps count + k <= C <= S / 2 before it launches, so an empty
-//    slot exists and the loop ends at it at the latest.  The loop is bounded by
-//    S all the same; running out cannot be reached and is reported through the
-//    error word, after which the box refuses further casts.
-// 4. The lookup (k_ballot_find) takes no atomics and writes no slot.  It runs
-//    on the box's stream in a launch of its own after every insert, resolve
-//    and rebuild has completed, and nothing runs beside it: the slot words and
-//    the log it reads were final before it started, and a kernel boundary on
-//    one stream makes them visible to plain loads on every XCD.  Nothing is
-//    ever removed, so a chain has no gap and an empty slot ends it.
-__device__ __forceinline__ uint32_t ballot_probe(const BallotDev &d, uint32_t seq, uint32_t limit) {
-  const uint64_t *key = d.nullifier + (uint64_t)seq * 4;
-  const uint64_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3];
-  uint64_t at = k0 & d.mask;
-  for (uint64_t tried = 0; tried <= d.mask; tried++, at = (at + 1) & d.mask) {
-    uint32_t cur = __hip_atomic_load(d.slot + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == BALLOT_EMPTY) {
-      cur = atomicCAS(d.slot + at, BALLOT_EMPTY, seq);
-      if (cur == BALLOT_EMPTY) return (uint32_t)at;  // claimed
-    }
-    if (cur == seq) return (uint32_t)at;
-    if (cur >= limit) break;  // not a log entry: cannot be reached (only seqs below the limit are ever stored)
-    const uint64_t *o = d.nullifier + (uint64_t)cur * 4;  // cur < limit = count + k <= C, written before the launch
-    if (o[0] == k0 && o[1] == k1 && o[2] == k2 && o[3] == k3) {
-      atomicMin(d.slot + at, seq);
-      return (uint32_t)at;
-    }
-  }
-  return BALLOT_NO_SLOT;
-}
+__device__ __forceinline__ SlotTable nullifier_table(const BallotDev &d) { return {d.nullifier, d.slot, d.mask}; }
 }  // namespace
 
 // one lane per admitted ballot of the batch
@@ -67,9 +18,10 @@ __global__ void __launch_bounds__(256) k_ballot_insert(BallotDev d, uint32_t fir
                                                        uint32_t *__restrict__ stay, uint32_t *__restrict__ err) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
-  const uint32_t at = ballot_probe(d, first_seq + i, first_seq + k);
+  bool claimed;
+  const uint32_t at = table_probe(nullifier_table(d), first_seq + i, first_seq + k, &claimed);
   stay[i] = at;
-  if (at == BALLOT_NO_SLOT) atomicOr(err, 1u);
+  if (at == NO_SLOT) atomicOr(err, 1u);
 }
 
 // a launch after the insert: every slot word is final.  One lane per admitted
@@ -81,7 +33,7 @@ __global__ void __launch_bounds__(256) k_ballot_resolve(BallotDev d, uint32_t fi
   bool yes = false, no = false;
   if (i < k) {
     const uint32_t seq = first_seq + i, at = stay[i];
-    const uint32_t owner = at == BALLOT_NO_SLOT ? BALLOT_EMPTY : d.slot[at];
+    const uint32_t owner = at == NO_SLOT ? SLOT_EMPTY : d.slot[at];
     if (owner > seq) {  // an entry's slot holds the minimum of its nullifier's seqs: defensive, as the probe's bound
       atomicOr(&ctr->err, 2u);
       first_out[i] = ~0ull;
@@ -106,7 +58,8 @@ __global__ void __launch_bounds__(256) k_ballot_resolve(BallotDev d, uint32_t fi
 __global__ void __launch_bounds__(256) k_ballot_rebuild(BallotDev d, uint32_t count, uint32_t *__restrict__ err) {
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   if (seq >= count || !(d.flags[seq] & BALLOT_COUNTED)) return;
-  if (ballot_probe(d, seq, count) == BALLOT_NO_SLOT) atomicOr(err, 1u);
+  bool claimed;
+  if (table_probe(nullifier_table(d), seq, count, &claimed) == NO_SLOT) atomicOr(err, 1u);
 }
 
 // the audit: yes, no, counted and admitted from the flags alone
@@ -138,7 +91,7 @@ __global__ void __launch_bounds__(256) k_ballot_leaves(BallotDev d, uint32_t fir
   s[4] = d.number[seq];
   s[5] = d.flags[seq];
   s[6] = s[7] = 0;
-  if (s[4] >= BALLOT_P) {
+  if (s[4] >= qst::P) {
     atomicOr(err, 4u);
     return;
   }
@@ -157,24 +110,12 @@ __global__ void __launch_bounds__(256) k_ballot_find(BallotDev d, uint32_t count
                                                      uint32_t *__restrict__ err) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
-  const uint64_t *key = q + (uint64_t)i * 4;
-  const uint64_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3];
-  uint32_t found = BALLOT_EMPTY;
-  uint64_t at = k0 & d.mask;
-  for (uint64_t tried = 0; tried <= d.mask; tried++, at = (at + 1) & d.mask) {
-    const uint32_t cur = d.slot[at];
-    if (cur == BALLOT_EMPTY) break;
-    if (cur >= count) {
-      atomicOr(err, 8u);
-      break;
-    }
-    const uint64_t *o = d.nullifier + (uint64_t)cur * 4;
-    if (o[0] == k0 && o[1] == k1 && o[2] == k2 && o[3] == k3) {
-      found = cur;
-      break;
-    }
-  }
-  seq_out[i] = found;
+  uint64_t key[4];
+  load_key(q + (uint64_t)i * 4, key);
+  bool bad = false;
+  const uint32_t at = table_lookup(nullifier_table(d), key, count, &bad);
+  if (bad) atomicOr(err, 8u);
+  seq_out[i] = at == NO_SLOT ? SLOT_EMPTY : d.slot[at];
 }
 
 // log entries seq[i] < count (the caller checks) into dense arrays: one lane per entry

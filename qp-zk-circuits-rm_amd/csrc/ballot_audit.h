@@ -164,7 +164,7 @@ inline bool audit_facts_host(const uint64_t *nullifiers, const uint64_t *numbers
   box.number.assign(numbers, numbers + n);
   box.flags.assign(flags, flags + n);
   for (uint64_t seq = 0; seq < n; seq++) {
-    const uint32_t owner = box.slot[box.probe((uint32_t)seq)];
+    const uint32_t owner = box.slot[box.table().probe((uint32_t)seq)];
     const bool counted = flags[seq] & FLAG_COUNTED;
     if (counted != (owner == seq) && f.count_rule == AUDIT_NONE) {
       f.count_rule = seq;

@@ -5,30 +5,20 @@
 // between the two is ballot.hip's own k_ballot_insert over the whole log; the
 // root is k_ballot_leaves and the accumulator tree's append, as commit_log.
 //
-// Why the whole-log insert decides the count rule (facts 1-3 of ballot.hip's
-// probe): the host uploaded all n entries before the launch (fact 2), the
-// table is fresh and holds S >= 2 n slots (fact 3), and whatever the
+// Why the whole-log insert decides the count rule (facts 1-3 of table_probe,
+// slot_table_device.h): the host uploaded all n entries before the launch
+// (fact 2), the table is fresh and holds S >= 2 n slots (fact 3), and whatever the
 // scheduling the slot of a nullifier ends at the minimum seq of the entries
 // that carry it (fact 1).  k_audit_resolve is a launch of its own after the
 // insert on the same stream, so every slot word is final and visible to plain
 // loads: owner == seq says "no earlier entry has this nullifier".
 //
-// The lowest offender: seqs are consecutive across a wave, so the lowest
-// offending lane of a wave's ballot holds the wave's lowest seq and alone
-// sends it, one atomicMin per wave and reason at the most; the minimum over
-// the waves does not depend on the order they arrive in.
-#include "ballot_device.h"
+// Seqs are consecutive across a wave, so each reason's lowest offender goes out
+// by lowest_offender's one atomicMin per wave.
 #include "ballot_kernels.h"
+#include "slot_table_device.h"
 
 namespace qpk {
-
-namespace {
-// true in the lowest lane of the wave whose `bad` is set; every lane of the wave calls it
-__device__ __forceinline__ bool lowest_offender(bool bad) {
-  const uint64_t m = __ballot(bad);
-  return bad && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)m) - 1);
-}
-}  // namespace
 
 // one lane per entry.  The neighbour number[seq - 1] is a plain load of
 // uploaded data, across a block edge as inside one.
@@ -38,7 +28,7 @@ __global__ void __launch_bounds__(256) k_audit_screen(BallotDev d, uint32_t n, B
   if (seq < n) {
     const uint64_t *key = d.nullifier + (uint64_t)seq * 4;
     const uint64_t num = d.number[seq];
-    bad = key[0] >= BALLOT_P || key[1] >= BALLOT_P || key[2] >= BALLOT_P || key[3] >= BALLOT_P || num >= BALLOT_P ||
+    bad = key[0] >= qst::P || key[1] >= qst::P || key[2] >= qst::P || key[3] >= qst::P || num >= qst::P ||
           d.flags[seq] > (BALLOT_VOTE | BALLOT_COUNTED);
     unordered = seq && num <= d.number[seq - 1];
   }
@@ -53,10 +43,10 @@ __global__ void __launch_bounds__(256) k_audit_resolve(BallotDev d, uint32_t n, 
                                                        BallotAuditDev *rep) {
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   bool yes = false, no = false, counted = false, broken = false;
-  uint32_t owner = BALLOT_EMPTY;
+  uint32_t owner = SLOT_EMPTY;
   if (seq < n) {
     const uint32_t at = stay[seq];
-    if (at != BALLOT_NO_SLOT) owner = d.slot[at];
+    if (at != NO_SLOT) owner = d.slot[at];
     const uint8_t f = d.flags[seq];
     counted = f & BALLOT_COUNTED;
     yes = counted && (f & BALLOT_VOTE);

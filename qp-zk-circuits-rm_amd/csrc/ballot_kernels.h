@@ -5,11 +5,9 @@
 // The log (dense, indexed by admission sequence seq, written by the host's
 // upload before any launch that reads it):
 //   nullifier[C][4]   number[C]   flags[C] (bit 0 the vote, bit 1 counted)
-// The table: S = the power of two >= 2 C slots of uint32_t, a seq or
-// 0xFFFFFFFF (empty); open addressing, linear probing, wrapping.
-//   HOME SLOT = nullifier[0] & (S - 1)
-// (ballot_table.h states the same rule for the host path; the tests craft
-// colliding nullifiers from it.)
+// The table: a slot table (slot_table.h has the layout and the home-slot rule,
+// slot_table_device.h the probes) of S = the power of two >= 2 C slots, keyed
+// by the nullifier.
 //
 // The log commitment (ballot_log.h has the definitions): the log tree is an
 // accumulator tree (acc_tree.h) laid out for the box's capacity.
@@ -28,6 +26,8 @@ struct BallotDev {
   uint32_t *slot;       // [mask + 1]
   uint64_t mask;        // S - 1
 };
+
+constexpr uint8_t BALLOT_VOTE = 1, BALLOT_COUNTED = 2;  // the bits of a log entry's flags byte
 
 // the box's device counters: the running tally and the defensive error word
 struct BallotCounters {

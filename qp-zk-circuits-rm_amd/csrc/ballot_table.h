@@ -7,25 +7,20 @@
 // A voting proof's 13 public inputs (voting/src/lib.rs:55-62):
 //   proposal[0:4] root[4:8] vote[8] nullifier[9:13]
 //
-// The table (both paths): open addressing, linear probing, S = table_slots(C)
-// slots for a capacity of C admitted ballots, S the power of two >= 2 C.  A
-// slot is a uint32_t: the admission sequence number `seq` of a log entry, or
-// EMPTY.  The key is not in the slot: it is log.nullifier[seq].
-//   HOME SLOT = nullifier[0] & (S - 1)
-// and the probe goes to slot + 1, wrapping.  A nullifier is a Poseidon output,
-// so a voter cannot choose theirs; tests craft colliding ones from this rule.
+// The table (both paths): a slot table (slot_table.h) for a capacity of C
+// admitted ballots; seq is a ballot's admission sequence number, the key
+// log.nullifier[seq].
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <vector>
+#include "slot_table.h"
 
 namespace qb {
 
-constexpr uint64_t P = 0xFFFFFFFF00000001ull;
+using qst::canonical, qst::EMPTY, qst::MAX_CAPACITY, qst::NOT_FOUND, qst::P, qst::SlotTable, qst::table_slots;
 constexpr uint32_t NPI = 13, PI_ROOT = 4, PI_VOTE = 8, PI_NULLIFIER = 9;
 constexpr uint32_t MAX_ROOTS = 64;
-constexpr uint64_t MAX_CAPACITY = 1ull << 31;
-constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr uint8_t FLAG_VOTE = 1, FLAG_COUNTED = 2;
 
 // qp_ballot_status (qpgpu.h), in the order of the checks
@@ -37,18 +32,6 @@ struct Result {
   uint32_t status, verify_status;
   uint64_t number, first;
 };
-
-inline uint64_t table_slots(uint64_t capacity) {
-  uint64_t s = 2;
-  while (s < 2 * capacity) s <<= 1;
-  return s;
-}
-inline uint64_t home_slot(const uint64_t nul[4], uint64_t mask) { return nul[0] & mask; }
-inline bool canonical(const uint64_t *v, uint32_t n) {
-  for (uint32_t i = 0; i < n; i++)
-    if (v[i] >= P) return false;
-  return true;
-}
 
 // what a box accepts: one proposal, the published roots [nroots][4]
 struct Screen {
@@ -116,21 +99,15 @@ struct HostBox {
     capacity = cap;
     mask = slot.size() - 1;
   }
-  // the slot of log entry seq's nullifier: its own (claimed now) or an equal earlier entry's
-  uint64_t probe(uint32_t seq) {
-    const uint64_t *k = &nullifier[(size_t)seq * 4];
-    for (uint64_t at = home_slot(k, mask);; at = (at + 1) & mask) {  // count <= C <= S / 2: an empty slot exists
-      if (slot[at] == EMPTY) slot[at] = seq;
-      if (slot[at] == seq || !memcmp(&nullifier[(size_t)slot[at] * 4], k, 32)) return at;
-    }
-  }
+  // the table over the log as it stands; a const box's is for lookup, which writes no slot
+  SlotTable table() const { return {const_cast<uint32_t *>(slot.data()), mask, nullifier.data()}; }
   // one admitted ballot (the caller keeps count() < capacity): true if counted; *first as qp_ballot_result's
   bool admit(const uint64_t nul[4], uint64_t num, uint8_t vote_flag, uint64_t *first) {
     const uint32_t seq = (uint32_t)count();
     nullifier.insert(nullifier.end(), nul, nul + 4);
     number.push_back(num);
     flags.push_back(vote_flag);
-    const uint32_t owner = slot[probe(seq)];
+    const uint32_t owner = slot[table().probe(seq)];
     *first = number[owner];
     if (owner != seq) return false;
     flags[seq] |= FLAG_COUNTED;
@@ -151,7 +128,12 @@ struct HostBox {
     capacity = new_capacity;
     mask = slot.size() - 1;
     for (uint64_t seq = 0; seq < count(); seq++)
-      if (flags[seq] & FLAG_COUNTED) probe((uint32_t)seq);
+      if (flags[seq] & FLAG_COUNTED) table().probe((uint32_t)seq);
+  }
+  // the log index of the counted entry with nullifier q, NOT_FOUND if none
+  uint64_t find(const uint64_t q[4]) const {
+    const uint32_t seq = table().lookup(q);
+    return seq == EMPTY ? NOT_FOUND : seq;
   }
   // yes, no, counted, admitted from the log's flags alone
   void recount(uint64_t out[4]) const {

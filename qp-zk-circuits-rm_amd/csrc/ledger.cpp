@@ -941,7 +941,7 @@ int qp_ledger_receipts(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t 
     return device_step(l, l->log.paths({l->err}, l->ctx->stream, seqs, k, siblings, path_bits, depth, leaves));
   }
   for (uint32_t i = 0; i < k; i++)
-    l->hlog.path(seqs[i], siblings + (size_t)i * ql::PATH_SLOTS * 4, path_bits + i, depth + i,
+    l->hlog.path(seqs[i], siblings + (size_t)i * ql::ACC_PATH_SLOTS * 4, path_bits + i, depth + i,
                  leaves ? leaves + (size_t)i * 4 : nullptr);
   return QP_OK;
 }

@@ -10,110 +10,19 @@
 // compaction over a table of the audit's own; a restore runs the audit's screen,
 // insert and resolve over the new ledger's tables; a payout round credits a
 // range of the log into a scratch account table and reuses the same compaction.
-#include "ballot_device.h"
 #include "ledger_kernels.h"
 #include "ledger_rounds.h"
 #include "ledger_table.h"
 #include "poseidon_dev.h"
+#include "slot_table_device.h"
 
 namespace qpk {
 
 namespace {
-constexpr uint32_t LEDGER_EMPTY = 0xFFFFFFFFu;    // a slot that holds no seq
-constexpr uint32_t LEDGER_NO_SLOT = 0xFFFFFFFFu;  // stay[] / astay[] of a lane whose probe ran out (defensive)
 constexpr uint8_t LEDGER_CREDITED = ql::FLAG_CREDITED;
-
-// one table: slot words over keys[seq][4] that live in the log
-struct SlotTable {
-  const uint64_t *keys;
-  uint32_t *slot;
-  uint64_t mask;
-};
-
-__device__ __forceinline__ void load_key(const uint64_t *p, uint64_t k[4]) {
-  const ulonglong2 a = reinterpret_cast<const ulonglong2 *>(p)[0], b = reinterpret_cast<const ulonglong2 *>(p)[1];
-  k[0] = a.x, k[1] = a.y, k[2] = b.x, k[3] = b.y;
-}
-
-// The probe of log entry seq's key (only seqs below `limit` are ever stored): returns the slot
-// where it stays, LEDGER_NO_SLOT if S slots were tried; *claimed = this lane took an empty slot.
-// It is the ballot box's probe (ballot.hip) over either table, and that file's facts 1-4 carry over
-// word for word with "nullifier" read as "key":
-// 1. A claimed slot's key never changes: the only later write is an atomicMin by a lane whose own
-//    key equals the slot entry's, so all entries of one key stop at one slot whatever the
-//    interleaving, and the word ends at the minimum of their seqs.  seq is monotone in the
-//    transfer number (the pack is stable), so that is the lowest number.
-// 2. The keys compared against were written by k_ledger_pack, a launch before this one; of what a
-//    lane of the same launch writes only the slot word is read, and only through agent-scope
-//    atomics.  No fences, no flags, no spinning.
-// 3. count + k <= C <= S / 2 (the host checks before it launches), so an empty slot ends the loop;
-//    it is bounded by S all the same, and running out sets the error word.
-// 4. The lookups take no atomics and run in launches of their own after everything that writes.
-__device__ __forceinline__ uint32_t table_probe(const SlotTable &t, uint32_t seq, uint32_t limit, bool *claimed) {
-  uint64_t k[4];
-  load_key(t.keys + (uint64_t)seq * 4, k);
-  *claimed = false;
-  uint64_t at = k[0] & t.mask;
-  for (uint64_t tried = 0; tried <= t.mask; tried++, at = (at + 1) & t.mask) {
-    uint32_t cur = __hip_atomic_load(t.slot + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == LEDGER_EMPTY) {
-      cur = atomicCAS(t.slot + at, LEDGER_EMPTY, seq);
-      if (cur == LEDGER_EMPTY) {
-        *claimed = true;
-        return (uint32_t)at;
-      }
-    }
-    if (cur == seq) return (uint32_t)at;
-    if (cur >= limit) break;  // not a log entry: cannot be reached
-    uint64_t o[4];
-    load_key(t.keys + (uint64_t)cur * 4, o);  // cur < limit <= C, written before the launch
-    if (ql::key_equal(o, k)) {
-      atomicMin(t.slot + at, seq);
-      return (uint32_t)at;
-    }
-  }
-  return LEDGER_NO_SLOT;
-}
-
-// the read-only probe (fact 4) of key k in a table whose log holds `count` entries: the slot that
-// holds an entry with that key, or LEDGER_NO_SLOT; a slot word at or beyond count sets *bad
-__device__ __forceinline__ uint32_t table_lookup(const SlotTable &t, const uint64_t k[4], uint32_t count, bool *bad) {
-  uint64_t at = k[0] & t.mask;
-  for (uint64_t tried = 0; tried <= t.mask; tried++, at = (at + 1) & t.mask) {
-    const uint32_t cur = t.slot[at];
-    if (cur == LEDGER_EMPTY) break;
-    if (cur >= count) {
-      *bad = true;
-      break;
-    }
-    uint64_t o[4];
-    load_key(t.keys + (uint64_t)cur * 4, o);
-    if (ql::key_equal(o, k)) return (uint32_t)at;
-  }
-  return LEDGER_NO_SLOT;
-}
 
 __device__ __forceinline__ SlotTable nullifier_table(const LedgerDev &d) { return {d.nullifier, d.nslot, d.mask}; }
 __device__ __forceinline__ SlotTable account_table(const LedgerDev &d) { return {d.account, d.aslot, d.mask}; }
-
-// the lane's rank among the block's lanes with pred, in lane order; *total = how many there are.
-// Every lane of the block calls it, once per kernel.
-__device__ __forceinline__ uint32_t block_rank(bool pred, uint32_t *total) {
-  __shared__ uint32_t wave_n[4];
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(pred);
-  if (lane == 0) wave_n[wave] = __popcll(b);
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4; w++) {
-    const uint32_t n = wave_n[w];
-    all += n;
-    before += w < wave ? n : 0;
-  }
-  *total = all;
-  return before + __popcll(b & ((1ull << lane) - 1));
-}
 
 // a credited entry into the account table, its limbs onto the account's sums.  The sums are indexed
 // by the slot the key stays at, which fact 1 fixes for the key whatever the interleaving; integer
@@ -121,7 +30,7 @@ __device__ __forceinline__ uint32_t block_rank(bool pred, uint32_t *total) {
 __device__ __forceinline__ bool credit_entry(const LedgerDev &d, uint32_t seq, uint32_t limit, bool *claimed) {
   const uint32_t at = table_probe(account_table(d), seq, limit, claimed);
   d.astay[seq] = at;
-  if (at == LEDGER_NO_SLOT) return false;
+  if (at == NO_SLOT) return false;
   const uint4 a = reinterpret_cast<const uint4 *>(d.amount)[seq];
   unsigned long long *s = d.sum + (uint64_t)at * 4;
   atomicAdd(s + 0, (unsigned long long)a.x);
@@ -134,7 +43,7 @@ __device__ __forceinline__ bool credit_entry(const LedgerDev &d, uint32_t seq, u
 __device__ __forceinline__ bool owns_account(const LedgerDev &d, uint32_t seq) {
   if (!(d.flags[seq] & LEDGER_CREDITED)) return false;
   const uint32_t at = d.astay[seq];
-  return at != LEDGER_NO_SLOT && d.aslot[at] == seq;
+  return at != NO_SLOT && d.aslot[at] == seq;
 }
 }  // namespace
 
@@ -209,7 +118,7 @@ __global__ void __launch_bounds__(256) k_ledger_pack(LedgerDev d, const uint64_t
   reinterpret_cast<uint4 *>(d.amount)[seq] = make_uint4((uint32_t)hi.x, (uint32_t)hi.y, (uint32_t)lo.x, (uint32_t)lo.y);
   d.number[seq] = res[i].number;
   d.flags[seq] = 0;
-  d.astay[seq] = LEDGER_NO_SLOT;
+  d.astay[seq] = NO_SLOT;
   pos[j] = i;
 }
 
@@ -221,7 +130,7 @@ __global__ void __launch_bounds__(256) k_ledger_insert(LedgerDev d, uint32_t fir
   bool claimed;
   const uint32_t at = table_probe(nullifier_table(d), first_seq + j, first_seq + k, &claimed);
   stay[j] = at;
-  if (at == LEDGER_NO_SLOT) atomicOr(err, 1u);
+  if (at == NO_SLOT) atomicOr(err, 1u);
 }
 
 // a launch after the insert: every nullifier slot word is final.  One lane per admitted transfer of
@@ -234,7 +143,7 @@ __global__ void __launch_bounds__(256) k_ledger_resolve(LedgerDev d, uint32_t fi
   bool credited = false, claimed = false;
   if (j < k) {
     const uint32_t seq = first_seq + j, at = stay[j];
-    const uint32_t owner = at == LEDGER_NO_SLOT ? LEDGER_EMPTY : d.nslot[at];
+    const uint32_t owner = at == NO_SLOT ? SLOT_EMPTY : d.nslot[at];
     LedgerResult *r = res + pos[j];
     if (owner > seq) {  // a slot holds the minimum of its nullifier's seqs: defensive, as the probe's bound
       atomicOr(&ctr->err, 2u);
@@ -259,7 +168,7 @@ __global__ void __launch_bounds__(256) k_ledger_rebuild(LedgerDev d, uint32_t co
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   if (seq >= count || !(d.flags[seq] & LEDGER_CREDITED)) return;
   bool claimed;
-  if (table_probe(nullifier_table(d), seq, count, &claimed) == LEDGER_NO_SLOT) atomicOr(err, 1u);
+  if (table_probe(nullifier_table(d), seq, count, &claimed) == NO_SLOT) atomicOr(err, 1u);
   if (!credit_entry(d, seq, count, &claimed)) atomicOr(err, 4u);
 }
 
@@ -274,7 +183,7 @@ __global__ void __launch_bounds__(256) k_ledger_find(LedgerDev d, uint32_t count
   bool bad = false;
   const uint32_t at = table_lookup(nullifier_table(d), key, count, &bad);
   if (bad) atomicOr(err, 8u);
-  seq_out[i] = at == LEDGER_NO_SLOT ? LEDGER_EMPTY : d.nslot[at];
+  seq_out[i] = at == NO_SLOT ? SLOT_EMPTY : d.nslot[at];
 }
 
 // one lane per queried account q[i][4]
@@ -288,9 +197,9 @@ __global__ void __launch_bounds__(256) k_ledger_totals(LedgerDev d, uint32_t cou
   bool bad = false;
   const uint32_t at = table_lookup(account_table(d), key, count, &bad);
   if (bad) atomicOr(err, 8u);
-  found[i] = at != LEDGER_NO_SLOT;
+  found[i] = at != NO_SLOT;
 #pragma unroll
-  for (int j = 0; j < 4; j++) sums[(uint64_t)i * 4 + j] = at == LEDGER_NO_SLOT ? 0 : d.sum[(uint64_t)at * 4 + j];
+  for (int j = 0; j < 4; j++) sums[(uint64_t)i * 4 + j] = at == NO_SLOT ? 0 : d.sum[(uint64_t)at * 4 + j];
 }
 
 // the payouts: the entries that own their account slot, compacted in log order (= the order of each
@@ -409,17 +318,7 @@ __global__ void __launch_bounds__(256) k_ledger_gather(LedgerDev d, const uint64
 }
 
 // ---- the audit of a published log (ledger_audit.h has the rules).  Seqs are consecutive across a
-// wave, so the lowest offending lane of a wave's ballot holds the wave's lowest seq and alone sends
-// it: one atomicMin per wave and reason at the most, and the minimum does not depend on the order the
-// waves arrive in.
-
-namespace {
-// true in the lowest lane of the wave whose `bad` is set; every lane of the wave calls it
-__device__ __forceinline__ bool lowest_offender(bool bad) {
-  const uint64_t m = __ballot(bad);
-  return bad && (threadIdx.x & 63) == (uint32_t)(__ffsll((unsigned long long)m) - 1);
-}
-}  // namespace
+// wave, so each reason's lowest offender goes out by lowest_offender's one atomicMin per wave.
 
 // one lane per entry.  number[seq - 1] is a plain load of uploaded data, across a block edge as inside one.
 __global__ void __launch_bounds__(256) k_ledger_audit_screen(LedgerDev d, uint32_t n, LedgerAuditDev *rep) {
@@ -449,16 +348,16 @@ __global__ void __launch_bounds__(256) k_ledger_audit_resolve(LedgerDev d, uint3
                                                               LedgerAuditDev *rep) {
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   bool credited = false, claimed = false, broken = false;
-  uint32_t owner = LEDGER_EMPTY;
+  uint32_t owner = SLOT_EMPTY;
   if (seq < n) {
     const uint32_t at = stay[seq];
-    if (at != LEDGER_NO_SLOT) owner = d.nslot[at];
+    if (at != NO_SLOT) owner = d.nslot[at];
     credited = d.flags[seq] & LEDGER_CREDITED;
     if (owner > seq)  // a slot holds the minimum of its nullifier's seqs: defensive, as the probe's bound
       atomicOr(&rep->ctr.err, 2u);
     else
       broken = credited != (owner == seq);
-    d.astay[seq] = LEDGER_NO_SLOT;
+    d.astay[seq] = NO_SLOT;
     if (credited && !credit_entry(d, seq, n, &claimed)) atomicOr(&rep->ctr.err, 4u);
   }
   if (lowest_offender(broken)) atomicMin(&rep->credit_rule, (unsigned long long)seq << 32 | owner);
@@ -503,7 +402,7 @@ __global__ void __launch_bounds__(256) k_ledger_round_credit(LedgerDev v, uint32
   if (j >= k) return;
   bool claimed;
   if (!ql::round_credits(v.flags[j]))
-    v.astay[j] = LEDGER_NO_SLOT;
+    v.astay[j] = NO_SLOT;
   else if (!credit_entry(v, j, k, &claimed))
     atomicOr(err, 4u);  // the probe ran out of slots: cannot be reached
 }

@@ -188,7 +188,7 @@ inline bool audit_facts_host(const AuditLog &g, const AuditClaims &c, HostLedger
   led.flags.assign(g.flags, g.flags + n);
   led.astay.assign(n, EMPTY);
   for (uint64_t seq = 0; seq < n; seq++) {
-    const uint32_t owner = led.nslot[led.probe(led.nslot, led.nullifier, (uint32_t)seq)];
+    const uint32_t owner = led.nslot[led.ntable().probe((uint32_t)seq)];
     const bool credited = g.flags[seq] & FLAG_CREDITED;
     if (credited != (owner == seq) && f.credit_rule == AUDIT_NONE) {
       f.credit_rule = seq;

@@ -6,11 +6,10 @@
 // a launch before any launch that reads it):
 //   nullifier[C][4] number[C] amount[C][4] (u32 limbs, most significant first)
 //   account[C][4]   flags[C] (bit 0 credited)   astay[C] (a credited entry's account slot)
-// The tables: S = the power of two >= 2 C slots of uint32_t each, a seq or
-// 0xFFFFFFFF (empty); open addressing, linear probing, wrapping.
-//   HOME SLOT = nullifier[0] & (S - 1)      (nslot)
-//   HOME SLOT = exit_account[0] & (S - 1)   (aslot; sum[S][4] beside it)
-// (ledger_table.h states the same rules for the host path.)
+// The tables: two slot tables (slot_table.h has the layout and the home-slot
+// rule, slot_table_device.h the probes) of S = the power of two >= 2 C slots
+// each: nslot keyed by the nullifier, aslot by the exit account, with sum[S][4]
+// beside it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -16,10 +16,8 @@
 //     (acc_layout.h): node = hash_no_pad(left || right), the last node of an odd
 //     level moves up unchanged; laid out for the ledger's capacity
 //   commitment = (root, n); the settler publishes (root, n, payouts)
-// The checker takes the tree's shape from (seq, n), never from the receipt
-// (qpk::path_levels), and a receipt whose depth or side bits say otherwise is
-// rejected: (depth, side bits) is the route from the root to one node of the
-// tree, and the shape rule yields the routes of level-0 nodes only.  A leaf is
+// The checker (qpk::receipt_walk) takes the tree's shape from (seq, n), never
+// from the receipt.  A leaf is
 // the second permutation of a sponge and a node the only permutation of one
 // over a zero state, so a node's digest is a leaf's only where a 14-felt input
 // and an 8-felt input collide.
@@ -33,10 +31,8 @@
 
 namespace ql {
 
-constexpr uint32_t PATH_SLOTS = qpk::ACC_PATH_SLOTS;
 constexpr uint32_t LEAF_FELTS = 14;
-// qp_receipt_status (qpgpu.h)
-enum : int { RECEIPT_OK = 0, RECEIPT_SHAPE = 1, RECEIPT_ROOT = 2, RECEIPT_NON_CANONICAL = 3, RECEIPT_NULL = 4 };
+using qpk::ACC_PATH_SLOTS, qpk::RECEIPT_NON_CANONICAL, qpk::RECEIPT_NULL, qpk::RECEIPT_OK, qpk::RECEIPT_ROOT, qpk::RECEIPT_SHAPE;
 
 inline void log_leaf(const uint64_t nul[4], uint64_t number, const uint32_t amount[4], const uint64_t account[4],
                      uint8_t flags, uint64_t out[4]) {
@@ -49,11 +45,8 @@ inline void log_leaf(const uint64_t nul[4], uint64_t number, const uint32_t amou
   memcpy(out, s, 32);
 }
 
-inline void log_node(const uint64_t l[4], const uint64_t r[4], uint64_t out[4]) {
-  uint64_t s[12] = {l[0], l[1], l[2], l[3], r[0], r[1], r[2], r[3], 0, 0, 0, 0};
-  ps::permute(s);
-  memcpy(out, s, 32);
-}
+// the node hash, hash_no_pad(left || right): one function for every log tree
+inline constexpr auto &log_node = ps::two_to_one;
 
 // the host path's log tree: a qpk::HostTree laid out for the ledger's capacity, the log's entries its leaves
 struct HostLog : qpk::HostTree {
@@ -87,27 +80,11 @@ struct HostLog : qpk::HostTree {
 inline int receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, const uint64_t nullifier[4], uint64_t number,
                          const uint32_t amount[4], const uint64_t account[4], uint8_t flags, const uint64_t *siblings,
                          uint32_t path_bits, uint32_t depth) {
-  if (!canonical(root, 4) || !canonical(nullifier, 4) || number >= P || !canonical(account, 4) ||
-      flags > FLAG_CREDITED || !canonical(siblings, PATH_SLOTS * 4))
+  if (!canonical(nullifier, 4) || number >= P || !canonical(account, 4) || flags > FLAG_CREDITED)
     return RECEIPT_NON_CANONICAL;
-  if (!n || n > qpk::ACC_MAX_LEAVES || seq >= n) return RECEIPT_SHAPE;
-  const uint32_t m = qpk::path_levels(seq, n);
-  uint32_t d = 0, bits = 0;
-  for (uint32_t l = 0; l < 32; l++)
-    if (m >> l & 1) bits |= (uint32_t)((seq >> l) & 1) << d++;
-  if (d != depth || bits != path_bits) return RECEIPT_SHAPE;
-  for (uint32_t i = d * 4; i < PATH_SLOTS * 4; i++)
-    if (siblings[i]) return RECEIPT_SHAPE;  // the slots above the depth hold the zero digest
-  uint64_t cur[4];
-  log_leaf(nullifier, number, amount, account, flags, cur);
-  for (uint32_t i = 0; i < d; i++) {
-    const uint64_t *s = siblings + i * 4;
-    if (bits >> i & 1)
-      log_node(s, cur, cur);
-    else
-      log_node(cur, s, cur);
-  }
-  return memcmp(cur, root, 32) ? RECEIPT_ROOT : RECEIPT_OK;
+  uint64_t leaf[4];
+  log_leaf(nullifier, number, amount, account, flags, leaf);
+  return qpk::receipt_walk(root, n, seq, leaf, siblings, path_bits, depth, log_node);
 }
 
 }  // namespace ql

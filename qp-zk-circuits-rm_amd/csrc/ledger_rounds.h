@@ -18,9 +18,9 @@
 //   trust them; the audit is what checks flags.  [0, n) gives the cumulative
 //   payouts; the rounds of consecutive ranges add up to them account by account.
 //   m0 == m1 gives no rows.
-// Both paths use a scratch account table of the call's own, table_slots(m1 -
-// m0) slots, home slot account[0] & (S - 1), linear probing: the ledger's rule
-// (ledger_table.h).  The ledger and the log are only read.
+// Both paths use a scratch account table of the call's own, a slot table
+// (slot_table.h) of table_slots(m1 - m0) slots keyed by the account.  The
+// ledger and the log are only read.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -64,7 +64,9 @@ inline std::string round_log_refusal(const uint64_t *accounts_log, const uint8_t
 
 // The host path, sequentially, over a log in the layout qp_ledger_entries gives (indexed by seq from
 // 0).  Entries arrive in seq order, so an account's row is made by its first credited entry of the
-// range and the rows come out in first_seq order.  A slot holds a row's index.
+// range and the rows come out in first_seq order.  A slot holds a row's index, and a row exists only
+// once its slot is claimed, so the probing key is not in the table's key column yet: the probe is
+// written out here and not qst::SlotTable's, which takes the key from keys[seq].
 inline void round_payouts_host(const uint64_t *accounts_log, const uint32_t *amounts, const uint8_t *flags, uint64_t m0,
                                uint64_t m1, RoundRows &out) {
   out = RoundRows();

@@ -9,36 +9,26 @@
 //   nullifier[0:4] root_hash[4:8] funding_amount[8:12] exit_account[12:16]
 // funding_amount is four 32-bit limbs, most significant first (felts_to_u128).
 //
-// Two tables of one kind (both paths): open addressing, linear probing, S =
-// table_slots(C) slots for a capacity of C admitted transfers, S the power of
-// two >= 2 C.  A slot is a uint32_t: the log index `seq` of an entry, or EMPTY.
-// The key is not in the slot: it is the entry's nullifier, or its exit account.
-//   HOME SLOT = key[0] & (S - 1)
-// and the probe goes to slot + 1, wrapping.  The nullifier table takes every
-// admitted entry and its slot ends at the lowest seq of that nullifier: the
-// credited one.  The account table takes the credited entries and its slot ends
-// at the lowest seq credited to that account; sum[slot][4] holds the account's
-// four limb sums.
+// Two slot tables (slot_table.h; both paths), each for a capacity of C admitted
+// transfers.  The nullifier table takes every admitted entry and its slot ends
+// at the lowest seq of that nullifier: the credited one.  The account table
+// takes the credited entries and its slot ends at the lowest seq credited to
+// that account; sum[slot][4] holds the account's four limb sums.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 #include <vector>
+#include "slot_table.h"
 
-#if defined(__HIPCC__)
-#define QL_HD __host__ __device__
-#else
-#define QL_HD
-#endif
+#define QL_HD QST_HD
 
 namespace ql {
 
-constexpr uint64_t P = 0xFFFFFFFF00000001ull;
+using qst::canonical, qst::EMPTY, qst::key_equal, qst::MAX_CAPACITY, qst::NOT_FOUND, qst::P, qst::SlotTable,
+    qst::table_slots;
 constexpr uint32_t NPI = 16, PI_NULLIFIER = 0, PI_ROOT = 4, PI_AMOUNT = 8, PI_ACCOUNT = 12;
 constexpr uint32_t MAX_ROOTS = 4096;
-constexpr uint64_t MAX_CAPACITY = 1ull << 31;
 constexpr uint32_t MAX_BATCH = 1u << 22;  // transfers per cast call
-constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-constexpr uint64_t NOT_FOUND = ~0ull;
 constexpr uint8_t FLAG_CREDITED = 1;
 
 // qp_transfer_status (qpgpu.h), in the order of the checks
@@ -51,21 +41,7 @@ struct Result {
   uint64_t number, first;
 };
 
-inline uint64_t table_slots(uint64_t capacity) {
-  uint64_t s = 2;
-  while (s < 2 * capacity) s <<= 1;
-  return s;
-}
-inline bool canonical(const uint64_t *v, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (v[i] >= P) return false;
-  return true;
-}
-
-// four felts as a key: equality, and the order the accepted roots are sorted in (felt 0 first)
-QL_HD inline bool key_equal(const uint64_t *a, const uint64_t *b) {
-  return a[0] == b[0] && a[1] == b[1] && a[2] == b[2] && a[3] == b[3];
-}
+// four felts as a key: the order the accepted roots are sorted in (felt 0 first)
 QL_HD inline int key_compare(const uint64_t *a, const uint64_t *b) {
   for (int i = 0; i < 4; i++)
     if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
@@ -190,16 +166,11 @@ struct HostLedger {
     capacity = cap;
     mask = S - 1;
   }
-  // the slot of log entry seq's key in one table: its own (claimed now) or an equal earlier entry's
-  uint64_t probe(std::vector<uint32_t> &slot, const std::vector<uint64_t> &keys, uint32_t seq) const {
-    const uint64_t *k = &keys[(size_t)seq * 4];
-    for (uint64_t at = k[0] & mask;; at = (at + 1) & mask) {  // count <= C <= S / 2: an empty slot exists
-      if (slot[at] == EMPTY) slot[at] = seq;
-      if (slot[at] == seq || key_equal(&keys[(size_t)slot[at] * 4], k)) return at;
-    }
-  }
+  // the two tables over the log as it stands; a const ledger's are for lookup, which writes no slot
+  SlotTable ntable() const { return {const_cast<uint32_t *>(nslot.data()), mask, nullifier.data()}; }
+  SlotTable atable() const { return {const_cast<uint32_t *>(aslot.data()), mask, account.data()}; }
   void credit(uint32_t seq) {
-    const uint64_t at = probe(aslot, account, seq);
+    const uint64_t at = atable().probe(seq);
     astay[seq] = (uint32_t)at;
     for (int j = 0; j < 4; j++) sum[at * 4 + j] += amount[(size_t)seq * 4 + j];
   }
@@ -212,7 +183,7 @@ struct HostLedger {
     number.push_back(num);
     flags.push_back(0);
     astay.push_back(EMPTY);
-    const uint32_t owner = nslot[probe(nslot, nullifier, seq)];
+    const uint32_t owner = nslot[ntable().probe(seq)];
     *first = number[owner];
     if (owner != seq) return false;
     flags[seq] |= FLAG_CREDITED;
@@ -241,30 +212,17 @@ struct HostLedger {
     mask = S - 1;
     for (uint64_t seq = 0; seq < count(); seq++)
       if (flags[seq] & FLAG_CREDITED) {
-        probe(nslot, nullifier, (uint32_t)seq);
+        ntable().probe((uint32_t)seq);
         credit((uint32_t)seq);
       }
   }
-  // the read-only probe: the entry a key's chain holds, or EMPTY
-  uint32_t lookup(const std::vector<uint32_t> &slot, const std::vector<uint64_t> &keys, const uint64_t k[4],
-                  uint64_t *at_out = nullptr) const {
-    uint64_t at = k[0] & mask;
-    for (uint64_t tried = 0; tried <= mask; tried++, at = (at + 1) & mask) {
-      if (slot[at] == EMPTY) return EMPTY;
-      if (key_equal(&keys[(size_t)slot[at] * 4], k)) {
-        if (at_out) *at_out = at;
-        return slot[at];
-      }
-    }
-    return EMPTY;
-  }
   uint64_t find(const uint64_t nul[4]) const {
-    const uint32_t seq = lookup(nslot, nullifier, nul);
+    const uint32_t seq = ntable().lookup(nul);
     return seq == EMPTY ? NOT_FOUND : seq;
   }
   bool total_for(const uint64_t acc[4], uint64_t sums[4]) const {
     uint64_t at = 0;
-    const bool found = lookup(aslot, account, acc, &at) != EMPTY;
+    const bool found = atable().lookup(acc, &at) != EMPTY;
     for (int j = 0; j < 4; j++) sums[j] = found ? sum[at * 4 + j] : 0;
     return found;
   }

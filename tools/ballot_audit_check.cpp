@@ -157,7 +157,7 @@ static void run(uint64_t n) {
     AuditFacts f;
     CHECK(audit_facts_host(g.nul.data(), g.num.data(), g.fl.data(), n, cap, true, b2, log, f));
     CHECK(b2.slot.size() == table_slots(cap) && b2.count() == n && b2.yes == box.yes && b2.no == box.no);
-    for (uint64_t s = 0; s < n; s++) CHECK(find(b2, &g.nul[s * 4]) == find(box, &g.nul[s * 4]));
+    for (uint64_t s = 0; s < n; s++) CHECK(b2.find(&g.nul[s * 4]) == box.find(&g.nul[s * 4]));
     HostLog grown;  // the same leaves appended one at a time into a tree with room to spare
     grown.open(cap);
     for (uint64_t m = 1; m <= n; m++) {

@@ -1,5 +1,5 @@
 // ballot_log_check.cpp — the ballot box's log commitment in host C++
-// (csrc/ballot_log.h: the read-only find, the leaf and node hashes, HostLog on
+// (csrc/ballot_table.h: the read-only find; csrc/ballot_log.h: the leaf and node hashes, HostLog on
 // acc_layout.h's host tree, path extraction, the receipt check) under the sanitizers, against a
 // brute-force scan of the log and a naive recursive tree, at 1, 2, 3, 64 and 65
 // entries and on a capacity-full box, with doubles among the entries, committed
@@ -63,7 +63,7 @@ static void check_receipts(const HostBox &box, const HostLog &log, const std::ve
   uint64_t root[4];
   memcpy(root, log.root(), 32);
   for (uint64_t seq = 0; seq < n; seq++) {
-    uint64_t sib[PATH_SLOTS * 4], leaf[4];
+    uint64_t sib[ACC_PATH_SLOTS * 4], leaf[4];
     uint32_t bits, depth;
     log.path(seq, sib, &bits, &depth, leaf);
     CHECK(!memcmp(leaf, leaves[seq].v, 32));
@@ -79,7 +79,7 @@ static void check_receipts(const HostBox &box, const HostLog &log, const std::ve
     CHECK(receipt_check(root, n, n, nul, num, fl, sib, bits, depth) == RECEIPT_SHAPE);
     CHECK(receipt_check(root, 0, seq, nul, num, fl, sib, bits, depth) == RECEIPT_SHAPE);
     CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, depth + 1) == RECEIPT_SHAPE);
-    CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, PATH_SLOTS + 1) == RECEIPT_SHAPE);
+    CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, ACC_PATH_SLOTS + 1) == RECEIPT_SHAPE);
     if (depth) {
       CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits ^ 1, depth) == RECEIPT_SHAPE);
       CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, depth - 1) == RECEIPT_SHAPE);
@@ -87,7 +87,7 @@ static void check_receipts(const HostBox &box, const HostLog &log, const std::ve
       CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, depth) == RECEIPT_ROOT);
       sib[(depth - 1) * 4 + 3] ^= 1;
     }
-    if (depth < PATH_SLOTS) {
+    if (depth < ACC_PATH_SLOTS) {
       sib[depth * 4] = 1;
       CHECK(receipt_check(root, n, seq, nul, num, fl, sib, bits, depth) == RECEIPT_SHAPE);
       sib[depth * 4] = P;
@@ -130,12 +130,12 @@ static void run(uint64_t n, uint64_t capacity, const std::vector<uint64_t> &step
   check_receipts(box, log, leaves);
   // find: every entry's nullifier gives the counted entry; absent keys with a crowded, an empty and the last home slot
   for (uint64_t s = 0; s < n; s++) {
-    const uint64_t got = find(box, &box.nullifier[s * 4]);
+    const uint64_t got = box.find(&box.nullifier[s * 4]);
     CHECK(got == brute_find(box, &box.nullifier[s * 4]) && got <= s && (box.flags[got] & FLAG_COUNTED));
   }
   for (uint64_t home : {box.mask - 1, box.mask, (uint64_t)0, box.mask / 2}) {
     uint64_t q[4] = {(felt() & ~box.mask) | home, felt(), felt(), felt()};
-    CHECK(find(box, q) == brute_find(box, q));
+    CHECK(box.find(q) == brute_find(box, q));
   }
   if (reserve_to) {
     uint64_t before[4];
@@ -144,7 +144,7 @@ static void run(uint64_t n, uint64_t capacity, const std::vector<uint64_t> &step
     log.drop();
     CHECK(log.commit(box) && log.capacity == reserve_to && !memcmp(before, log.root(), 32));
     check_receipts(box, log, leaves);
-    for (uint64_t s = 0; s < n; s++) CHECK(find(box, &box.nullifier[s * 4]) == brute_find(box, &box.nullifier[s * 4]));
+    for (uint64_t s = 0; s < n; s++) CHECK(box.find(&box.nullifier[s * 4]) == brute_find(box, &box.nullifier[s * 4]));
   }
 }
 

@@ -5,6 +5,7 @@
 // tree, at 1, 2, 3, 5, 65 and 131 entries in a ledger of exactly that capacity,
 // with double spends among the entries, committed in one step and in several,
 // across a reserve; the receipt check with all 32 sibling slots in use; the
+// shared receipt walk on its own under a ballot leaf and a ledger leaf; the
 // audit of an exactly-full log, honest and tampered.  A stand-alone CPU
 // program; device code runs under no sanitizer.
 //
@@ -14,6 +15,7 @@
 #include <stdlib.h>
 #include <map>
 #include <random>
+#include "../qp-zk-circuits-rm_amd/csrc/ballot_log.h"
 #include "../qp-zk-circuits-rm_amd/csrc/ledger_audit.h"
 #include "../qp-zk-circuits-rm_amd/csrc/ledger_log.h"
 
@@ -76,7 +78,7 @@ static void check_receipts(const HostLedger &h, const HostLog &log, const std::v
   uint64_t root[4];
   memcpy(root, log.root(), 32);
   for (uint64_t seq = 0; seq < n; seq++) {
-    uint64_t sib[PATH_SLOTS * 4], leaf[4], nul[4], acc[4];
+    uint64_t sib[ACC_PATH_SLOTS * 4], leaf[4], nul[4], acc[4];
     uint32_t bits, depth, amt[4];
     log.path(seq, sib, &bits, &depth, leaf);
     CHECK(!memcmp(leaf, leaves[seq].v, 32));
@@ -104,7 +106,7 @@ static void check_receipts(const HostLedger &h, const HostLog &log, const std::v
     CHECK(receipt_check(root, n, n, nul, num, amt, acc, fl, sib, bits, depth) == RECEIPT_SHAPE);
     CHECK(receipt_check(root, 0, seq, nul, num, amt, acc, fl, sib, bits, depth) == RECEIPT_SHAPE);
     CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, depth + 1) == RECEIPT_SHAPE);
-    CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, PATH_SLOTS + 1) == RECEIPT_SHAPE);
+    CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, ACC_PATH_SLOTS + 1) == RECEIPT_SHAPE);
     if (depth) {
       CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits ^ 1, depth) == RECEIPT_SHAPE);
       CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, depth - 1) == RECEIPT_SHAPE);
@@ -112,7 +114,7 @@ static void check_receipts(const HostLedger &h, const HostLog &log, const std::v
       CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, depth) == RECEIPT_ROOT);
       sib[(depth - 1) * 4 + 3] ^= 1;
     }
-    sib[depth * 4] = 1;  // depth <= 31 < PATH_SLOTS
+    sib[depth * 4] = 1;  // depth <= 31 < ACC_PATH_SLOTS
     CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, depth) == RECEIPT_SHAPE);
     sib[depth * 4] = P;
     CHECK(receipt_check(root, n, seq, nul, num, amt, acc, fl, sib, bits, depth) == RECEIPT_NON_CANONICAL);
@@ -177,7 +179,7 @@ static void run(uint64_t n, uint64_t capacity, const std::vector<uint64_t> &step
 // a receipt whose 32 sibling slots are all in use cannot come from a tree (the deepest path is 31): the
 // checker reads all 32 slots and refuses the depth, for every n and seq
 static void check_all_slots() {
-  uint64_t sib[PATH_SLOTS * 4], root[4] = {1, 2, 3, 4}, nul[4] = {5, 6, 7, 8}, acc[4] = {9, 10, 11, 12};
+  uint64_t sib[ACC_PATH_SLOTS * 4], root[4] = {1, 2, 3, 4}, nul[4] = {5, 6, 7, 8}, acc[4] = {9, 10, 11, 12};
   uint32_t amt[4] = {1, 2, 3, 4};
   for (uint64_t &x : sib) x = felt();
   for (uint64_t n : {(uint64_t)1, (uint64_t)2, qpk::ACC_MAX_LEAVES})
@@ -192,6 +194,40 @@ static void check_all_slots() {
   CHECK(receipt_check(root, n, seq, nul, 0, amt, acc, 1, sib, 0x7FFFFFFFu, 31) == RECEIPT_ROOT);
   sib[31 * 4 + 3] = P;
   CHECK(receipt_check(root, n, seq, nul, 0, amt, acc, 1, sib, 0x7FFFFFFFu, 31) == RECEIPT_NON_CANONICAL);
+}
+
+// acc_layout.h's receipt_walk on its own, under a ballot leaf and a ledger leaf, at the sizes that promote
+// a node at each level, against HostTree's paths: every path walks to the root, and a flipped depth, a
+// flipped side bit, a sibling above the depth and a sibling felt of p each give their reason
+static void check_walk() {
+  for (uint64_t n : {1ull, 2ull, 3ull, 5ull, 8ull, 9ull})
+    for (int ballot = 0; ballot < 2; ballot++) {
+      qpk::HostTree t;
+      t.open(n);
+      for (uint64_t seq = 0; seq < n; seq++) {
+        const uint64_t nul[4] = {felt(), felt(), felt(), felt()}, acc[4] = {felt(), felt(), felt(), felt()};
+        const uint32_t amt[4] = {(uint32_t)rng(), (uint32_t)rng(), (uint32_t)rng(), (uint32_t)rng()};
+        if (ballot)
+          qb::log_leaf(nul, seq + 1, 3, t.node(0, seq));
+        else
+          log_leaf(nul, seq + 1, amt, acc, 1, t.node(0, seq));
+      }
+      t.append(n, log_node);
+      for (uint64_t seq = 0; seq < n; seq++) {
+        uint64_t sib[ACC_PATH_SLOTS * 4], leaf[4];
+        uint32_t bits, depth;
+        t.path(seq, sib, &bits, &depth, leaf);
+        auto walk = [&](uint32_t b, uint32_t d) { return qpk::receipt_walk(t.root(), n, seq, leaf, sib, b, d, log_node); };
+        CHECK(walk(bits, depth) == RECEIPT_OK);
+        CHECK(walk(bits, depth ^ 1) == RECEIPT_SHAPE);
+        CHECK(walk(bits ^ 1, depth) == RECEIPT_SHAPE);
+        sib[depth * 4] = 1;
+        CHECK(walk(bits, depth) == RECEIPT_SHAPE);
+        sib[depth * 4] = 0;
+        sib[1] = P;
+        CHECK(walk(bits, depth) == RECEIPT_NON_CANONICAL);
+      }
+    }
 }
 
 // the host audit of an exactly-full log against a brute-force scan
@@ -291,6 +327,7 @@ int main() {
   run(64, 100, {7, 14, 63, 64}, 64);    // a reserve down to exactly full
   run(131, 131, {1, 100, 101, 130, 131}, 4096);
   check_all_slots();
+  check_walk();
   check_audit(200);
   printf("ledger_log_check: ok\n");
   return 0;
