@@ -1,5 +1,6 @@
-// acc_tree.cpp — AccTree (acc_tree.h): allocation, the batched path download, the re-lay of a reserve.
+// acc_tree.cpp — AccTree (acc_tree.h): allocation, the batched path download, the re-lay of a reserve, an audit's batch of prefix roots.
 #include "acc_tree.h"
+#include <string.h>
 #include <algorithm>
 #include "../../include/qpgpu.h"
 
@@ -65,4 +66,19 @@ int AccTree::reserve(AccErr e, uint64_t new_capacity, const qpk::AccLevels &nlv,
   lv = nlv;
   capacity = new_capacity;
   return QP_OK;
+}
+
+void PrefixRootBatch::get(uint32_t i, uint64_t out[4]) {
+  if (!asked) {
+    asked = true;
+    at.assign(k, 0);
+    for (uint32_t j = 0; j < k; j++)
+      if (ns[j] <= n) {
+        at[j] = (uint32_t)ms.size();
+        ms.push_back(ns[j]);
+      }
+    got.assign(ms.size() * 4, 0);
+    rc = tree.prefix_roots(e, s, ms.data(), (uint32_t)ms.size(), got.data());
+  }
+  memcpy(out, &got[(size_t)at[i] * 4], 32);
 }

@@ -1,11 +1,14 @@
 // acc_tree.h — the device owner of one accumulator tree (acc_kernels.h): the
-// digest buffer, the level table and one batch of path buffers.  qp_registry and
-// qp_ballot_box each hold one.  The leaves, hipSetDevice, timing events and the
-// moment a new size counts stay with the handle: the launching calls only
-// launch, and the handle sets `lv` once its own synchronise succeeded.
+// digest buffer, the level table and one batch of path buffers.  qp_registry
+// holds one; qp_ballot_box and qp_ledger hold theirs in a LogCommit
+// (log_commit.h), and each log audit builds one for its call.  The leaves,
+// hipSetDevice, timing events and the moment a new size counts stay with the
+// owner: the launching calls only launch, and the owner sets `lv` once its own
+// synchronise succeeded.
 #pragma once
 #include <stdint.h>
 #include <string>
+#include <vector>
 #include "acc_kernels.h"
 #include "ctx.h"
 
@@ -53,4 +56,22 @@ struct AccTree {
   // the same leaves re-laid for new_capacity, nlv = their table there: a new buffer beside the old, every
   // level copied, the stream synchronised; the tree moves over only once all of it succeeded
   int reserve(AccErr e, uint64_t new_capacity, const qpk::AccLevels &nlv, hipStream_t s);
+};
+
+// The prefix roots that an audit's commitment claims (root_i, n_i) name, fetched from `tree` (n
+// leaves) in one batch by the first get(), so a verdict that stops at an earlier reason launches
+// nothing: get(i, out) = the root at n_i leaves, for a claim with n_i <= n.  rc: what the batch
+// returned (its reason is in e.err).
+struct PrefixRootBatch {
+  AccTree &tree;
+  AccErr e;
+  hipStream_t s;
+  const uint64_t *ns;  // [k]
+  uint32_t k;
+  uint64_t n;
+  int rc = 0;  // QP_OK
+  bool asked = false;
+  std::vector<uint64_t> ms, got;
+  std::vector<uint32_t> at;
+  void get(uint32_t i, uint64_t out[4]);
 };

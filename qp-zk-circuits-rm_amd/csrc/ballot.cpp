@@ -3,10 +3,12 @@
 // host (ballot_table.h), each nullifier admitted once.  With a context the
 // nullifier set and the tally live on the device (ballot.hip); without one the
 // same semantics run on the host (qb::HostBox).  The log commitment (find,
-// commit_log, receipts and the receipt check: ballot_log.h) is brought up to
-// date on demand; a cast does not touch it.  roots_at answers from that tree;
-// restore reopens a box from a published log through the audit's passes
-// (ballot_audit.h, ballot_audit.cpp) and keeps the table they built.
+// commit_log, receipts and the receipt check: ballot_log.h) is the box's
+// LogCommit (log_commit.h), brought up to date on demand; a cast does not touch
+// it.  roots_at answers from that tree; restore reopens a box from a published
+// log through the audit's passes (ballot_audit.h, ballot_audit.cpp) and keeps
+// the table they built.  The refusals worded alike for the box and the transfer
+// ledger are handle_common.h's; what is stated here is the box's own.
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <algorithm>
@@ -22,6 +24,8 @@
 #include "ballot_log.h"
 #include "ballot_table.h"
 #include "ctx.h"
+#include "handle_common.h"
+#include "log_commit.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_ballot_result) == sizeof(qb::Result) && sizeof(qb::Result) == 24, "qp_ballot_result layout");
@@ -35,19 +39,12 @@ static_assert(QP_BALLOT_COUNTED == qb::COUNTED && QP_BALLOT_PROOF_REJECTED == qb
                   QP_BALLOT_DOUBLE_VOTE == qb::DOUBLE_VOTE,
               "qp_ballot_status and ballot_table.h differ");
 
-namespace {
-// the device half of a box for one capacity: the log, the table
-struct DeviceTables {
-  DevBuf nul, num, flags, slot;
-  uint64_t mask = 0;
-  qpk::BallotDev dev() const {
-    return qpk::BallotDev{nul.p, num.p, flags.as<uint8_t>(), slot.as<uint32_t>(), mask};
-  }
-};
-}  // namespace
+using namespace qph;
+using qba::DeviceTables;
 
-struct qp_ballot_box {
-  qp_ctx *ctx = nullptr;  // null: the host path
+struct qp_ballot_box : qb::Words {
+  static constexpr int BROKEN = QP_ERR_STATE;  // what a broken invariant returns (the ledger: QP_ERR_HIP)
+  qp_ctx *ctx = nullptr;                       // null: the host path
   std::string err;
   bool dead = false;  // a device step failed part-way, or the defensive error word was set: no further casts
   qb::Screen screen;
@@ -61,49 +58,25 @@ struct qp_ballot_box {
   std::vector<uint64_t> h_first;
   TimingEvents<3> ev;  // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
-  // ---- the log commitment, both paths: built by the first commit, dropped by reserve
-  qb::HostLog hlog;
-  AccTree log;             // the device path's log tree, laid out for `capacity`; `committed` leaves
-  uint64_t committed = 0;  // leaves of the tree = the n of (log_root, n)
-  uint64_t log_root[4] = {0, 0, 0, 0};
+  LogCommit<qb::HostLog> lc;         // the log commitment, both paths
   DevBuf d_q, d_seq, d_nul, d_flag;  // per find / entries_at batch (LOG_BATCH entries)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
 };
 
 namespace {
-thread_local std::string g_new_err;  // why the last qp_ballot_box_new on this thread was refused
+// why the last qp_ballot_box_new (restore, log_audit) on this thread was refused
+thread_local HandlelessError g_new_err;
 
 int refuse_new(qp_ctx *c, const std::string &why) {
-  g_new_err = "qp_ballot_box_new: " + why;
-  if (c) c->err = g_new_err;
+  g_new_err.set(c, "qp_ballot_box_new: " + why);
   return QP_ERR_ARG;
 }
-
 }  // namespace
 
-void qba::set_boxless_error(qp_ctx *c, const std::string &why) {
-  g_new_err = why;
-  if (c) c->err = why;
-}
+void qba::set_boxless_error(qp_ctx *c, const std::string &why) { g_new_err.set(c, why); }
 
 namespace {
-int alloc_tables(qp_ballot_box *b, uint64_t capacity, DeviceTables &t) {
-  const uint64_t S = qb::table_slots(capacity);
-  QP_HIP_TRY(b, t.nul.alloc(capacity * 4));
-  QP_HIP_TRY(b, t.num.alloc(capacity));
-  QP_HIP_TRY(b, t.flags.alloc((capacity + 7) / 8));
-  QP_HIP_TRY(b, t.slot.alloc(S / 2));
-  t.mask = S - 1;
-  QP_HIP_TRY(b, hipMemsetAsync(t.slot.p, 0xFF, S * 4, b->ctx->stream));
-  return QP_OK;
-}
-
-int dead_box(qp_ballot_box *b, const char *fn) {
-  b->err = std::string(fn) + ": an earlier call on this box failed on the device part-way; its state is not known";
-  return QP_ERR_STATE;
-}
-
 // the device steps of one batch: the packed ballots into log [count, count + k), insert, resolve
 int cast_device(qp_ballot_box *b, qb::Result *out) {
   qp_ctx *c = b->ctx;
@@ -136,10 +109,8 @@ int cast_device(qp_ballot_box *b, qb::Result *out) {
   QP_HIP_TRY(b, hipStreamSynchronize(s));
   QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[0], b->ev.e[0], b->ev.e[1]));
   QP_HIP_TRY(b, hipEventElapsedTime(&b->ms[1], b->ev.e[1], b->ev.e[2]));
-  if (now.err) {
-    b->err = "qp_ballot_box_cast: the nullifier table's probe found no slot (an internal invariant broke)";
-    return QP_ERR_STATE;
-  }
+  if (now.err)
+    return refuse(b, b->BROKEN, "qp_ballot_box_cast: the nullifier table's probe found no slot (an internal invariant broke)");
   for (uint32_t j = 0; j < k; j++) {
     qb::Result &r = out[pk.pos[j]];
     r.first = b->h_first[j];
@@ -156,11 +127,7 @@ int cast_screened(qp_ballot_box *b, const char *fn, const uint64_t *pis, const u
                   qb::Result *out) {
   qb::screen_and_pack(b->screen, pis, verdicts, n, b->cast, out, b->pk);
   const uint64_t k = b->pk.size();
-  if (k > b->cap() - b->admitted()) {
-    b->err = std::string(fn) + ": " + std::to_string(b->admitted()) + " + " + std::to_string(k) +
-             " admitted ballots exceed the capacity " + std::to_string(b->cap()) + "; call qp_ballot_box_reserve first";
-    return QP_ERR_ARG;
-  }
+  if (k > b->cap() - b->admitted()) return over_capacity(b, fn, k);
   if (!b->ctx) {
     b->host.admit_packed(b->pk, out);
   } else if (k) {
@@ -172,11 +139,6 @@ int cast_screened(qp_ballot_box *b, const char *fn, const uint64_t *pis, const u
   }
   b->cast += n;
   return QP_OK;
-}
-
-int bad_alloc(qp_ballot_box *b, const char *fn) {
-  b->err = std::string(fn) + ": out of host memory";
-  return QP_ERR_OOM;
 }
 
 // entries per k_ballot_find / k_ballot_gather launch (the batch buffers hold this many)
@@ -194,10 +156,9 @@ int log_batch_buffers(qp_ballot_box *b) {
 // the defensive error word after a launch of the log's kernels (copied by the caller, stream synchronised)
 int log_error_word(qp_ballot_box *b, const char *fn, uint32_t err) {
   if (!err) return QP_OK;
-  b->err = std::string(fn) + (err & 4 ? ": a ballot number in the log is not a field element"
-                                      : ": a slot of the nullifier table holds no log entry") +
-           " (an internal invariant broke)";
-  return QP_ERR_STATE;
+  return refuse(b, b->BROKEN, std::string(fn) + (err & 4 ? ": a ballot number in the log is not a field element"
+                                                         : ": a slot of the nullifier table holds no log entry") +
+                                  " (an internal invariant broke)");
 }
 
 int find_device(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
@@ -224,50 +185,17 @@ int find_device(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64
   return QP_OK;
 }
 
-// the log tree up to the admitted count (> 0; the caller checks): leaves [committed, count), the
-// levels above them, the root
-int commit_device(qp_ballot_box *b) {
-  qp_ctx *c = b->ctx;
-  hipStream_t s = c->stream;
-  if (b->committed == b->count) return QP_OK;
-  QP_HIP_TRY(b, hipSetDevice(c->device));
-  if (!b->log.dig.p)
-    if (int rc = b->log.alloc({b->err}, b->capacity)) return rc;
-  qpk::AccLevels lv;
-  if (!qpk::acc_levels_reserved(b->count, b->capacity, lv)) {
-    b->err = "qp_ballot_box_commit_log: the log does not fit its capacity (an internal invariant broke)";
-    return QP_ERR_STATE;
-  }
+// the log commitment up to the admitted count (> 0; the caller checks), on either path
+int commit(qp_ballot_box *b) {
+  const char *fn = "qp_ballot_box_commit_log";
+  if (!b->ctx) return b->lc.commit(b->host) ? QP_OK : log_error_word(b, fn, 4);
   qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
-  uint64_t root[4];
-  uint32_t err = 0;
-  qpk::ballot_leaves(b->t.dev(), (uint32_t)b->committed, (uint32_t)b->count, b->log.dig.p, ctr, s);
-  QP_HIP_TRY(b, hipGetLastError());
-  b->log.append(lv, qpk::acc_row_max(), s);  // the tree holds `committed` leaves
-  QP_HIP_TRY(b, hipGetLastError());
-  QP_HIP_TRY(b, hipMemcpyAsync(root, b->log.root(lv), 32, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(b, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(b, hipStreamSynchronize(s));
-  if (int rc = log_error_word(b, "qp_ballot_box_commit_log", err)) return rc;
-  memcpy(b->log_root, root, 32);
-  b->log.lv = lv;
-  b->committed = b->count;
-  return QP_OK;
-}
-
-// commit on either path; the caller checked that the log is not empty
-int commit_log(qp_ballot_box *b) {
-  if (b->ctx) return commit_device(b);
-  if (!b->hlog.commit(b->host)) return log_error_word(b, "qp_ballot_box_commit_log", 4);
-  memcpy(b->log_root, b->hlog.root(), 32);
-  b->committed = b->hlog.n;
-  return QP_OK;
-}
-
-int receipts_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
-                    uint32_t *depth, uint64_t *leaves) {
-  QP_HIP_TRY(b, hipSetDevice(b->ctx->device));
-  return b->log.paths({b->err}, b->ctx->stream, seqs, k, siblings, path_bits, depth, leaves);
+  auto leaves = [&](uint32_t first, uint32_t end, uint64_t *dig) {
+    qpk::ballot_leaves(b->t.dev(), first, end, dig, ctr, b->ctx->stream);
+  };
+  uint32_t word = 0;
+  if (int rc = b->lc.commit(b->ctx, b->err, fn, b->BROKEN, b->count, b->capacity, leaves, &ctr->err, &word)) return rc;
+  return log_error_word(b, fn, word);
 }
 
 int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
@@ -292,27 +220,6 @@ int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64
   return QP_OK;
 }
 
-// a failed device step of the log's calls leaves the box dead, as a failed cast does
-int device_step(qp_ballot_box *b, int rc) {
-  if (rc) b->dead = true;
-  return rc;
-}
-
-// seqs[k] all inside the log, or QP_ERR_ARG naming the first that is not
-int check_seqs(qp_ballot_box *b, const char *fn, const uint64_t *seqs, uint32_t k) {
-  for (uint32_t i = 0; i < k; i++)
-    if (seqs[i] >= b->admitted()) {
-      b->err = std::string(fn) + ": entry " + std::to_string(seqs[i]) + " (position " + std::to_string(i) +
-               ") is outside the log's " + std::to_string(b->admitted());
-      return QP_ERR_ARG;
-    }
-  return QP_OK;
-}
-
-int empty_log(qp_ballot_box *b, const char *fn) {
-  b->err = std::string(fn) + ": empty log (no ballot has been admitted yet)";
-  return QP_ERR_STATE;
-}
 }  // namespace
 
 extern "C" {
@@ -341,13 +248,13 @@ int qp_ballot_box_new(qp_ctx *c, const uint64_t proposal_id[4], const uint64_t *
       return QP_OK;
     }
   } catch (const std::bad_alloc &) {
-    g_new_err = "qp_ballot_box_new: out of host memory";
+    g_new_err.text = "qp_ballot_box_new: out of host memory";
     return QP_ERR_OOM;
   }
   int rc = QP_OK;
   auto device_open = [&]() -> int {
     QP_HIP_TRY(b, hipSetDevice(c->device));
-    if ((rc = alloc_tables(b.get(), capacity, b->t))) return rc;
+    if ((rc = qba::alloc_tables({b->err}, c->stream, capacity, b->t))) return rc;
     QP_HIP_TRY(b, b->d_ctr.alloc((sizeof(qpk::BallotCounters) + 7) / 8));
     QP_HIP_TRY(b, b->d_audit.alloc(4));
     QP_HIP_TRY(b, hipMemsetAsync(b->d_ctr.p, 0, sizeof(qpk::BallotCounters), c->stream));
@@ -355,7 +262,7 @@ int qp_ballot_box_new(qp_ctx *c, const uint64_t proposal_id[4], const uint64_t *
     return QP_OK;
   };
   if ((rc = device_open())) {
-    g_new_err = c->err = "qp_ballot_box_new: " + b->err;
+    g_new_err.set(c, "qp_ballot_box_new: " + b->err);
     return rc;
   }
   b->capacity = capacity;
@@ -369,7 +276,7 @@ void qp_ballot_box_free(qp_ballot_box *b) {
   delete b;
 }
 
-const char *qp_ballot_box_last_error(const qp_ballot_box *b) { return b ? b->err.c_str() : g_new_err.c_str(); }
+const char *qp_ballot_box_last_error(const qp_ballot_box *b) { return b ? b->err.c_str() : g_new_err.text.c_str(); }
 
 int qp_ballot_box_accept_root(qp_ballot_box *b, const uint64_t root[4]) {
   if (!b) return QP_ERR_ARG;
@@ -393,12 +300,9 @@ int qp_ballot_box_accept_root(qp_ballot_box *b, const uint64_t root[4]) {
 int qp_ballot_box_cast_public(qp_ballot_box *b, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
                               qp_ballot_result *out) {
   if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_cast_public");
+  if (b->dead) return dead_handle(b, "qp_ballot_box_cast_public");
   if (!n) return QP_OK;
-  if (!pis || !out) {
-    b->err = "qp_ballot_box_cast_public: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!pis || !out) return null_buffer(b, "qp_ballot_box_cast_public");
   try {
     return cast_screened(b, "qp_ballot_box_cast_public", pis, verdicts, n, reinterpret_cast<qb::Result *>(out));
   } catch (const std::bad_alloc &) {
@@ -409,30 +313,14 @@ int qp_ballot_box_cast_public(qp_ballot_box *b, const uint64_t *pis, const uint3
 int qp_ballot_box_cast(qp_ballot_box *b, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens,
                        uint32_t n, qp_ballot_result *out) {
   if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_cast");
-  const uint32_t npi = qv::public_input_count(v);
-  if (npi != qb::NPI) {
-    b->err = !v ? "qp_ballot_box_cast: null verifier"
-                : !npi ? "qp_ballot_box_cast: the verifier is not usable"
-                       : "qp_ballot_box_cast: the verifier's circuit has " + std::to_string(npi) +
-                             " public inputs; a voting circuit's has " + std::to_string(qb::NPI);
-    return QP_ERR_ARG;
-  }
+  if (b->dead) return dead_handle(b, "qp_ballot_box_cast");
+  if (int rc = check_verifier(b, "qp_ballot_box_cast", v, qb::NPI, "a voting circuit's")) return rc;
   if (!n) return QP_OK;
-  if (!proofs || !lens || !out) {
-    b->err = "qp_ballot_box_cast: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!proofs || !lens || !out) return null_buffer(b, "qp_ballot_box_cast");
   try {
-    std::vector<uint32_t> verdicts(n);
-    const int rc = qp_verifier_verify(v, proofs, lens, n, verdicts.data());
-    if (rc) {
-      b->err = std::string("qp_ballot_box_cast: qp_verifier_verify: ") + qp_verifier_last_error(v);
-      return rc;
-    }
-    std::vector<uint64_t> pis((size_t)n * qb::NPI, 0);
-    for (uint32_t i = 0; i < n; i++)
-      if (verdicts[i] == QP_VERIFY_OK) memcpy(&pis[(size_t)i * qb::NPI], qv::public_inputs(v, proofs[i]), qb::NPI * 8);
+    std::vector<uint32_t> verdicts;
+    std::vector<uint64_t> pis;
+    if (int rc = verify_and_gather(b, "qp_ballot_box_cast", v, proofs, lens, n, qb::NPI, verdicts, pis)) return rc;
     return cast_screened(b, "qp_ballot_box_cast", pis.data(), verdicts.data(), n, reinterpret_cast<qb::Result *>(out));
   } catch (const std::bad_alloc &) {
     return bad_alloc(b, "qp_ballot_box_cast");
@@ -441,12 +329,8 @@ int qp_ballot_box_cast(qp_ballot_box *b, struct qp_verifier *v, const uint8_t *c
 
 int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
   if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_reserve");
-  if (new_capacity > qb::MAX_CAPACITY || new_capacity < b->admitted() || !new_capacity) {
-    b->err = "qp_ballot_box_reserve: capacity " + std::to_string(new_capacity) + " for " + std::to_string(b->admitted()) +
-             " admitted ballots: it must hold them (and at least one) and be at most 2^31";
-    return QP_ERR_ARG;
-  }
+  if (b->dead) return dead_handle(b, "qp_ballot_box_reserve");
+  if (int rc = check_reserve(b, "qp_ballot_box_reserve", new_capacity)) return rc;
   if (new_capacity == b->cap()) return QP_OK;
   if (!b->ctx) {
     try {
@@ -454,8 +338,7 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
     } catch (const std::bad_alloc &) {
       return bad_alloc(b, "qp_ballot_box_reserve");
     }
-    b->hlog.drop();  // the log tree's layout is the capacity's: the next commit rebuilds it
-    b->committed = 0;
+    b->lc.drop();
     return QP_OK;
   }
   // a new log and table beside the old; the box moves over only once all of it succeeded
@@ -464,7 +347,7 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
   DeviceTables nt;
   qpk::BallotCounters now;
   QP_HIP_TRY(b, hipSetDevice(c->device));
-  const int rc = alloc_tables(b, new_capacity, nt);
+  const int rc = qba::alloc_tables({b->err}, s, new_capacity, nt);
   if (rc) return rc;
   const qpk::BallotDev od = b->t.dev(), nd = nt.dev();
   qpk::BallotCounters *ctr = b->d_ctr.as<qpk::BallotCounters>();
@@ -477,17 +360,12 @@ int qp_ballot_box_reserve(qp_ballot_box *b, uint64_t new_capacity) {
   }
   QP_HIP_TRY(b, hipMemcpyAsync(&now, ctr, sizeof now, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(b, hipStreamSynchronize(s));
-  if (now.err) {
-    b->dead = true;
-    b->err = "qp_ballot_box_reserve: the nullifier table's probe found no slot (an internal invariant broke)";
-    return QP_ERR_STATE;
-  }
+  if (now.err)
+    return device_step(b, refuse(b, b->BROKEN, "qp_ballot_box_reserve: the nullifier table's probe found no slot (an internal "
+                                               "invariant broke)"));
   b->t = std::move(nt);
   b->capacity = new_capacity;
-  // the log tree's layout is the capacity's: dropped here, rebuilt by the next
-  // commit from the copied log, which gives the same root
-  b->log.drop();
-  b->committed = 0;
+  b->lc.drop();
   return QP_OK;
 }
 
@@ -509,11 +387,7 @@ int qp_ballot_box_state(const qp_ballot_box *b, uint64_t *cast, uint64_t *admitt
 int qp_ballot_box_entries(qp_ballot_box *b, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
                           uint8_t *flags) {
   if (!b) return QP_ERR_ARG;
-  if (first > b->admitted() || k > b->admitted() - first) {
-    b->err = "qp_ballot_box_entries: entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
-             std::to_string(k) + ") are outside the log's " + std::to_string(b->admitted());
-    return QP_ERR_ARG;
-  }
+  if (int rc = check_range(b, "qp_ballot_box_entries", first, k)) return rc;
   if (!k) return QP_OK;
   if (!b->ctx) {
     if (nullifiers) memcpy(nullifiers, &b->host.nullifier[first * 4], k * 32);
@@ -551,19 +425,10 @@ int qp_ballot_box_recount(qp_ballot_box *b, uint64_t out[4]) {
 
 int qp_ballot_box_find(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
   if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_find");
+  if (b->dead) return dead_handle(b, "qp_ballot_box_find");
   if (!k) return QP_OK;
-  if (!nullifiers || !seq_out) {
-    b->err = "qp_ballot_box_find: null buffer";
-    return QP_ERR_ARG;
-  }
-  for (uint32_t i = 0; i < k; i++)
-    for (uint32_t f = 0; f < 4; f++)
-      if (nullifiers[(size_t)i * 4 + f] >= qb::P) {
-        b->err = "qp_ballot_box_find: nullifier at position " + std::to_string(i) + " felt " + std::to_string(f) +
-                 " is not a canonical field element";
-        return QP_ERR_ARG;
-      }
+  if (!nullifiers || !seq_out) return null_buffer(b, "qp_ballot_box_find");
+  if (int rc = canonical_keys(b, "qp_ballot_box_find", "nullifier", nullifiers, k)) return rc;
   if (!b->ctx) {
     for (uint32_t i = 0; i < k; i++) seq_out[i] = b->host.find(nullifiers + (size_t)i * 4);
     return QP_OK;
@@ -576,55 +441,20 @@ int qp_ballot_box_find(qp_ballot_box *b, const uint64_t *nullifiers, uint32_t k,
 }
 
 int qp_ballot_box_commit_log(qp_ballot_box *b, uint64_t root_out[4], uint64_t *n_out) {
-  if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_commit_log");
-  if (!b->admitted()) return empty_log(b, "qp_ballot_box_commit_log");
-  try {
-    const int rc = device_step(b, commit_log(b));
-    if (rc) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(b, "qp_ballot_box_commit_log");
-  }
-  if (root_out) memcpy(root_out, b->log_root, 32);
-  if (n_out) *n_out = b->committed;
-  return QP_OK;
+  return qph::commit_log(b, "qp_ballot_box_commit_log", commit, root_out, n_out);
 }
 
 int qp_ballot_box_receipts(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
                            uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out) {
-  if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_receipts");
-  if (!b->admitted()) return empty_log(b, "qp_ballot_box_receipts");
-  if (k && (!seqs || !siblings || !path_bits || !depth)) {
-    b->err = "qp_ballot_box_receipts: null buffer";
-    return QP_ERR_ARG;
-  }
-  int rc = check_seqs(b, "qp_ballot_box_receipts", seqs, k);
-  if (rc) return rc;
-  try {
-    if ((rc = device_step(b, commit_log(b)))) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(b, "qp_ballot_box_receipts");
-  }
-  if (root_out) memcpy(root_out, b->log_root, 32);
-  if (n_out) *n_out = b->committed;
-  if (!k) return QP_OK;
-  if (b->ctx) return device_step(b, receipts_device(b, seqs, k, siblings, path_bits, depth, leaves));
-  for (uint32_t i = 0; i < k; i++)
-    b->hlog.path(seqs[i], siblings + (size_t)i * qb::ACC_PATH_SLOTS * 4, path_bits + i, depth + i,
-                 leaves ? leaves + (size_t)i * 4 : nullptr);
-  return QP_OK;
+  return qph::receipts(b, "qp_ballot_box_receipts", commit, seqs, k, siblings, path_bits, depth, leaves, root_out, n_out);
 }
 
 int qp_ballot_box_entries_at(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers,
                              uint64_t *numbers, uint8_t *flags) {
   if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_entries_at");
+  if (b->dead) return dead_handle(b, "qp_ballot_box_entries_at");
   if (!k) return QP_OK;
-  if (!seqs) {
-    b->err = "qp_ballot_box_entries_at: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!seqs) return null_buffer(b, "qp_ballot_box_entries_at");
   const int rc = check_seqs(b, "qp_ballot_box_entries_at", seqs, k);
   if (rc) return rc;
   if (b->ctx) return device_step(b, entries_at_device(b, seqs, k, nullifiers, numbers, flags));
@@ -637,31 +467,7 @@ int qp_ballot_box_entries_at(qp_ballot_box *b, const uint64_t *seqs, uint32_t k,
 }
 
 int qp_ballot_box_roots_at(qp_ballot_box *b, const uint64_t *ms, uint32_t k, uint64_t *roots_out) {
-  if (!b) return QP_ERR_ARG;
-  if (b->dead) return dead_box(b, "qp_ballot_box_roots_at");
-  if (!b->admitted()) return empty_log(b, "qp_ballot_box_roots_at");
-  if (k && (!ms || !roots_out)) {
-    b->err = "qp_ballot_box_roots_at: null buffer";
-    return QP_ERR_ARG;
-  }
-  for (uint32_t i = 0; i < k; i++)
-    if (!ms[i] || ms[i] > b->admitted()) {
-      b->err = "qp_ballot_box_roots_at: size " + std::to_string(ms[i]) + " (position " + std::to_string(i) +
-               ") is outside 1.." + std::to_string(b->admitted()) + ", the sizes the log has had";
-      return QP_ERR_ARG;
-    }
-  try {
-    if (int rc = device_step(b, commit_log(b))) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(b, "qp_ballot_box_roots_at");
-  }
-  if (!k) return QP_OK;
-  if (b->ctx) {
-    QP_HIP_TRY(b, hipSetDevice(b->ctx->device));
-    return device_step(b, b->log.prefix_roots({b->err}, b->ctx->stream, ms, k, roots_out));
-  }
-  for (uint32_t i = 0; i < k; i++) b->hlog.prefix_root(ms[i], qb::log_node, roots_out + (size_t)i * 4);
-  return QP_OK;
+  return qph::roots_at(b, "qp_ballot_box_roots_at", commit, qb::log_node, ms, k, roots_out);
 }
 
 int qp_ballot_box_restore(qp_ctx *c, const uint64_t proposal_id[4], const uint64_t *roots, uint32_t nroots,
@@ -699,7 +505,9 @@ int qp_ballot_box_restore(qp_ctx *c, const uint64_t proposal_id[4], const uint64
       const qpk::BallotDev d = b->t.dev();
       // With an expected root the audit builds the log tree for n leaves in `tree`, and the tree is discarded
       // on purpose: a restored box has committed nothing yet, and its own tree is laid out for the capacity,
-      // not for n, by the first commit_log (which hashes these leaves again).
+      // not for n, by the first commit_log (which hashes these leaves again).  qp_ledger_restore instead
+      // commits the restored ledger's own tree and keeps it; the two are left as they are, since making
+      // them one changes what a commit_log after a restore launches.
       AccTree tree;
       auto device_restore = [&]() -> int {
         QP_HIP_TRY(b, hipSetDevice(c->device));

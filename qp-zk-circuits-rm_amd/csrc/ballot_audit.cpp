@@ -1,8 +1,9 @@
 // ballot_audit.cpp — qp_ballot_log_audit (qpgpu.h), and the device path of the
 // audit that it and qp_ballot_box_restore (ballot.cpp) share.  An audit needs no
-// box: with a context the log is uploaded into buffers of this call's own, a
-// fresh table takes it whole, and the verdict is ballot_audit.h's, the same the
-// host path reaches.
+// box: with a context the log is uploaded into tables of this call's own
+// (ballot_audit_device.h's DeviceTables), the fresh table takes it whole, the
+// tree is log_commit.h's whole-log form, and the verdict is ballot_audit.h's,
+// the same the host path reaches.
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <new>
@@ -10,6 +11,7 @@
 #include <vector>
 #include "ballot_audit.h"
 #include "ballot_audit_device.h"
+#include "log_commit.h"
 
 static_assert(sizeof(qp_audit_report) == sizeof(qb::AuditReport) && sizeof(qb::AuditReport) == 80, "qp_audit_report layout");
 static_assert(QP_AUDIT_OK == qb::AUDIT_OK && QP_AUDIT_NON_CANONICAL == qb::AUDIT_NON_CANONICAL &&
@@ -48,13 +50,8 @@ int audit_facts_device(qp_ctx *c, AccErr e, const qpk::BallotDev &d, uint64_t n,
   QP_HIP_TRY(&e, hipGetLastError());
   qpk::AccLevels lv;
   if (tree) {
-    if (int rc = tree->alloc(e, n)) return rc;
-    qpk::acc_levels_reserved(n, n, lv);
-    qpk::ballot_leaves(d, 0, (uint32_t)n, tree->dig.p, &rep->ctr, s);
-    QP_HIP_TRY(&e, hipGetLastError());
-    tree->append(lv, qpk::acc_row_max(), s);  // from an empty tree: every level
-    QP_HIP_TRY(&e, hipGetLastError());
-    QP_HIP_TRY(&e, hipMemcpyAsync(f.root, tree->root(lv), 32, hipMemcpyDeviceToHost, s));
+    auto leaves = [&](uint32_t first, uint32_t end, uint64_t *dig) { qpk::ballot_leaves(d, first, end, dig, &rep->ctr, s); };
+    if (int rc = log_tree_whole(e, s, *tree, n, leaves, lv, f.root)) return rc;
   }
   QP_HIP_TRY(&e, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(&e, hipStreamSynchronize(s));
@@ -88,17 +85,12 @@ int audit_device(qp_ctx *c, const uint64_t *nullifiers, const uint64_t *numbers,
   hipStream_t s = c->stream;
   AccErr e{c->err};
   QP_HIP_TRY(c, hipSetDevice(c->device));
-  DevBuf nul, num, fl, slot;
-  const uint64_t S = qb::table_slots(n);
-  QP_HIP_TRY(c, nul.alloc((size_t)n * 4));
-  QP_HIP_TRY(c, num.alloc((size_t)n));
-  QP_HIP_TRY(c, fl.alloc((size_t)((n + 7) / 8)));
-  QP_HIP_TRY(c, slot.alloc((size_t)(S / 2)));
-  const qpk::BallotDev d{nul.p, num.p, fl.as<uint8_t>(), slot.as<uint32_t>(), S - 1};
-  QP_HIP_TRY(c, hipMemsetAsync(slot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(nul.p, nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(num.p, numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(fl.p, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  qba::DeviceTables t;
+  if (int rc = qba::alloc_tables(e, s, n, t)) return rc;
+  const qpk::BallotDev d = t.dev();
+  QP_HIP_TRY(c, hipMemcpyAsync(d.nullifier, nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(c, hipMemcpyAsync(d.number, numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(c, hipMemcpyAsync(d.flags, flags, (size_t)n, hipMemcpyHostToDevice, s));
   AccTree tree;
   qb::AuditFacts f;
   bool canonical = false;
@@ -109,24 +101,9 @@ int audit_device(qp_ctx *c, const uint64_t *nullifiers, const uint64_t *numbers,
     return QP_OK;
   }
   // the prefix roots of the commitments that name a prefix, in one batch, once no earlier reason fired
-  std::vector<uint64_t> ms, got;
-  std::vector<uint32_t> at(claims.ncommit, 0);
-  bool asked = false;
-  auto prefix_root = [&](uint32_t i, uint64_t, uint64_t out[4]) {
-    if (!asked) {
-      asked = true;
-      for (uint32_t j = 0; j < claims.ncommit; j++)
-        if (claims.commit_ns[j] <= n) {
-          at[j] = (uint32_t)ms.size();
-          ms.push_back(claims.commit_ns[j]);
-        }
-      got.assign(ms.size() * 4, 0);
-      rc = tree.prefix_roots(e, s, ms.data(), (uint32_t)ms.size(), got.data());
-    }
-    memcpy(out, &got[(size_t)at[i] * 4], 32);
-  };
-  qb::audit_verdict(f, n, claims, qb::AUDIT_ALL_REASONS, prefix_root, r);
-  return rc;
+  PrefixRootBatch roots{tree, e, s, claims.commit_ns, claims.ncommit, n};
+  qb::audit_verdict(f, n, claims, qb::AUDIT_ALL_REASONS, [&roots](uint32_t i, uint64_t, uint64_t out[4]) { roots.get(i, out); }, r);
+  return roots.rc;
 }
 
 int refuse(qp_ctx *c, const std::string &why) {

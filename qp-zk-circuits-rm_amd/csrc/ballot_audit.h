@@ -1,8 +1,10 @@
 // ballot_audit.h — the audit of a published ballot log in host C++: the seven
 // reasons and their witnesses, the verdict both paths share, and the host path
 // itself (HostBox's probe gives the owner, HostLog the root and the prefix
-// roots).  Plain C++ next to ballot_log.h (no HIP).  Included by ballot.cpp,
-// ballot_audit.cpp and the stand-alone check tools/ballot_audit_check.cpp.
+// roots).  The commitment claims, a restore's refusals and the text of a failing
+// audit are audit_common.h's, shared with the transfer log.  Plain C++ next to
+// ballot_log.h (no HIP).  Included by ballot.cpp, ballot_audit.cpp and the
+// stand-alone check tools/ballot_audit_check.cpp.
 //
 // Definitions (DESIGN §13 and qpgpu.h state the same):
 //   A published log is what qp_ballot_box_entries returns: nullifiers[n][4],
@@ -37,6 +39,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "audit_common.h"
 #include "ballot_log.h"
 
 namespace qb {
@@ -44,7 +47,12 @@ namespace qb {
 // qp_audit_status (qpgpu.h)
 enum : uint32_t { AUDIT_OK = 0, AUDIT_NON_CANONICAL = 1, AUDIT_ORDER = 2, AUDIT_COUNT_RULE = 3, AUDIT_TALLY = 4,
                   AUDIT_ROOT = 5, AUDIT_COMMITMENT = 6 };
-constexpr uint64_t AUDIT_NONE = ~0ull;  // no witness, no first
+using qpk::AUDIT_NONE;
+
+// the nouns of a box's texts, stated once: qp_ballot_box (ballot.cpp) inherits them for handle_common.h's
+struct Words {
+  static constexpr const char *HANDLE = "box", *ENTRY = "ballot", *ABI = "qp_ballot_box";
+};
 
 // qp_audit_report
 struct AuditReport {
@@ -107,18 +115,10 @@ inline void audit_verdict(const AuditFacts &f, uint64_t n, const AuditClaims &c,
   } else if (on(AUDIT_ROOT) && c.root && memcmp(c.root, f.root, 32)) {
     r.status = AUDIT_ROOT;
   } else if (on(AUDIT_COMMITMENT)) {
-    for (uint32_t i = 0; i < c.ncommit; i++) {
-      uint64_t got[4];
-      bool holds = c.commit_ns[i] <= n;
-      if (holds) {
-        prefix_root(i, c.commit_ns[i], got);
-        holds = !memcmp(got, c.commit_roots + (size_t)i * 4, 32);
-      }
-      if (!holds) {
-        r.status = AUDIT_COMMITMENT;
-        r.witness = i;
-        return;
-      }
+    const uint64_t i = qpk::broken_commitment(c.commit_roots, c.commit_ns, c.ncommit, n, prefix_root);
+    if (i != AUDIT_NONE) {
+      r.status = AUDIT_COMMITMENT;
+      r.witness = i;
     }
   }
 }
@@ -129,13 +129,7 @@ constexpr uint32_t AUDIT_ALL_REASONS = 0x7E, AUDIT_RESTORE_REASONS = 1u << AUDIT
 inline std::string audit_refusal(uint64_t n, const AuditClaims &c) {
   if (!n || n > MAX_CAPACITY) return "a log of " + std::to_string(n) + " entries: an audit takes 1 to 2^31";
   if (c.root && !canonical(c.root, 4)) return "the claimed root is not four canonical field elements";
-  if (c.ncommit && (!c.commit_roots || !c.commit_ns)) return "null commitment buffer";
-  for (uint32_t i = 0; i < c.ncommit; i++) {
-    if (!c.commit_ns[i]) return "commitment " + std::to_string(i) + " names n = 0";
-    if (!canonical(c.commit_roots + (size_t)i * 4, 4))
-      return "the root of commitment " + std::to_string(i) + " is not four canonical field elements";
-  }
-  return "";
+  return qpk::commitment_refusal(c.commit_roots, c.commit_ns, c.ncommit);
 }
 
 // the first pass of the host path: the lowest non-canonical entry, the lowest entry out of order
@@ -198,23 +192,12 @@ inline void audit_host(const uint64_t *nullifiers, const uint64_t *numbers, cons
 
 // what a restore refuses beside a failing audit: "" when (capacity, cast_count) fit the log
 inline std::string restore_refusal(const uint64_t *numbers, uint64_t n, uint64_t capacity, uint64_t cast_count) {
-  if (n > MAX_CAPACITY) return "a log of " + std::to_string(n) + " entries: a box holds at most 2^31";
-  if (!capacity || capacity > MAX_CAPACITY || capacity < n)
-    return "capacity " + std::to_string(capacity) + " for a log of " + std::to_string(n) +
-           " entries: it must hold them (and at least one) and be at most 2^31";
-  if (n && cast_count <= numbers[n - 1])
-    return "cast_count " + std::to_string(cast_count) + " is not above the log's last ballot number " +
-           std::to_string(numbers[n - 1]);
-  return "";
+  return qpk::restore_refusal(numbers, n, capacity, cast_count, Words::HANDLE, Words::ENTRY);
 }
 
 // the reason and the witness of a failing audit, for a refusal's message
 inline std::string audit_failure_text(const AuditReport &r) {
-  std::string s = std::string("the log fails its audit: ") + audit_status_text(r.status);
-  if (r.witness != AUDIT_NONE) s += (r.status == AUDIT_COMMITMENT ? " (commitment " : " (entry ") + std::to_string(r.witness);
-  if (r.first != AUDIT_NONE) s += ", its nullifier first at entry " + std::to_string(r.first);
-  if (r.witness != AUDIT_NONE) s += ")";
-  return s;
+  return qpk::audit_failure_text(audit_status_text(r.status), r.witness, r.first, r.status == AUDIT_COMMITMENT);
 }
 
 }  // namespace qb

@@ -6,10 +6,13 @@
 // the device (ledger.hip); without one the same semantics run on the host
 // (ql::HostLedger).  Both paths state the checks once, in ledger_table.h.
 // The log commitment (commit_log, receipts, entries_at, roots_at and the
-// receipt check: ledger_log.h) is brought up to date on demand; a cast does
-// not touch it, and the tree is allocated by the first commit only.
+// receipt check: ledger_log.h) is the ledger's LogCommit (log_commit.h), brought
+// up to date on demand; a cast does not touch it, and the tree is allocated by
+// the first commit only.  The refusals worded alike for the ledger and the
+// ballot box are handle_common.h's; what is stated here is the ledger's own.
 // qp_ledger_restore reopens a ledger from a published log through the audit's
-// passes (ledger_audit.h) over the new ledger's own buffers;
+// passes (ledger_audit.h; on the device qla::audit_screen_insert_resolve,
+// shared with qp_ledger_log_audit) over the new ledger's own buffers;
 // qp_ledger_payouts_between is a payout round over the ledger's log
 // (ledger_rounds.h; the device launches are ledger_rounds.cpp's).
 #include "../../include/qpgpu.h"
@@ -22,12 +25,14 @@
 #include <vector>
 #include "acc_tree.h"
 #include "ctx.h"
+#include "handle_common.h"
 #include "ledger_audit.h"
 #include "ledger_audit_device.h"
 #include "ledger_kernels.h"
 #include "ledger_log.h"
 #include "ledger_rounds.h"
 #include "ledger_table.h"
+#include "log_commit.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_transfer_result) == sizeof(ql::Result) && sizeof(ql::Result) == 24 &&
@@ -43,26 +48,17 @@ static_assert(QP_RECEIPT_OK == ql::RECEIPT_OK && QP_RECEIPT_SHAPE == ql::RECEIPT
                   QP_RECEIPT_NULL == ql::RECEIPT_NULL,
               "qp_receipt_status and ledger_log.h differ");
 
-namespace {
-// the device half of a ledger for one capacity: the log, the two tables, the sums
-struct LedgerTables {
-  DevBuf nul, num, amt, acc, flags, astay, nslot, aslot, sum;
-  uint64_t mask = 0;
-  qpk::LedgerDev dev() const {
-    return qpk::LedgerDev{nul.p,          num.p,
-                          amt.as<uint32_t>(),   acc.p,
-                          flags.as<uint8_t>(),  astay.as<uint32_t>(),
-                          nslot.as<uint32_t>(), aslot.as<uint32_t>(),
-                          sum.as<unsigned long long>(), mask};
-  }
-};
+using namespace qph;
+using qla::LedgerTables;
 
+namespace {
 // entries per launch of the lookups and gathers (their buffers hold this many)
 constexpr uint32_t QUERY_BATCH = 8192;
 }  // namespace
 
-struct qp_ledger {
-  qp_ctx *ctx = nullptr;  // null: the host path
+struct qp_ledger : ql::Words {
+  static constexpr int BROKEN = QP_ERR_HIP;  // what a broken invariant returns (the box: QP_ERR_STATE)
+  qp_ctx *ctx = nullptr;                     // null: the host path
   std::string err;
   bool dead = false;  // a device step failed part-way, or the defensive error word was set: no further calls
   ql::Screen screen;
@@ -81,11 +77,7 @@ struct qp_ledger {
   DevBuf d_q, d_qsum, d_qaux;                       // per lookup / gather batch (QUERY_BATCH entries)
   TimingEvents<3> ev;                               // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
-  // ---- the log commitment, both paths: built by the first commit, dropped by reserve
-  ql::HostLog hlog;
-  AccTree log;             // the device path's log tree, laid out for `capacity`; `committed` leaves
-  uint64_t committed = 0;  // leaves of the tree = the n of (log_root, n)
-  uint64_t log_root[4] = {0, 0, 0, 0};
+  LogCommit<ql::HostLog> lc;               // the log commitment, both paths
   DevBuf d_gacc, d_gnum, d_gamt, d_gflag;  // per entries_at batch, beside d_q (the seqs) and d_qsum (the nullifiers)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
@@ -94,74 +86,29 @@ struct qp_ledger {
 };
 
 namespace {
-thread_local std::string g_new_err;  // why the last qp_ledger_new on this thread was refused
+// why the last qp_ledger_new (restore, log_audit, log_payouts_between) on this thread was refused
+thread_local HandlelessError g_new_err;
 
 int refuse_new(qp_ctx *c, const std::string &why) {
-  g_new_err = "qp_ledger_new: " + why;
-  if (c) c->err = g_new_err;
+  g_new_err.set(c, "qp_ledger_new: " + why);
   return QP_ERR_ARG;
 }
-
 }  // namespace
 
-void qla::set_ledgerless_error(qp_ctx *c, const std::string &why) {
-  g_new_err = why;
-  if (c) c->err = why;
-}
+void qla::set_ledgerless_error(qp_ctx *c, const std::string &why) { g_new_err.set(c, why); }
 
 namespace {
-int alloc_tables(qp_ledger *l, uint64_t capacity, LedgerTables &t) {
-  const uint64_t S = ql::table_slots(capacity);
-  hipStream_t s = l->ctx->stream;
-  QP_HIP_TRY(l, t.nul.alloc(capacity * 4));
-  QP_HIP_TRY(l, t.num.alloc(capacity));
-  QP_HIP_TRY(l, t.amt.alloc(capacity * 2));
-  QP_HIP_TRY(l, t.acc.alloc(capacity * 4));
-  QP_HIP_TRY(l, t.flags.alloc((capacity + 7) / 8));
-  QP_HIP_TRY(l, t.astay.alloc((capacity + 1) / 2));
-  QP_HIP_TRY(l, t.nslot.alloc(S / 2));
-  QP_HIP_TRY(l, t.aslot.alloc(S / 2));
-  QP_HIP_TRY(l, t.sum.alloc(S * 4));
-  t.mask = S - 1;
-  QP_HIP_TRY(l, hipMemsetAsync(t.nslot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(l, hipMemsetAsync(t.aslot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(l, hipMemsetAsync(t.sum.p, 0, S * 32, s));
-  return QP_OK;
-}
-
-int dead_ledger(qp_ledger *l, const char *fn) {
-  l->err = std::string(fn) + ": an earlier call on this ledger failed on the device part-way; its state is not known";
-  return QP_ERR_STATE;
-}
-
-int bad_alloc(qp_ledger *l, const char *fn) {
-  l->err = std::string(fn) + ": out of host memory";
-  return QP_ERR_OOM;
-}
-
-// a failed device step leaves the ledger dead
-int device_step(qp_ledger *l, int rc) {
-  if (rc) l->dead = true;
-  return rc;
-}
-
 // the defensive error word after a launch (copied by the caller, stream synchronised)
 int error_word(qp_ledger *l, const char *fn, uint32_t err) {
   if (!err) return QP_OK;
-  l->err = std::string(fn) +
-           (err & 1 ? ": the nullifier table's probe found no slot"
-                    : err & 2 ? ": a nullifier slot holds a later entry than the one that stopped at it"
-                              : err & 4 ? ": the account table's probe found no slot"
-                                        : err & 8 ? ": a table slot holds no log entry"
-                                                  : ": a transfer number in the log is not a field element") +
-           " (an internal invariant broke)";
-  return QP_ERR_HIP;
-}
-
-int over_capacity(qp_ledger *l, const char *fn, uint64_t k) {
-  l->err = std::string(fn) + ": " + std::to_string(l->admitted()) + " + " + std::to_string(k) +
-           " admitted transfers exceed the capacity " + std::to_string(l->cap()) + "; call qp_ledger_reserve first";
-  return QP_ERR_ARG;
+  return refuse(l, l->BROKEN,
+                std::string(fn) +
+                    (err & 1 ? ": the nullifier table's probe found no slot"
+                             : err & 2 ? ": a nullifier slot holds a later entry than the one that stopped at it"
+                                       : err & 4 ? ": the account table's probe found no slot"
+                                                 : err & 8 ? ": a table slot holds no log entry"
+                                                           : ": a transfer number in the log is not a field element") +
+                    " (an internal invariant broke)");
 }
 
 int upload_roots(qp_ledger *l) {
@@ -218,10 +165,9 @@ int cast_device(qp_ledger *l, const char *fn, const uint64_t *pis, const uint32_
   QP_HIP_TRY(l, hipGetLastError());
   QP_HIP_TRY(l, hipMemcpyAsync(&k, blk + nb, 4, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(l, hipStreamSynchronize(s));
-  if (k > n) {
-    l->err = std::string(fn) + ": the pack's scan counted more admitted transfers than were cast (an internal invariant broke)";
-    return QP_ERR_HIP;
-  }
+  if (k > n)
+    return refuse(l, l->BROKEN, std::string(fn) + ": the pack's scan counted more admitted transfers than were cast (an "
+                                                  "internal invariant broke)");
   if (k > l->capacity - l->count) {
     *refused = true;
     return over_capacity(l, fn, k);
@@ -342,11 +288,9 @@ int payees_device(qp_ledger *l) {
     QP_HIP_TRY(l, hipGetLastError());
     QP_HIP_TRY(l, hipMemcpyAsync(&total, blk + nb, 4, hipMemcpyDeviceToHost, s));
     QP_HIP_TRY(l, hipStreamSynchronize(s));
-    if (total != l->accounts) {
-      l->err = "qp_ledger_payouts: " + std::to_string(total) + " entries own an account slot, the ledger counts " +
-               std::to_string(l->accounts) + " accounts (an internal invariant broke)";
-      return QP_ERR_HIP;
-    }
+    if (total != l->accounts)
+      return refuse(l, l->BROKEN, "qp_ledger_payouts: " + std::to_string(total) + " entries own an account slot, the ledger counts " +
+                                      std::to_string(l->accounts) + " accounts (an internal invariant broke)");
   }
   l->payee_valid = true;
   return QP_OK;
@@ -378,7 +322,7 @@ int reserve_device(qp_ledger *l, uint64_t new_capacity) {
   LedgerTables nt;
   qpk::LedgerCounters now;
   QP_HIP_TRY(l, hipSetDevice(c->device));
-  if (int rc = alloc_tables(l, new_capacity, nt)) return rc;
+  if (int rc = qla::alloc_tables({l->err}, s, new_capacity, nt)) return rc;
   const qpk::LedgerDev od = l->t.dev(), nd = nt.dev();
   qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
   if (l->count) {
@@ -397,106 +341,49 @@ int reserve_device(qp_ledger *l, uint64_t new_capacity) {
   l->t = std::move(nt);
   l->capacity = new_capacity;
   l->payee_valid = false;  // the payees are the same entries, but the list is cheap and this keeps one rule
-  // the log tree's layout is the capacity's: dropped here, rebuilt by the next commit from the copied
-  // log, which gives the same root
-  l->log.drop();
-  l->committed = 0;
+  l->lc.drop();
   return QP_OK;
 }
 
-// the log tree up to the admitted count (> 0; the caller checks): leaves [committed, count), the
-// levels above them, the root
-int commit_device(qp_ledger *l) {
-  hipStream_t s = l->ctx->stream;
-  if (l->committed == l->count) return QP_OK;
-  QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
-  if (!l->log.dig.p)
-    if (int rc = l->log.alloc({l->err}, l->capacity)) return rc;
-  qpk::AccLevels lv;
-  if (!qpk::acc_levels_reserved(l->count, l->capacity, lv)) {
-    l->err = "qp_ledger_commit_log: the log does not fit its capacity (an internal invariant broke)";
-    return QP_ERR_HIP;
-  }
+// the log commitment up to the admitted count (> 0; the caller checks), on either path
+int commit(qp_ledger *l) {
+  const char *fn = "qp_ledger_commit_log";
+  if (!l->ctx) return l->lc.commit(l->host) ? QP_OK : error_word(l, fn, qpk::LEDGER_ERR_NUMBER);
   qpk::LedgerCounters *ctr = l->d_ctr.as<qpk::LedgerCounters>();
-  uint64_t root[4];
-  uint32_t err = 0;
-  qpk::ledger_leaves(l->t.dev(), (uint32_t)l->committed, (uint32_t)l->count, l->log.dig.p, ctr, s);
-  QP_HIP_TRY(l, hipGetLastError());
-  l->log.append(lv, qpk::acc_row_max(), s);  // the tree holds `committed` leaves
-  QP_HIP_TRY(l, hipGetLastError());
-  QP_HIP_TRY(l, hipMemcpyAsync(root, l->log.root(lv), 32, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(l, hipMemcpyAsync(&err, &ctr->err, 4, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(l, hipStreamSynchronize(s));
-  if (int rc = error_word(l, "qp_ledger_commit_log", err)) return rc;
-  memcpy(l->log_root, root, 32);
-  l->log.lv = lv;
-  l->committed = l->count;
-  return QP_OK;
-}
-
-// commit on either path; the caller checked that the log is not empty
-int commit_log(qp_ledger *l) {
-  if (l->ctx) return commit_device(l);
-  if (!l->hlog.commit(l->host)) return error_word(l, "qp_ledger_commit_log", qpk::LEDGER_ERR_NUMBER);
-  memcpy(l->log_root, l->hlog.root(), 32);
-  l->committed = l->hlog.n;
-  return QP_OK;
+  auto leaves = [&](uint32_t first, uint32_t end, uint64_t *dig) {
+    qpk::ledger_leaves(l->t.dev(), first, end, dig, ctr, l->ctx->stream);
+  };
+  uint32_t word = 0;
+  if (int rc = l->lc.commit(l->ctx, l->err, fn, l->BROKEN, l->count, l->capacity, leaves, &ctr->err, &word)) return rc;
+  return error_word(l, fn, word);
 }
 
 // The device half of a restore, over the fresh ledger's own log and tables (sized for its capacity):
-// one upload of the log; the audit's screen; a synchronise, where a non-canonical log ends (*canonical
-// false, nothing inserted or hashed); the whole-log insert into the nullifier table; the audit's
-// resolve, a launch of its own, which reads the final slot words for the credit rule and credits the
-// flagged entries into the account table and the sums.  What those launches leave is a live ledger's
-// state (both tables, astay, the sums), so no kernel of the restore's own is needed; the counts go from
-// the audit's report into the ledger's counters.  The root, when one is expected, is the restored
-// ledger's own commit afterwards.
+// the audit's passes up to its resolve (ledger_audit_device.h), then this call's own synchronise.  What
+// those launches leave is a live ledger's state (both tables, astay, the sums), so no kernel of the
+// restore's own is needed; the counts go from the audit's report into the ledger's counters.  The
+// root, when one is expected, is the restored ledger's own commit afterwards.
 int restore_device(qp_ledger *l, const ql::AuditLog &g, ql::AuditFacts &f, bool *canonical) {
   qp_ctx *c = l->ctx;
   hipStream_t s = c->stream;
   const uint64_t n = g.n;
-  const qpk::LedgerDev d = l->t.dev();
-  DevBuf d_rep, d_stay;
+  qla::AuditPasses a;
+  const qpk::LedgerAuditDev &h = a.h;
+  bool screened = false;
   *canonical = false;
   QP_HIP_TRY(l, hipSetDevice(c->device));
-  QP_HIP_TRY(l, d_rep.alloc((sizeof(qpk::LedgerAuditDev) + 7) / 8));
-  QP_HIP_TRY(l, d_stay.alloc((size_t)((n + 1) / 2)));
-  QP_HIP_TRY(l, hipMemcpyAsync(d.nullifier, g.nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(l, hipMemcpyAsync(d.number, g.numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(l, hipMemcpyAsync(d.amount, g.amounts, (size_t)n * 16, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(l, hipMemcpyAsync(d.account, g.accounts, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(l, hipMemcpyAsync(d.flags, g.flags, (size_t)n, hipMemcpyHostToDevice, s));
-  qpk::LedgerAuditDev *rep = d_rep.as<qpk::LedgerAuditDev>();
-  qpk::LedgerAuditDev h;
-  memset(&h, 0, sizeof h);
-  h.credit_rule = ~0ull;
-  h.non_canonical = h.order = h.payout = qpk::LEDGER_AUDIT_NO_SEQ;
-  QP_HIP_TRY(l, hipMemcpyAsync(rep, &h, sizeof h, hipMemcpyHostToDevice, s));
-  qpk::ledger_audit_screen(d, (uint32_t)n, rep, s);
-  QP_HIP_TRY(l, hipGetLastError());
-  QP_HIP_TRY(l, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(l, hipStreamSynchronize(s));
-  if (h.non_canonical != qpk::LEDGER_AUDIT_NO_SEQ) {
+  if (int rc = qla::audit_screen_insert_resolve({l->err}, s, g, l->t.dev(), a, &screened)) return rc;
+  if (!screened) {
     f.non_canonical = h.non_canonical;
     return QP_OK;
   }
-  qpk::ledger_insert(d, 0, (uint32_t)n, d_stay.as<uint32_t>(), &rep->ctr, s);
-  QP_HIP_TRY(l, hipGetLastError());
-  qpk::ledger_audit_resolve(d, (uint32_t)n, d_stay.as<uint32_t>(), rep, s);
-  QP_HIP_TRY(l, hipGetLastError());
-  QP_HIP_TRY(l, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(l, hipMemcpyAsync(&a.h, a.rep(), sizeof h, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(l, hipStreamSynchronize(s));
   if (int rc = error_word(l, "qp_ledger_restore", h.ctr.err)) return rc;
-  if (h.ctr.credited > n || h.ctr.accounts > h.ctr.credited) {
-    l->err = "qp_ledger_restore: the resolve counted more credited entries or accounts than the log has (an internal "
-             "invariant broke)";
-    return QP_ERR_HIP;
-  }
-  if (h.order != qpk::LEDGER_AUDIT_NO_SEQ) f.order = h.order;
-  if (h.credit_rule != ~0ull) {
-    f.credit_rule = h.credit_rule >> 32;
-    f.first = h.credit_rule & 0xFFFFFFFFu;
-  }
+  if (h.ctr.credited > n || h.ctr.accounts > h.ctr.credited)
+    return refuse(l, l->BROKEN, "qp_ledger_restore: the resolve counted more credited entries or accounts than the log has (an "
+                                "internal invariant broke)");
+  a.rule_facts(f);
   f.credited = h.ctr.credited;
   f.accounts = h.ctr.accounts;
   const qpk::LedgerCounters now{h.ctr.credited, h.ctr.accounts, 0, 0};
@@ -540,32 +427,6 @@ int entries_at_device(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *
   return QP_OK;
 }
 
-// seqs[k] all inside the log, or QP_ERR_ARG naming the first that is not
-int check_seqs(qp_ledger *l, const char *fn, const uint64_t *seqs, uint32_t k) {
-  for (uint32_t i = 0; i < k; i++)
-    if (seqs[i] >= l->admitted()) {
-      l->err = std::string(fn) + ": entry " + std::to_string(seqs[i]) + " (position " + std::to_string(i) +
-               ") is outside the log's " + std::to_string(l->admitted());
-      return QP_ERR_ARG;
-    }
-  return QP_OK;
-}
-
-int empty_log(qp_ledger *l, const char *fn) {
-  l->err = std::string(fn) + ": empty log (no transfer has been admitted yet)";
-  return QP_ERR_STATE;
-}
-
-int canonical_keys(qp_ledger *l, const char *fn, const char *what, const uint64_t *keys, uint32_t k) {
-  for (uint32_t i = 0; i < k; i++)
-    for (uint32_t f = 0; f < 4; f++)
-      if (keys[(size_t)i * 4 + f] >= ql::P) {
-        l->err = std::string(fn) + ": " + what + " at position " + std::to_string(i) + " felt " + std::to_string(f) +
-                 " is not a canonical field element";
-        return QP_ERR_ARG;
-      }
-  return QP_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -598,13 +459,13 @@ int qp_ledger_new(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const uint6
       return QP_OK;
     }
   } catch (const std::bad_alloc &) {
-    g_new_err = "qp_ledger_new: out of host memory";
+    g_new_err.text = "qp_ledger_new: out of host memory";
     return QP_ERR_OOM;
   }
   int rc = QP_OK;
   auto device_open = [&]() -> int {
     QP_HIP_TRY(l, hipSetDevice(c->device));
-    if ((rc = alloc_tables(l.get(), capacity, l->t))) return rc;
+    if ((rc = qla::alloc_tables({l->err}, c->stream, capacity, l->t))) return rc;
     QP_HIP_TRY(l, l->d_roots.alloc((size_t)ql::MAX_ROOTS * 4));
     QP_HIP_TRY(l, l->d_ctr.alloc((sizeof(qpk::LedgerCounters) + 7) / 8));
     QP_HIP_TRY(l, l->d_audit.alloc(6));
@@ -612,7 +473,7 @@ int qp_ledger_new(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const uint6
     return upload_roots(l.get());
   };
   if ((rc = device_open())) {
-    g_new_err = c->err = "qp_ledger_new: " + l->err;
+    g_new_err.set(c, "qp_ledger_new: " + l->err);
     return rc;
   }
   l->capacity = capacity;
@@ -626,11 +487,11 @@ void qp_ledger_free(qp_ledger *l) {
   delete l;
 }
 
-const char *qp_ledger_last_error(const qp_ledger *l) { return l ? l->err.c_str() : g_new_err.c_str(); }
+const char *qp_ledger_last_error(const qp_ledger *l) { return l ? l->err.c_str() : g_new_err.text.c_str(); }
 
 int qp_ledger_accept_root(qp_ledger *l, const uint64_t root[4]) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_accept_root");
+  if (l->dead) return dead_handle(l, "qp_ledger_accept_root");
   if (!root || !ql::canonical(root, 4)) {
     l->err = "qp_ledger_accept_root: the root must be four canonical field elements";
     return QP_ERR_ARG;
@@ -651,16 +512,13 @@ int qp_ledger_accept_root(qp_ledger *l, const uint64_t root[4]) {
 int qp_ledger_cast_public(qp_ledger *l, const uint64_t *pis, const uint32_t *verdicts, uint32_t n,
                           qp_transfer_result *out) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_cast_public");
+  if (l->dead) return dead_handle(l, "qp_ledger_cast_public");
   if (!n) return QP_OK;
   if (n > ql::MAX_BATCH) {
     l->err = "qp_ledger_cast_public: " + std::to_string(n) + " transfers in one call; the most is 2^22";
     return QP_ERR_ARG;
   }
-  if (!pis || !out) {
-    l->err = "qp_ledger_cast_public: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!pis || !out) return null_buffer(l, "qp_ledger_cast_public");
   try {
     return cast_screened(l, "qp_ledger_cast_public", pis, verdicts, n, reinterpret_cast<ql::Result *>(out));
   } catch (const std::bad_alloc &) {
@@ -671,34 +529,18 @@ int qp_ledger_cast_public(qp_ledger *l, const uint64_t *pis, const uint32_t *ver
 int qp_ledger_cast(qp_ledger *l, struct qp_verifier *v, const uint8_t *const *proofs, const size_t *lens, uint32_t n,
                    qp_transfer_result *out) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_cast");
-  const uint32_t npi = qv::public_input_count(v);
-  if (npi != ql::NPI) {
-    l->err = !v ? "qp_ledger_cast: null verifier"
-                : !npi ? "qp_ledger_cast: the verifier is not usable"
-                       : "qp_ledger_cast: the verifier's circuit has " + std::to_string(npi) +
-                             " public inputs; the Wormhole circuit's has " + std::to_string(ql::NPI);
-    return QP_ERR_ARG;
-  }
+  if (l->dead) return dead_handle(l, "qp_ledger_cast");
+  if (int rc = check_verifier(l, "qp_ledger_cast", v, ql::NPI, "the Wormhole circuit's")) return rc;
   if (!n) return QP_OK;
   if (n > ql::MAX_BATCH) {
     l->err = "qp_ledger_cast: " + std::to_string(n) + " transfers in one call; the most is 2^22";
     return QP_ERR_ARG;
   }
-  if (!proofs || !lens || !out) {
-    l->err = "qp_ledger_cast: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!proofs || !lens || !out) return null_buffer(l, "qp_ledger_cast");
   try {
-    std::vector<uint32_t> verdicts(n);
-    const int rc = qp_verifier_verify(v, proofs, lens, n, verdicts.data());
-    if (rc) {
-      l->err = std::string("qp_ledger_cast: qp_verifier_verify: ") + qp_verifier_last_error(v);
-      return rc;
-    }
-    std::vector<uint64_t> pis((size_t)n * ql::NPI, 0);
-    for (uint32_t i = 0; i < n; i++)
-      if (verdicts[i] == QP_VERIFY_OK) memcpy(&pis[(size_t)i * ql::NPI], qv::public_inputs(v, proofs[i]), ql::NPI * 8);
+    std::vector<uint32_t> verdicts;
+    std::vector<uint64_t> pis;
+    if (int rc = verify_and_gather(l, "qp_ledger_cast", v, proofs, lens, n, ql::NPI, verdicts, pis)) return rc;
     return cast_screened(l, "qp_ledger_cast", pis.data(), verdicts.data(), n, reinterpret_cast<ql::Result *>(out));
   } catch (const std::bad_alloc &) {
     return bad_alloc(l, "qp_ledger_cast");
@@ -707,12 +549,8 @@ int qp_ledger_cast(qp_ledger *l, struct qp_verifier *v, const uint8_t *const *pr
 
 int qp_ledger_reserve(qp_ledger *l, uint64_t new_capacity) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_reserve");
-  if (new_capacity > ql::MAX_CAPACITY || new_capacity < l->admitted() || !new_capacity) {
-    l->err = "qp_ledger_reserve: capacity " + std::to_string(new_capacity) + " for " + std::to_string(l->admitted()) +
-             " admitted transfers: it must hold them (and at least one) and be at most 2^31";
-    return QP_ERR_ARG;
-  }
+  if (l->dead) return dead_handle(l, "qp_ledger_reserve");
+  if (int rc = check_reserve(l, "qp_ledger_reserve", new_capacity)) return rc;
   if (new_capacity == l->cap()) return QP_OK;
   if (l->ctx) return reserve_device(l, new_capacity);
   try {
@@ -720,8 +558,7 @@ int qp_ledger_reserve(qp_ledger *l, uint64_t new_capacity) {
   } catch (const std::bad_alloc &) {
     return bad_alloc(l, "qp_ledger_reserve");
   }
-  l->hlog.drop();  // the log tree's layout is the capacity's: the next commit rebuilds it
-  l->committed = 0;
+  l->lc.drop();
   return QP_OK;
 }
 
@@ -738,12 +575,9 @@ int qp_ledger_state(const qp_ledger *l, uint64_t *cast, uint64_t *admitted, uint
 
 int qp_ledger_find(qp_ledger *l, const uint64_t *nullifiers, uint32_t k, uint64_t *seq_out) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_find");
+  if (l->dead) return dead_handle(l, "qp_ledger_find");
   if (!k) return QP_OK;
-  if (!nullifiers || !seq_out) {
-    l->err = "qp_ledger_find: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!nullifiers || !seq_out) return null_buffer(l, "qp_ledger_find");
   if (int rc = canonical_keys(l, "qp_ledger_find", "nullifier", nullifiers, k)) return rc;
   if (!l->ctx) {
     for (uint32_t i = 0; i < k; i++) seq_out[i] = l->host.find(nullifiers + (size_t)i * 4);
@@ -759,12 +593,8 @@ int qp_ledger_find(qp_ledger *l, const uint64_t *nullifiers, uint32_t k, uint64_
 int qp_ledger_entries(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *nullifiers, uint64_t *numbers,
                       uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_entries");
-  if (first > l->admitted() || k > l->admitted() - first) {
-    l->err = "qp_ledger_entries: entries [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
-             std::to_string(k) + ") are outside the log's " + std::to_string(l->admitted());
-    return QP_ERR_ARG;
-  }
+  if (l->dead) return dead_handle(l, "qp_ledger_entries");
+  if (int rc = check_range(l, "qp_ledger_entries", first, k)) return rc;
   if (!k) return QP_OK;
   if (!l->ctx) {
     const ql::HostLedger &h = l->host;
@@ -790,7 +620,7 @@ int qp_ledger_entries(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *nullif
 int qp_ledger_payouts(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accounts, uint64_t *sums,
                       uint64_t *first_seq) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_payouts");
+  if (l->dead) return dead_handle(l, "qp_ledger_payouts");
   if (first > l->naccounts() || k > l->naccounts() - first) {
     l->err = "qp_ledger_payouts: accounts [" + std::to_string(first) + ", " + std::to_string(first) + " + " +
              std::to_string(k) + ") are outside the " + std::to_string(l->naccounts()) + " credited so far";
@@ -811,7 +641,7 @@ int qp_ledger_payouts(qp_ledger *l, uint64_t first, uint64_t k, uint64_t *accoun
 int qp_ledger_payouts_between(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t cap, uint64_t *accounts, uint64_t *sums,
                               uint64_t *first_seq, uint64_t *count) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_payouts_between");
+  if (l->dead) return dead_handle(l, "qp_ledger_payouts_between");
   const std::string why = ql::round_refusal(l->admitted(), m0, m1, cap, accounts, sums, first_seq, count);
   if (!why.empty()) {
     l->err = "qp_ledger_payouts_between: " + why;
@@ -841,12 +671,9 @@ int qp_ledger_payouts_between(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t c
 
 int qp_ledger_totals_for(qp_ledger *l, const uint64_t *accounts, uint32_t k, uint64_t *sums, uint8_t *found) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_totals_for");
+  if (l->dead) return dead_handle(l, "qp_ledger_totals_for");
   if (!k) return QP_OK;
-  if (!accounts) {
-    l->err = "qp_ledger_totals_for: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!accounts) return null_buffer(l, "qp_ledger_totals_for");
   if (int rc = canonical_keys(l, "qp_ledger_totals_for", "account", accounts, k)) return rc;
   if (!l->ctx) {
     for (uint32_t i = 0; i < k; i++) {
@@ -866,7 +693,7 @@ int qp_ledger_totals_for(qp_ledger *l, const uint64_t *accounts, uint32_t k, uin
 
 int qp_ledger_recount(qp_ledger *l, uint64_t out[6]) {
   if (!l || !out) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_recount");
+  if (l->dead) return dead_handle(l, "qp_ledger_recount");
   if (!l->ctx) {
     l->host.recount(out);
     return QP_OK;
@@ -882,28 +709,15 @@ int qp_ledger_recount(qp_ledger *l, uint64_t out[6]) {
 }
 
 int qp_ledger_commit_log(qp_ledger *l, uint64_t root_out[4], uint64_t *n_out) {
-  if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_commit_log");
-  if (!l->admitted()) return empty_log(l, "qp_ledger_commit_log");
-  try {
-    if (int rc = device_step(l, commit_log(l))) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(l, "qp_ledger_commit_log");
-  }
-  if (root_out) memcpy(root_out, l->log_root, 32);
-  if (n_out) *n_out = l->committed;
-  return QP_OK;
+  return qph::commit_log(l, "qp_ledger_commit_log", commit, root_out, n_out);
 }
 
 int qp_ledger_entries_at(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
                          uint32_t *amounts, uint64_t *accounts, uint8_t *flags) {
   if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_entries_at");
+  if (l->dead) return dead_handle(l, "qp_ledger_entries_at");
   if (!k) return QP_OK;
-  if (!seqs) {
-    l->err = "qp_ledger_entries_at: null buffer";
-    return QP_ERR_ARG;
-  }
+  if (!seqs) return null_buffer(l, "qp_ledger_entries_at");
   if (int rc = check_seqs(l, "qp_ledger_entries_at", seqs, k)) return rc;
   if (l->ctx) return device_step(l, entries_at_device(l, seqs, k, nullifiers, numbers, amounts, accounts, flags));
   const ql::HostLedger &h = l->host;
@@ -920,58 +734,11 @@ int qp_ledger_entries_at(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_
 
 int qp_ledger_receipts(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *siblings, uint32_t *path_bits,
                        uint32_t *depth, uint64_t *leaves, uint64_t root_out[4], uint64_t *n_out) {
-  if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_receipts");
-  if (!l->admitted()) return empty_log(l, "qp_ledger_receipts");
-  if (k && (!seqs || !siblings || !path_bits || !depth)) {
-    l->err = "qp_ledger_receipts: null buffer";
-    return QP_ERR_ARG;
-  }
-  if (int rc = check_seqs(l, "qp_ledger_receipts", seqs, k)) return rc;
-  try {
-    if (int rc = device_step(l, commit_log(l))) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(l, "qp_ledger_receipts");
-  }
-  if (root_out) memcpy(root_out, l->log_root, 32);
-  if (n_out) *n_out = l->committed;
-  if (!k) return QP_OK;
-  if (l->ctx) {
-    QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
-    return device_step(l, l->log.paths({l->err}, l->ctx->stream, seqs, k, siblings, path_bits, depth, leaves));
-  }
-  for (uint32_t i = 0; i < k; i++)
-    l->hlog.path(seqs[i], siblings + (size_t)i * ql::ACC_PATH_SLOTS * 4, path_bits + i, depth + i,
-                 leaves ? leaves + (size_t)i * 4 : nullptr);
-  return QP_OK;
+  return qph::receipts(l, "qp_ledger_receipts", commit, seqs, k, siblings, path_bits, depth, leaves, root_out, n_out);
 }
 
 int qp_ledger_roots_at(qp_ledger *l, const uint64_t *ms, uint32_t k, uint64_t *roots_out) {
-  if (!l) return QP_ERR_ARG;
-  if (l->dead) return dead_ledger(l, "qp_ledger_roots_at");
-  if (!l->admitted()) return empty_log(l, "qp_ledger_roots_at");
-  if (k && (!ms || !roots_out)) {
-    l->err = "qp_ledger_roots_at: null buffer";
-    return QP_ERR_ARG;
-  }
-  for (uint32_t i = 0; i < k; i++)
-    if (!ms[i] || ms[i] > l->admitted()) {
-      l->err = "qp_ledger_roots_at: size " + std::to_string(ms[i]) + " (position " + std::to_string(i) +
-               ") is outside 1.." + std::to_string(l->admitted()) + ", the sizes the log has had";
-      return QP_ERR_ARG;
-    }
-  try {
-    if (int rc = device_step(l, commit_log(l))) return rc;
-  } catch (const std::bad_alloc &) {
-    return bad_alloc(l, "qp_ledger_roots_at");
-  }
-  if (!k) return QP_OK;
-  if (l->ctx) {
-    QP_HIP_TRY(l, hipSetDevice(l->ctx->device));
-    return device_step(l, l->log.prefix_roots({l->err}, l->ctx->stream, ms, k, roots_out));
-  }
-  for (uint32_t i = 0; i < k; i++) l->hlog.prefix_root(ms[i], ql::log_node, roots_out + (size_t)i * 4);
-  return QP_OK;
+  return qph::roots_at(l, "qp_ledger_roots_at", commit, ql::log_node, ms, k, roots_out);
 }
 
 int qp_ledger_restore(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const uint64_t *padding_pis, uint64_t capacity,
@@ -1016,8 +783,8 @@ int qp_ledger_restore(qp_ctx *c, const uint64_t *roots, uint32_t nroots, const u
       if (r.status == ql::AUDIT_OK && expect_root) {
         // The leaves and the tree, laid out for the capacity: the restored ledger's own first commit.
         // The tree is kept, so a commit_log() that follows returns this pair with nothing launched.
-        if ((rc = commit_log(l.get()))) return refuse(rc, l->err);
-        memcpy(f.root, l->log_root, 32);
+        if ((rc = commit(l.get()))) return refuse(rc, l->err);
+        memcpy(f.root, l->lc.root, 32);
         ql::restore_verdict(f, n, expect_root, r);
       }
     }

@@ -1,8 +1,11 @@
-// ledger_audit.cpp — qp_ledger_log_audit (qpgpu.h).  An audit needs no ledger:
-// with a context the log is uploaded into buffers of this call's own, fresh
-// tables take it whole (ledger.hip's insert, probes, recount and payee
-// compaction, with the audit's three kernels in between), and the verdict is
-// ledger_audit.h's, the same the host path reaches.
+// ledger_audit.cpp — qp_ledger_log_audit (qpgpu.h), and the passes over an
+// uploaded log that it shares with qp_ledger_restore (ledger.cpp):
+// qla::audit_screen_insert_resolve.  An audit needs no ledger: with a context
+// the log is uploaded into tables of this call's own (ledger_audit_device.h's
+// LedgerTables), which take it whole (ledger.hip's insert, probes, recount and
+// payee compaction, with the audit's three kernels in between), the tree is
+// log_commit.h's whole-log form, and the verdict is ledger_audit.h's, the same
+// the host path reaches.
 #include "../../include/qpgpu.h"
 #include <string.h>
 #include <algorithm>
@@ -13,6 +16,7 @@
 #include "ledger_audit.h"
 #include "ledger_audit_device.h"
 #include "ledger_kernels.h"
+#include "log_commit.h"
 
 static_assert(sizeof(qp_ledger_audit_report) == sizeof(ql::AuditReport) && sizeof(ql::AuditReport) == 104,
               "qp_ledger_audit_report layout");
@@ -22,74 +26,72 @@ static_assert(QP_LEDGER_AUDIT_OK == ql::AUDIT_OK && QP_LEDGER_AUDIT_NON_CANONICA
                   QP_LEDGER_AUDIT_ROOT == ql::AUDIT_ROOT && QP_LEDGER_AUDIT_COMMITMENT == ql::AUDIT_COMMITMENT,
               "qp_ledger_audit_status and ledger_audit.h differ");
 
+namespace qla {
+
+int audit_screen_insert_resolve(AccErr e, hipStream_t s, const ql::AuditLog &g, const qpk::LedgerDev &d, AuditPasses &a,
+                                bool *canonical) {
+  const uint64_t n = g.n;
+  *canonical = false;
+  QP_HIP_TRY(&e, a.d_rep.alloc((sizeof(qpk::LedgerAuditDev) + 7) / 8));
+  QP_HIP_TRY(&e, a.d_stay.alloc((size_t)((n + 1) / 2)));
+  QP_HIP_TRY(&e, hipMemcpyAsync(d.nullifier, g.nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(&e, hipMemcpyAsync(d.number, g.numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(&e, hipMemcpyAsync(d.amount, g.amounts, (size_t)n * 16, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(&e, hipMemcpyAsync(d.account, g.accounts, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  QP_HIP_TRY(&e, hipMemcpyAsync(d.flags, g.flags, (size_t)n, hipMemcpyHostToDevice, s));
+  qpk::LedgerAuditDev &h = a.h;
+  memset(&h, 0, sizeof h);
+  h.credit_rule = ~0ull;
+  h.non_canonical = h.order = h.payout = qpk::LEDGER_AUDIT_NO_SEQ;
+  QP_HIP_TRY(&e, hipMemcpyAsync(a.rep(), &h, sizeof h, hipMemcpyHostToDevice, s));
+  qpk::ledger_audit_screen(d, (uint32_t)n, a.rep(), s);
+  QP_HIP_TRY(&e, hipGetLastError());
+  QP_HIP_TRY(&e, hipMemcpyAsync(&h, a.rep(), sizeof h, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(&e, hipStreamSynchronize(s));
+  if (h.non_canonical != qpk::LEDGER_AUDIT_NO_SEQ) return QP_OK;
+  qpk::ledger_insert(d, 0, (uint32_t)n, a.d_stay.as<uint32_t>(), &a.rep()->ctr, s);
+  QP_HIP_TRY(&e, hipGetLastError());
+  qpk::ledger_audit_resolve(d, (uint32_t)n, a.d_stay.as<uint32_t>(), a.rep(), s);
+  QP_HIP_TRY(&e, hipGetLastError());
+  *canonical = true;
+  return QP_OK;
+}
+
+}  // namespace qla
+
 namespace {
 
 // The passes over log [0, n) on the device.  Launch order on the one stream: screen (then a
 // synchronise: on a non-canonical log nothing is hashed), the whole-log insert, the credit rule and the
-// account sums, the recount, the payees' compaction, the leaves and the levels above them; one more
-// synchronise; then, with payouts claimed, their compare, which therefore reads the sums launches
-// after the one that added them.
+// account sums (those three are audit_screen_insert_resolve, shared with the restore), the recount, the
+// payees' compaction, the leaves and the levels above them; one more synchronise; then, with payouts
+// claimed, their compare, which therefore reads the sums launches after the one that added them.
 int audit_device(qp_ctx *c, const ql::AuditLog &g, const ql::AuditClaims &claims, ql::AuditReport &r) {
   hipStream_t s = c->stream;
   AccErr e{c->err};
-  const uint64_t n = g.n, S = ql::table_slots(n);
+  const uint64_t n = g.n;
   const uint32_t nb = qpk::ledger_blocks(n);
   QP_HIP_TRY(c, hipSetDevice(c->device));
-  DevBuf nul, num, amt, acc, fl, astay, nslot, aslot, sum, d_rep, d_stay, d_tot, d_blk, d_payee;
-  QP_HIP_TRY(c, nul.alloc((size_t)n * 4));
-  QP_HIP_TRY(c, num.alloc((size_t)n));
-  QP_HIP_TRY(c, amt.alloc((size_t)n * 2));
-  QP_HIP_TRY(c, acc.alloc((size_t)n * 4));
-  QP_HIP_TRY(c, fl.alloc((size_t)((n + 7) / 8)));
-  QP_HIP_TRY(c, astay.alloc((size_t)((n + 1) / 2)));
-  QP_HIP_TRY(c, nslot.alloc((size_t)(S / 2)));
-  QP_HIP_TRY(c, aslot.alloc((size_t)(S / 2)));
-  QP_HIP_TRY(c, sum.alloc((size_t)(S * 4)));
-  QP_HIP_TRY(c, d_rep.alloc((sizeof(qpk::LedgerAuditDev) + 7) / 8));
-  QP_HIP_TRY(c, d_stay.alloc((size_t)((n + 1) / 2)));
+  qla::LedgerTables t;
+  DevBuf d_tot, d_blk, d_payee;
+  if (int rc = qla::alloc_tables(e, s, n, t)) return rc;
   QP_HIP_TRY(c, d_tot.alloc(6));
   QP_HIP_TRY(c, d_blk.alloc(((size_t)nb + 2) / 2));
   QP_HIP_TRY(c, d_payee.alloc((size_t)((n + 1) / 2)));
-  const qpk::LedgerDev d{nul.p,
-                         num.p,
-                         amt.as<uint32_t>(),
-                         acc.p,
-                         fl.as<uint8_t>(),
-                         astay.as<uint32_t>(),
-                         nslot.as<uint32_t>(),
-                         aslot.as<uint32_t>(),
-                         sum.as<unsigned long long>(),
-                         S - 1};
-  QP_HIP_TRY(c, hipMemsetAsync(nslot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(c, hipMemsetAsync(aslot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(c, hipMemsetAsync(sum.p, 0, S * 32, s));
   QP_HIP_TRY(c, hipMemsetAsync(d_tot.p, 0, 48, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(nul.p, g.nullifiers, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(num.p, g.numbers, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(amt.p, g.amounts, (size_t)n * 16, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(acc.p, g.accounts, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  QP_HIP_TRY(c, hipMemcpyAsync(fl.p, g.flags, (size_t)n, hipMemcpyHostToDevice, s));
-  qpk::LedgerAuditDev *rep = d_rep.as<qpk::LedgerAuditDev>();
-  qpk::LedgerAuditDev h;
-  memset(&h, 0, sizeof h);
-  h.credit_rule = ~0ull;
-  h.non_canonical = h.order = h.payout = qpk::LEDGER_AUDIT_NO_SEQ;
-  QP_HIP_TRY(c, hipMemcpyAsync(rep, &h, sizeof h, hipMemcpyHostToDevice, s));
-  qpk::ledger_audit_screen(d, (uint32_t)n, rep, s);
-  QP_HIP_TRY(c, hipGetLastError());
-  QP_HIP_TRY(c, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(c, hipStreamSynchronize(s));
-  if (h.non_canonical != qpk::LEDGER_AUDIT_NO_SEQ) {
-    ql::audit_non_canonical(h.non_canonical, r);
+  const qpk::LedgerDev d = t.dev();
+  qla::AuditPasses a;
+  bool canonical = false;
+  if (int rc = qla::audit_screen_insert_resolve(e, s, g, d, a, &canonical)) return rc;
+  if (!canonical) {
+    ql::audit_non_canonical(a.h.non_canonical, r);
     return QP_OK;
   }
+  qpk::LedgerAuditDev *rep = a.rep();
+  qpk::LedgerAuditDev &h = a.h;
   uint32_t *blk = d_blk.as<uint32_t>(), *payee = d_payee.as<uint32_t>(), npayee = 0;
   uint64_t tot[6];
   ql::AuditFacts f;
-  qpk::ledger_insert(d, 0, (uint32_t)n, d_stay.as<uint32_t>(), &rep->ctr, s);
-  QP_HIP_TRY(c, hipGetLastError());
-  qpk::ledger_audit_resolve(d, (uint32_t)n, d_stay.as<uint32_t>(), rep, s);
-  QP_HIP_TRY(c, hipGetLastError());
   qpk::ledger_recount(d, (uint32_t)n, d_tot.as<unsigned long long>(), s);
   QP_HIP_TRY(c, hipGetLastError());
   qpk::ledger_payee_count(d, (uint32_t)n, blk, s);
@@ -100,13 +102,8 @@ int audit_device(qp_ctx *c, const ql::AuditLog &g, const ql::AuditClaims &claims
   QP_HIP_TRY(c, hipGetLastError());
   AccTree tree;
   qpk::AccLevels lv;
-  if (int rc = tree.alloc(e, n)) return rc;
-  qpk::acc_levels_reserved(n, n, lv);
-  qpk::ledger_leaves(d, 0, (uint32_t)n, tree.dig.p, &rep->ctr, s);
-  QP_HIP_TRY(c, hipGetLastError());
-  tree.append(lv, qpk::acc_row_max(), s);  // from an empty tree: every level
-  QP_HIP_TRY(c, hipGetLastError());
-  QP_HIP_TRY(c, hipMemcpyAsync(f.root, tree.root(lv), 32, hipMemcpyDeviceToHost, s));
+  auto leaves = [&](uint32_t first, uint32_t end, uint64_t *dig) { qpk::ledger_leaves(d, first, end, dig, &rep->ctr, s); };
+  if (int rc = log_tree_whole(e, s, tree, n, leaves, lv, f.root)) return rc;
   QP_HIP_TRY(c, hipMemcpyAsync(&npayee, blk + nb, 4, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(c, hipMemcpyAsync(tot, d_tot.p, 48, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(c, hipMemcpyAsync(&h, rep, sizeof h, hipMemcpyDeviceToHost, s));
@@ -121,11 +118,7 @@ int audit_device(qp_ctx *c, const ql::AuditLog &g, const ql::AuditClaims &claims
     return QP_ERR_HIP;
   }
   tree.lv = lv;
-  if (h.order != qpk::LEDGER_AUDIT_NO_SEQ) f.order = h.order;
-  if (h.credit_rule != ~0ull) {
-    f.credit_rule = h.credit_rule >> 32;
-    f.first = h.credit_rule & 0xFFFFFFFFu;
-  }
+  a.rule_facts(f);
   f.credited = tot[0];
   memcpy(f.sums, tot + 2, 32);
   f.accounts = npayee;
@@ -146,25 +139,9 @@ int audit_device(qp_ctx *c, const ql::AuditLog &g, const ql::AuditClaims &claims
     if (differs != qpk::LEDGER_AUDIT_NO_SEQ) f.payout = differs;
   }
   // the prefix roots of the commitments that name a prefix, in one batch, once no earlier reason fired
-  std::vector<uint64_t> ms, got;
-  std::vector<uint32_t> at(claims.ncommit, 0);
-  bool asked = false;
-  int rc = QP_OK;
-  auto prefix_root = [&](uint32_t i, uint64_t, uint64_t out[4]) {
-    if (!asked) {
-      asked = true;
-      for (uint32_t j = 0; j < claims.ncommit; j++)
-        if (claims.commit_ns[j] <= n) {
-          at[j] = (uint32_t)ms.size();
-          ms.push_back(claims.commit_ns[j]);
-        }
-      got.assign(ms.size() * 4, 0);
-      rc = tree.prefix_roots(e, s, ms.data(), (uint32_t)ms.size(), got.data());
-    }
-    memcpy(out, &got[(size_t)at[i] * 4], 32);
-  };
-  ql::audit_verdict(f, n, claims, prefix_root, r);
-  return rc;
+  PrefixRootBatch roots{tree, e, s, claims.commit_ns, claims.ncommit, n};
+  ql::audit_verdict(f, n, claims, [&roots](uint32_t i, uint64_t, uint64_t out[4]) { roots.get(i, out); }, r);
+  return roots.rc;
 }
 
 int refuse(qp_ctx *c, const std::string &why) {

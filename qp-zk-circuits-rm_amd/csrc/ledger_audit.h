@@ -2,7 +2,9 @@
 // eight statuses and their witnesses, the verdict both paths share, and the host
 // path itself (HostLedger's probes give the owner of a nullifier, the account
 // sums and the payees; HostLog the root and the prefix roots).  Plain C++ next
-// to ledger_log.h (no HIP).  Included by ledger_audit.cpp, by ledger.cpp
+// to ledger_log.h (no HIP); the commitment claims, a restore's refusals and the
+// text of a failing audit are audit_common.h's, shared with the ballot log.
+// Included by ledger_audit.cpp, by ledger.cpp
 // (qp_ledger_restore runs reasons 1-3 and the root on the ledger it builds) and
 // by the stand-alone checks tools/ledger_log_check.cpp and
 // tools/ledger_restore_check.cpp.
@@ -43,6 +45,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include "audit_common.h"
 #include "ledger_log.h"
 
 namespace ql {
@@ -50,7 +53,12 @@ namespace ql {
 // qp_ledger_audit_status (qpgpu.h)
 enum : uint32_t { AUDIT_OK = 0, AUDIT_NON_CANONICAL = 1, AUDIT_ORDER = 2, AUDIT_CREDIT_RULE = 3, AUDIT_TOTALS = 4,
                   AUDIT_PAYOUTS = 5, AUDIT_ROOT = 6, AUDIT_COMMITMENT = 7 };
-constexpr uint64_t AUDIT_NONE = ~0ull;  // no witness, no first
+using qpk::AUDIT_NONE;
+
+// the nouns of a ledger's texts, stated once: qp_ledger (ledger.cpp) inherits them for handle_common.h's
+struct Words {
+  static constexpr const char *HANDLE = "ledger", *ENTRY = "transfer", *ABI = "qp_ledger";
+};
 
 // qp_ledger_audit_report
 struct AuditReport {
@@ -123,18 +131,10 @@ inline void audit_verdict(const AuditFacts &f, uint64_t n, const AuditClaims &c,
   } else if (c.root && memcmp(c.root, f.root, 32)) {
     r.status = AUDIT_ROOT;
   } else {
-    for (uint32_t i = 0; i < c.ncommit; i++) {
-      uint64_t got[4];
-      bool holds = c.commit_ns[i] <= n;
-      if (holds) {
-        prefix_root(i, c.commit_ns[i], got);
-        holds = !memcmp(got, c.commit_roots + (size_t)i * 4, 32);
-      }
-      if (!holds) {
-        r.status = AUDIT_COMMITMENT;
-        r.witness = i;
-        return;
-      }
+    const uint64_t i = qpk::broken_commitment(c.commit_roots, c.commit_ns, c.ncommit, n, prefix_root);
+    if (i != AUDIT_NONE) {
+      r.status = AUDIT_COMMITMENT;
+      r.witness = i;
     }
   }
 }
@@ -149,13 +149,7 @@ inline std::string audit_refusal(const AuditLog &g, const AuditClaims &c) {
     for (uint64_t i = 0; i < c.npay; i++)
       if (!canonical(c.pay_accounts + i * 4, 4))
         return "the account of claimed payout " + std::to_string(i) + " is not four canonical field elements";
-  if (c.ncommit && (!c.commit_roots || !c.commit_ns)) return "null commitment buffer";
-  for (uint32_t i = 0; i < c.ncommit; i++) {
-    if (!c.commit_ns[i]) return "commitment " + std::to_string(i) + " names n = 0";
-    if (!canonical(c.commit_roots + (size_t)i * 4, 4))
-      return "the root of commitment " + std::to_string(i) + " is not four canonical field elements";
-  }
-  return "";
+  return qpk::commitment_refusal(c.commit_roots, c.commit_ns, c.ncommit);
 }
 
 // the first pass of the host path: the lowest non-canonical entry, the lowest entry out of order
@@ -234,14 +228,7 @@ inline void audit_host(const AuditLog &g, const AuditClaims &c, AuditReport &r) 
 
 // what a restore refuses beside a failing audit: "" when (capacity, cast_count) fit the log
 inline std::string restore_refusal(const uint64_t *numbers, uint64_t n, uint64_t capacity, uint64_t cast_count) {
-  if (n > MAX_CAPACITY) return "a log of " + std::to_string(n) + " entries: a ledger holds at most 2^31";
-  if (!capacity || capacity > MAX_CAPACITY || capacity < n)
-    return "capacity " + std::to_string(capacity) + " for a log of " + std::to_string(n) +
-           " entries: it must hold them (and at least one) and be at most 2^31";
-  if (n && cast_count <= numbers[n - 1])
-    return "cast_count " + std::to_string(cast_count) + " is not above the log's last transfer number " +
-           std::to_string(numbers[n - 1]);
-  return "";
+  return qpk::restore_refusal(numbers, n, capacity, cast_count, Words::HANDLE, Words::ENTRY);
 }
 
 // the verdict of a restore from the facts of a canonical log; root: the expected root, with f.root the
@@ -262,11 +249,7 @@ inline const char *audit_status_text(uint32_t status) {
 
 // the reason and the witness of a failing audit, for a refusal's message
 inline std::string audit_failure_text(const AuditReport &r) {
-  std::string s = std::string("the log fails its audit: ") + audit_status_text(r.status);
-  if (r.witness != AUDIT_NONE) s += " (entry " + std::to_string(r.witness);
-  if (r.first != AUDIT_NONE) s += ", its nullifier first at entry " + std::to_string(r.first);
-  if (r.witness != AUDIT_NONE) s += ")";
-  return s;
+  return qpk::audit_failure_text(audit_status_text(r.status), r.witness, r.first, r.status == AUDIT_COMMITMENT);
 }
 
 }  // namespace ql

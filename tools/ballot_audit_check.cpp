@@ -248,7 +248,45 @@ static void run(uint64_t n) {
   }
 }
 
+// audit_common.h through qb::'s entry points, on a log of three first ballots, against literals: a
+// commitment naming n + 1, a wrong root at index 0 and at the last index, cast_count = the last number
+void shared_commitments() {
+  const uint64_t n = 3, nul[12] = {7, 0, 0, 0, 7, 0, 0, 1, 7, 0, 0, 2}, num[3] = {4, 6, 9};
+  const uint8_t fl[3] = {3, 2, 3};
+  HostBox box;
+  HostLog log;
+  AuditFacts f;
+  CHECK(audit_facts_host(nul, num, fl, n, n, true, box, log, f));
+  uint64_t roots[12], ns[3] = {1, 2, 3};
+  for (int i = 0; i < 3; i++) log.prefix_root(ns[i], log_node, roots + 4 * i);
+  AuditClaims c;
+  c.commit_roots = roots, c.commit_ns = ns, c.ncommit = 3;
+  AuditReport r;
+  audit_host(nul, num, fl, n, c, AUDIT_ALL_REASONS, r);
+  CHECK(r.status == AUDIT_OK && r.witness == AUDIT_NONE && r.witness == ~0ull);
+  ns[1] = n + 1;
+  audit_host(nul, num, fl, n, c, AUDIT_ALL_REASONS, r);
+  CHECK(r.status == AUDIT_COMMITMENT && r.witness == 1 && r.first == ~0ull);
+  CHECK(audit_failure_text(r) == "the log fails its audit: an earlier commitment does not hold (commitment 1)");
+  ns[1] = 2;
+  roots[3] ^= 1;
+  roots[11] ^= 1;
+  audit_host(nul, num, fl, n, c, AUDIT_ALL_REASONS, r);
+  CHECK(r.status == AUDIT_COMMITMENT && r.witness == 0);
+  roots[3] ^= 1;
+  audit_host(nul, num, fl, n, c, AUDIT_ALL_REASONS, r);
+  CHECK(r.status == AUDIT_COMMITMENT && r.witness == 2);
+  ns[0] = 0;
+  CHECK(audit_refusal(n, c) == "commitment 0 names n = 0");
+  CHECK(restore_refusal(num, n, 8, 9) == "cast_count 9 is not above the log's last ballot number 9");
+  CHECK(restore_refusal(num, n, 8, 10).empty());
+  CHECK(restore_refusal(num, n, 2, 10) ==
+        "capacity 2 for a log of 3 entries: it must hold them (and at least one) and be at most 2^31");
+  CHECK(restore_refusal(num, MAX_CAPACITY + 1, 8, 10) == "a log of 2147483649 entries: a box holds at most 2^31");
+}
+
 int main() {
+  shared_commitments();
   for (uint64_t n : {1ull, 2ull, 3ull, 5ull, 64ull, 65ull, 131ull, 257ull}) run(n);
   printf("ballot_audit_check: ok\n");
   return 0;
