@@ -383,6 +383,49 @@ enum {
 };
 int qp_debug_poseidon_op(qp_ctx *ctx, uint32_t form, uint32_t param, const uint64_t *states, uint64_t nstates,
                          uint64_t *out);
+/* TEST-ONLY: a caller's witness-generator program through the production
+ * witness kernels (csrc/witness_probe.cpp; the launches are those of the
+ * prover's gen_witness_batch, csrc/witness_launch.h): every slot unset, the
+ * inputs stored, then the generators by the scheduler `form` names.
+ * gens: ngens records of five words (kind | row << 32, s[0] | s[1] << 32,
+ * s[2] | s[3] << 32, k0, k1: qc::DevGen, csrc/circuit.h) in level order;
+ * level_off[nlevels + 1] and level_pos[nlevels][2] (first Poseidon record of
+ * the level, count) as CircuitData holds them; wslot[nrows][W] the row-major
+ * wire -> slot table.  Slot ids in gens and wslot may carry bit 31 (several
+ * writers: compare-and-swap); in_slots, wslot_cm and pi_slots are plain ids.
+ * Results: vals[B][nslots] raw (2^64 - 1 where nothing was written), err[B]
+ * (0, or 1 + the index of a failing generator).  With wslot_cm (the
+ * column-major slot map [W][nrows]) also wires[B][W][nrows] and
+ * pis[B][npis] of witness_expand (wires, and pis when npis > 0, then required).
+ * The program is validated before any launch (csrc/witness_program.h): a
+ * malformed one returns QP_ERR_ARG with a text naming the fault and launches
+ * nothing.                                                                  */
+enum {
+    QP_WFORM_PROOF_256 = 0,    /* k_witness_gen, one 256-thread workgroup per proof          */
+    QP_WFORM_PROOF_512,        /* k_witness_gen, 512 threads (the aggregation circuits)      */
+    QP_WFORM_LEVEL_ROW,        /* k_witness_level per level, Poseidons one per 16-lane row   */
+    QP_WFORM_LEVEL_WAVE,       /* k_witness_level per level, Poseidons one per wave (wit_row=0) */
+    QP_WFORM_PROOF_256_WAVE,   /* k_witness_gen, 256 threads, cooperative Poseidons one per wave */
+    QP_WFORM_PROOF_512_WAVE,   /* k_witness_gen, 512 threads, cooperative Poseidons one per wave */
+    QP_WFORM_COUNT
+};
+typedef struct {
+    const uint64_t *gens;
+    uint32_t ngens;
+    const uint32_t *level_off;
+    const uint32_t *level_pos;
+    uint32_t nlevels;
+    const uint32_t *wslot;
+    uint32_t nrows, W, nslots, limbs, zero_slot, num_consts;
+    const uint32_t *in_slots;
+    const uint64_t *in_vals;   /* [B][nin] */
+    uint32_t nin, B, form;
+    const uint32_t *wslot_cm;  /* NULL: no expansion */
+    const uint32_t *pi_slots;
+    uint32_t npis;
+} qp_witness_program;
+int qp_debug_witness_program(qp_ctx *ctx, const qp_witness_program *prog, uint64_t *vals, uint32_t *err,
+                             uint64_t *wires, uint64_t *pis);
 /* host threads (the caller included) of the prover's pool for commit() and the
  * per-proof host stages; default min(hardware threads, 16).  Several provers in
  * one process should split the host cores (cores / provers each).           */

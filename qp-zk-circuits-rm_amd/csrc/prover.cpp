@@ -27,6 +27,7 @@
 #include "prover_kernels.h"
 #include "registry.h"
 #include "witness_kernels.h"
+#include "witness_launch.h"
 #include "paths.h"
 
 
@@ -886,11 +887,9 @@ int gen_witness_batch(qp_prover *P, uint32_t nb) {
   if (int rc = check_tables(P, 1, true)) return rc;
   if (P->wg_nin)
     TRY(hipMemcpyAsync(P->wg_in.p, P->h_in, (size_t)nb * P->wg_nin * 8, hipMemcpyHostToDevice, s));
-  qpk::k_witness_init<<<dim3(std::min<unsigned>(cdiv(P->wg_nslots, 256), 256), nb), 256, 0, s>>>(
-      P->wg_vals.p, P->wg_nslots, P->wg_nslots, nullptr, nullptr, 0);
-  if (P->wg_nin)
-    qpk::k_witness_inputs<<<dim3(cdiv(P->wg_nin, 256), nb), 256, 0, s>>>(
-        P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_in_slots.p, P->wg_in.p, P->wg_nin);
+  // launch shapes: witness_launch.h (shared with the test-only probe, witness_probe.cpp)
+  qpk::witness_launch_init(P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_in_slots.p, P->wg_in.p, P->wg_nin, nb,
+                           s);
   TRY(hipMemsetAsync(P->wg_err.p, 0, (size_t)nb * 4, s));
   qpk::WitnessGenArgs a;
   a.vals = P->wg_vals.p;
@@ -910,12 +909,9 @@ int gen_witness_batch(qp_prover *P, uint32_t nb) {
   // permutations: 256-leaf subtree 0.422 -> 0.415 s, witness stage 87 -> 73
   // ms), 256 for the leaf circuits
   const unsigned wthreads = P->circuit->kind == qp_circuit::AGGREGATION ? 512u : 256u;
-  // up to 4 Poseidon generators per wave per level run cooperatively (12 lanes
-  // on one permutation) instead of one per lane
-  a.coop_max = 4 * (wthreads / 64);
   // path hook wit_row=0: cooperative Poseidons one per wave instead of one per
   // 16-lane row
-  a.row = qpk::path_opt("wit_row", 1) != 0;
+  const bool row = qpk::path_opt("wit_row", 1) != 0;
   // a launch per dependency level over the whole batch (default for small
   // batches: one workgroup per proof leaves each level at a one-lane
   // permutation's latency) or one workgroup per proof (large batches, and the
@@ -931,17 +927,8 @@ int gen_witness_batch(qp_prover *P, uint32_t nb) {
   const bool by_level = wmode >= 0 ? wmode == 1
                                    : (kind == qp_circuit::AGGREGATION && nb <= 24) ||
                                          (kind == qp_circuit::WORMHOLE && nb <= 32);
-  if (by_level) {
-    const auto &lo = P->circuit->cd.level_off;
-    const auto &lp = P->circuit->cd.level_pos;
-    for (uint32_t l = 0; l < P->wg_nlev; l++) {
-      const uint32_t pcnt = lp[2 * l + 1], nother = lo[l + 1] - lo[l] - pcnt;
-      const uint32_t na = cdiv(nother, 256), npb = cdiv(pcnt, a.row ? 16 : 4);
-      if (na + npb) qpk::k_witness_level<<<dim3(na + npb, nb), 256, 0, s>>>(a, l, na);
-    }
-  } else {
-    qpk::k_witness_gen<<<nb, wthreads, 0, s>>>(a);
-  }
+  qpk::witness_launch_gens(a, qpk::WitnessForm{wthreads, by_level, row}, P->circuit->cd.level_off.data(),
+                           P->circuit->cd.level_pos.data(), nb, s);
   qpk::witness_expand(P->wg_vals.p, P->wg_nslots, (const uint32_t *)P->wg_wslot_cm.p, nw, P->wires.vals.p,
                       P->wires.cbs(), (const uint32_t *)P->wg_pi_slots.p, P->npis, P->wg_pis.p, nb, s);
   TRY(hipGetLastError());

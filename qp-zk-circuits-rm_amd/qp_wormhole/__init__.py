@@ -6,8 +6,8 @@ and plonky2's PolynomialBatch for the parity tests.  The HIP library is the
 only backend: importing the native pieces raises if it is not built.
 """
 from ._native import (GATE_KINDS, Context, FriLayer, GateDesc, PermutationData, PolynomialBatch, QpError,  # noqa: F401
-                      debug_field_op, debug_poseidon_op, fri_fold, fri_initial_poly, gate_desc, header_symbols, ifft, lde, lib,
-                      opening_set, poseidon_permute, pow_grind, quotient)
+                      debug_field_op, debug_poseidon_op, debug_witness_program, fri_fold, fri_initial_poly, gate_desc,
+                      header_symbols, ifft, lde, lib, opening_set, poseidon_permute, pow_grind, quotient)
 
 from .circuits import (Circuit, CircuitInputs, PrivateCircuitInputs, ProcessedStorageProof,  # noqa: F401,E402
                        PublicCircuitInputs, VoteCircuitData, VotePrivateInputs, VotePublicInputs, Witness)

@@ -61,6 +61,16 @@ class GateDesc(ctypes.Structure):
         return g
 
 
+class WitnessProgram(ctypes.Structure):
+    """qp_witness_program: a generator program for the TEST-ONLY qp_debug_witness_program."""
+    _fields_ = [("gens", VP), ("ngens", ctypes.c_uint32), ("level_off", VP), ("level_pos", VP),
+                ("nlevels", ctypes.c_uint32), ("wslot", VP), ("nrows", ctypes.c_uint32), ("W", ctypes.c_uint32),
+                ("nslots", ctypes.c_uint32), ("limbs", ctypes.c_uint32), ("zero_slot", ctypes.c_uint32),
+                ("num_consts", ctypes.c_uint32), ("in_slots", VP), ("in_vals", VP), ("nin", ctypes.c_uint32),
+                ("B", ctypes.c_uint32), ("form", ctypes.c_uint32), ("wslot_cm", VP), ("pi_slots", VP),
+                ("npis", ctypes.c_uint32)]
+
+
 class QpError(RuntimeError):
     def __init__(self, code, msg=""):
         self.code = code
@@ -226,6 +236,7 @@ def lib():
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),
         "qp_debug_field_op": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, U64P, VP, ctypes.c_uint64, U64P]),
         "qp_debug_poseidon_op": (ctypes.c_int, [VP, ctypes.c_uint32, ctypes.c_uint32, VP, ctypes.c_uint64, VP]),
+        "qp_debug_witness_program": (ctypes.c_int, [VP, ctypes.POINTER(WitnessProgram), VP, VP, VP, VP]),
         "qp_prover_set_host_threads": (ctypes.c_int, [VP, ctypes.c_uint32]),
         "qp_prover_kernel_stats": (ctypes.c_int, [VP, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                                   ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_int]),
@@ -437,6 +448,58 @@ def debug_poseidon_op(ctx, form, states, param=0):
     ctx.check(lib().qp_debug_poseidon_op(ctx.h, int(form), int(param), src, n, out.ctypes.data),
               "qp_debug_poseidon_op")
     return out
+
+
+# qp_debug_witness_program forms (include/qpgpu.h QP_WFORM_*)
+(WFORM_PROOF_256, WFORM_PROOF_512, WFORM_LEVEL_ROW, WFORM_LEVEL_WAVE, WFORM_PROOF_256_WAVE, WFORM_PROOF_512_WAVE,
+ WFORM_COUNT) = range(7)
+
+
+def debug_witness_program(ctx, form, gens, level_off, level_pos, wslot, nslots, in_slots, in_vals, limbs=63,
+                          zero_slot=0, num_consts=2, wslot_cm=None, pi_slots=None):
+    """TEST-ONLY (qp_debug_witness_program): the generator program through the
+    production witness kernels under scheduler `form`.  gens [ngens][5] u64
+    (DevGen words), level_off [nlevels + 1], level_pos [nlevels][2], wslot
+    [nrows][W], in_vals [B][nin].  Returns (vals [B][nslots] raw, err [B]), and
+    with wslot_cm ([W][nrows]) also (wires [B][W][nrows], pis [B][npis])."""
+    gens = np.ascontiguousarray(gens, dtype=np.uint64).reshape(-1, 5)
+    level_off = np.ascontiguousarray(level_off, dtype=np.uint32).ravel()
+    level_pos = np.ascontiguousarray(level_pos, dtype=np.uint32).reshape(-1, 2)
+    wslot = np.ascontiguousarray(wslot, dtype=np.uint32)
+    if wslot.ndim != 2:
+        raise ValueError("wslot is [nrows][W]")
+    in_slots = np.ascontiguousarray(in_slots, dtype=np.uint32).ravel()
+    in_vals = np.ascontiguousarray(in_vals, dtype=np.uint64)
+    if in_vals.ndim != 2 or in_vals.shape[1] != in_slots.size:
+        raise ValueError("in_vals is [B][nin]")
+    if level_off.size != level_pos.shape[0] + 1:
+        raise ValueError("level_off holds one entry more than level_pos has levels")
+    p = WitnessProgram()
+    p.gens, p.ngens = gens.ctypes.data, gens.shape[0]
+    p.level_off, p.level_pos, p.nlevels = level_off.ctypes.data, level_pos.ctypes.data, level_pos.shape[0]
+    p.wslot, p.nrows, p.W = wslot.ctypes.data, wslot.shape[0], wslot.shape[1]
+    p.nslots, p.limbs, p.zero_slot, p.num_consts = int(nslots), int(limbs), int(zero_slot), int(num_consts)
+    p.in_slots, p.in_vals, p.nin, p.B = in_slots.ctypes.data, in_vals.ctypes.data, in_slots.size, in_vals.shape[0]
+    p.form = int(form)
+    B = in_vals.shape[0]
+    wires = pis = None
+    if wslot_cm is not None:
+        wslot_cm = np.ascontiguousarray(wslot_cm, dtype=np.uint32)
+        if wslot_cm.shape != wslot.shape[::-1]:
+            raise ValueError("wslot_cm is [W][nrows]")
+        pi_slots = np.ascontiguousarray([] if pi_slots is None else pi_slots, dtype=np.uint32).ravel()
+        p.wslot_cm, p.pi_slots, p.npis = wslot_cm.ctypes.data, pi_slots.ctypes.data, pi_slots.size
+        if max(B, 0) * wslot.size <= 1 << 28:  # else left to the library's refusal
+            wires = np.zeros((B,) + wslot_cm.shape, np.uint64)
+            pis = np.zeros((B, pi_slots.size), np.uint64)
+    nv = B * int(nslots) if 0 < B <= 64 and 0 < int(nslots) <= 1 << 20 else 1  # a refused shape: never written
+    vals = np.zeros(nv, np.uint64)
+    err = np.zeros(max(B, 1), np.uint32)
+    ctx.check(lib().qp_debug_witness_program(ctx.h, ctypes.byref(p), vals.ctypes.data, err.ctypes.data,
+                                             None if wires is None else wires.ctypes.data,
+                                             None if pis is None else pis.ctypes.data), "qp_debug_witness_program")
+    vals = vals.reshape(B, int(nslots))
+    return (vals, err[:B]) if wslot_cm is None else (vals, err[:B], wires, pis)
 
 
 def hash_no_pad(values):
