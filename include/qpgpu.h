@@ -964,6 +964,88 @@ int qp_ledger_log_payouts_between(qp_ctx *ctx, const uint64_t *accounts_log, con
                                   const uint8_t *flags, uint64_t n, uint64_t m0, uint64_t m1, uint64_t cap,
                                   uint64_t *accounts, uint64_t *sums, uint64_t *first_seq, uint64_t *count);
 
+/* ---- the nullifier-set commitment: membership and absence proofs ----------------
+ * The log commitment proves what was admitted; it cannot prove that a nullifier
+ * was not.  A second commitment over the sorted set of admitted nullifiers can:
+ * absence is two adjacent leaves that straddle the key.  The ballot box and the
+ * transfer ledger share these definitions:
+ *   set      = the log entries whose member flag is set (a box's counted bit, a
+ *              ledger's credited bit); m = their number.  By the handles'
+ *              invariant these are the distinct admitted nullifiers;
+ *   order    = the nullifier's four felts, felt 0 first, each as a full 64-bit
+ *              unsigned word, then the log index seq as a fifth, least
+ *              significant word: total even on a malformed published log;
+ *   set leaf at sorted position j = hash_no_pad([K_j[0..4], seq_j, 2]), six
+ *              felts, one permutation;
+ *   set tree over leaves [0, m) in the log tree's convention: node =
+ *              hash_no_pad(left || right), the odd node moves up unchanged;
+ *   commitment = (set_root, m); m = 0: the root is four zeros and every absence
+ *              holds with no path;
+ *   proof for a key x: pos = the number of set keys below x, and found.  found:
+ *              the leaf at pos has key x, in the `hi` slot.  Not found: the leaf
+ *              at pos - 1 (if pos > 0; the `lo` slot) has a key below x and the
+ *              leaf at pos (if pos < m; the `hi` slot) a key above x; the two
+ *              positions are adjacent, so nothing lies between them.
+ * The constant 2 does not keep a set leaf apart from a box's log leaf (felt 5 a
+ * flags byte <= 3), nor from a node with such a right child; the position does:
+ * the checker takes the tree's shape from (j, m), never from the proof, as for
+ * receipts.  A proof holds only under the (set_root, m) it was made under.
+ * The set tree is rebuilt whole by a commit, because sorted positions move, and
+ * cached by the admitted count: a commit with nothing new launches nothing.  Its
+ * buffers (on the device two record buffers of 36 bytes per member and 64
+ * bytes per member for the tree) are its own: no other call allocates, launches or copies anything for it, and a
+ * handle that never asks for a set root pays nothing.  With a context the
+ * members are selected, sorted (a tile sort in LDS, then merge passes), hashed
+ * and searched on the device.                                                  */
+/* rebuilds the set commitment if an entry was admitted since the last one; root_out, *m_out (either
+ * may be NULL) = (set_root, m).  An empty log: (four zeros, 0).  A duplicate member cannot be
+ * reached in a handle's own log: the box's QP_ERR_STATE (the ledger's QP_ERR_HIP), and the handle is dead */
+int qp_ballot_box_commit_set(qp_ballot_box *b, uint64_t root_out[4], uint64_t *m_out);
+int qp_ledger_commit_set(qp_ledger *l, uint64_t root_out[4], uint64_t *m_out);
+/* commits the set if it is stale, then the proofs of keys[0..k) ([k][4], canonical felts, else
+ * QP_ERR_ARG naming the position before anything is enqueued): found [k], pos [k], and per slot
+ * key [k][4], seq [k], siblings [k][32][4], bits [k], depth [k] as qp_ballot_box_receipts lays a path
+ * out.  A found key's leaf is in the hi slot at pos; a slot the proof has no use for (lo: pos == 0
+ * or found; hi: pos == m) is all zero.  root_out, *m_out (either may be NULL) = the pair the proofs
+ * hold under.  k == 0: QP_OK, nothing beyond the commit                                          */
+int qp_ballot_box_set_proofs(qp_ballot_box *b, const uint64_t *keys, uint32_t k, uint8_t *found, uint64_t *pos,
+                             uint64_t *lo_key, uint64_t *lo_seq, uint64_t *lo_siblings, uint32_t *lo_bits,
+                             uint32_t *lo_depth, uint64_t *hi_key, uint64_t *hi_seq, uint64_t *hi_siblings,
+                             uint32_t *hi_bits, uint32_t *hi_depth, uint64_t root_out[4], uint64_t *m_out);
+int qp_ledger_set_proofs(qp_ledger *l, const uint64_t *keys, uint32_t k, uint8_t *found, uint64_t *pos, uint64_t *lo_key,
+                         uint64_t *lo_seq, uint64_t *lo_siblings, uint32_t *lo_bits, uint32_t *lo_depth,
+                         uint64_t *hi_key, uint64_t *hi_seq, uint64_t *hi_siblings, uint32_t *hi_bits,
+                         uint32_t *hi_depth, uint64_t root_out[4], uint64_t *m_out);
+/* the set commitment of a published log, no handle needed: nullifiers [n][4], member [n] (non-zero:
+ * the entry is in the set: a box's counted bit, a ledger's credited bit), 0 <= n <= 2^31.  root_out,
+ * *m_out = (set_root, m); order_out (may be NULL; room for n) = the members' seqs in sorted order,
+ * m of them; *dup_out (may be NULL) = UINT64_MAX, or the lowest seq of a member whose nullifier a
+ * member with a lower seq holds (the pair is then the commitment of the malformed set as sorted).
+ * QP_ERR_ARG: a null buffer, n > 2^31, a member's nullifier with a felt >= p; the reason is
+ * qp_nullifier_set_last_error()'s                                                               */
+int qp_nullifier_set_root(qp_ctx *ctx /* NULL: host */, const uint64_t *nullifiers, const uint8_t *member, uint64_t n,
+                          uint64_t root_out[4], uint64_t *m_out, uint64_t *order_out, uint64_t *dup_out);
+const char *qp_nullifier_set_last_error(void);
+typedef enum {
+    QP_SET_ORDER = 5 /* not lo.key < x < hi.key, or found with a key other than x; beside qp_receipt_status 0..4 */
+} qp_set_status;
+/* checks one proof against a published (set_root, m); host only, needs no handle and no device.
+ * siblings [32][4] each.  Returns QP_RECEIPT_OK or the first reason found, in this order:
+ * QP_RECEIPT_NULL; QP_RECEIPT_NON_CANONICAL (a felt >= p in root, x, a key, a seq or the siblings);
+ * QP_RECEIPT_SHAPE (m > 2^31, pos > m, found > 1, found with pos == m, a path whose depth or side
+ * bits are not the ones (j, m) gives, a non-zero sibling slot above the depth, a slot the proof has
+ * no use for that is not all zero); QP_SET_ORDER; QP_RECEIPT_ROOT (a walk does not end at root)   */
+int qp_nullifier_set_check(const uint64_t root[4], uint64_t m, const uint64_t x[4], uint32_t found, uint64_t pos,
+                           const uint64_t lo_key[4], uint64_t lo_seq, const uint64_t *lo_siblings, uint32_t lo_bits,
+                           uint32_t lo_depth, const uint64_t hi_key[4], uint64_t hi_seq, const uint64_t *hi_siblings,
+                           uint32_t hi_bits, uint32_t hi_depth);
+/* the records one workgroup sorts in LDS: the sizes at which the device sort changes path */
+uint32_t qp_nullifier_set_tile(void);
+/* the stage times (ms) of the last device build of a set on this thread: ms[0..4) = select, tile
+ * sort (with the host's wait for m), duplicates + leaves, levels; ms[4 + p] = merge pass p.  Returns
+ * the number written; 0: no build yet, or cap is too small (36 always suffices)                    */
+uint32_t qp_nullifier_set_times(double *ms, uint32_t cap);
+
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,
  * fri/prover.rs) a patched crate routes to the GPU for any circuit over the

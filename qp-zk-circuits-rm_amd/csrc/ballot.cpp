@@ -5,7 +5,9 @@
 // same semantics run on the host (qb::HostBox).  The log commitment (find,
 // commit_log, receipts and the receipt check: ballot_log.h) is the box's
 // LogCommit (log_commit.h), brought up to date on demand; a cast does not touch
-// it.  roots_at answers from that tree; restore reopens a box from a published
+// it.  The nullifier-set commitment (commit_set, set_proofs: nullifier_set.h) is the
+// box's SetCommit (set_commit.h) over the counted entries, rebuilt on demand
+// only.  roots_at answers from the log tree; restore reopens a box from a published
 // log through the audit's passes (ballot_audit.h, ballot_audit.cpp) and keeps
 // the table they built.  The refusals worded alike for the box and the transfer
 // ledger are handle_common.h's; what is stated here is the box's own.
@@ -26,6 +28,7 @@
 #include "ctx.h"
 #include "handle_common.h"
 #include "log_commit.h"
+#include "set_commit.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_ballot_result) == sizeof(qb::Result) && sizeof(qb::Result) == 24, "qp_ballot_result layout");
@@ -59,6 +62,7 @@ struct qp_ballot_box : qb::Words {
   TimingEvents<3> ev;  // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
   LogCommit<qb::HostLog> lc;         // the log commitment, both paths
+  SetCommit sc;                      // the nullifier-set commitment, both paths
   DevBuf d_q, d_seq, d_nul, d_flag;  // per find / entries_at batch (LOG_BATCH entries)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
@@ -196,6 +200,25 @@ int commit(qp_ballot_box *b) {
   uint32_t word = 0;
   if (int rc = b->lc.commit(b->ctx, b->err, fn, b->BROKEN, b->count, b->capacity, leaves, &ctr->err, &word)) return rc;
   return log_error_word(b, fn, word);
+}
+
+// the set commitment over the counted entries of the log as it stands, on either path.  A box's log
+// never counts one nullifier twice: a duplicate member is the defensive error.
+int commit_members(qp_ballot_box *b, const char *fn) {
+  uint64_t dup = qb::NOT_FOUND;
+  if (!b->ctx) {
+    b->sc.commit_host(b->host.nullifier.data(), b->host.flags.data(), b->host.count(), qb::FLAG_COUNTED, &dup);
+  } else {
+    const qpk::BallotDev d = b->t.dev();
+    if (int rc = b->sc.commit_device(b->ctx, b->err, d.nullifier, d.flags, b->count, qb::FLAG_COUNTED, &dup)) {
+      b->err = std::string(fn) + ": " + b->err;
+      return rc;
+    }
+  }
+  if (dup == qb::NOT_FOUND) return QP_OK;
+  b->dead = true;
+  return refuse(b, b->BROKEN, std::string(fn) + ": entry " + std::to_string(dup) +
+                                  " is counted and an earlier counted entry has its nullifier (an internal invariant broke)");
 }
 
 int entries_at_device(qp_ballot_box *b, const uint64_t *seqs, uint32_t k, uint64_t *nullifiers, uint64_t *numbers,
@@ -547,6 +570,19 @@ int qp_ballot_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, co
                             uint32_t depth) {
   if (!root || !nullifier || !siblings) return QP_RECEIPT_NULL;
   return qb::receipt_check(root, n, seq, nullifier, number, flags, siblings, path_bits, depth);
+}
+
+int qp_ballot_box_commit_set(qp_ballot_box *b, uint64_t root_out[4], uint64_t *m_out) {
+  return qph::commit_set(b, "qp_ballot_box_commit_set", commit_members, root_out, m_out);
+}
+
+int qp_ballot_box_set_proofs(qp_ballot_box *b, const uint64_t *keys, uint32_t k, uint8_t *found, uint64_t *pos,
+                             uint64_t *lo_key, uint64_t *lo_seq, uint64_t *lo_siblings, uint32_t *lo_bits,
+                             uint32_t *lo_depth, uint64_t *hi_key, uint64_t *hi_seq, uint64_t *hi_siblings,
+                             uint32_t *hi_bits, uint32_t *hi_depth, uint64_t root_out[4], uint64_t *m_out) {
+  const SetCommit::Out o{found, pos, {lo_key, hi_key}, {lo_seq, hi_seq}, {lo_siblings, hi_siblings}, {lo_bits, hi_bits},
+                         {lo_depth, hi_depth}};
+  return qph::set_proofs(b, "qp_ballot_box_set_proofs", commit_members, keys, k, o, root_out, m_out);
 }
 
 int qp_ballot_box_cast_times(const qp_ballot_box *b, double ms[2]) {

@@ -2,8 +2,8 @@
 // once for both handles (ballot.cpp, ledger.cpp): the refusals that differ by the
 // handle's nouns alone, the error of a call that has no handle to carry it, and
 // the verify-and-gather front of *_cast, and the three calls on the log
-// commitment.  H is a handle with err, dead, ctx, admitted(), cap(), its
-// LogCommit lc and the nouns H::HANDLE ("box"), H::ENTRY ("ballot") and H::ABI
+// commitment, and the two on the nullifier-set commitment.  H is a handle with
+// err, dead, ctx, admitted(), cap(), its LogCommit lc, its SetCommit sc and the nouns H::HANDLE ("box"), H::ENTRY ("ballot") and H::ABI
 // ("qp_ballot_box").  fn names the ABI call in the text.  A text that differs
 // by more than the nouns stays with its handle.
 #pragma once
@@ -191,6 +191,42 @@ int roots_at(H *h, const char *fn, Commit commit, NodeHash node, const uint64_t 
   if (int rc = commit_log(h, fn, commit, nullptr, nullptr)) return rc;
   if (!k) return QP_OK;
   return device_step(h, h->lc.roots_at(h->ctx, h->err, ms, k, node, roots_out));
+}
+
+// ---- *_commit_set and *_set_proofs (set_commit.h; nullifier_set.h has the definitions).
+// commit(h): the handle's set commit on either path (its log's nullifier column and member bit, its
+// defensive error's text and code).  An empty log has the empty set: (four zeros, 0), no refusal.
+
+// brings the set commitment up to date and stores (root, m), either of which may be null
+template <class H, class Commit>
+int commit_set(H *h, const char *fn, Commit commit, uint64_t root_out[4], uint64_t *m_out) {
+  if (!h) return QP_ERR_ARG;
+  if (h->dead) return dead_handle(h, fn);
+  try {
+    if (int rc = device_step(h, commit(h, fn))) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(h, fn);
+  }
+  h->sc.pair(root_out, m_out);
+  return QP_OK;
+}
+
+template <class H, class Commit, class Out>
+int set_proofs(H *h, const char *fn, Commit commit, const uint64_t *keys, uint32_t k, const Out &o, uint64_t root_out[4],
+               uint64_t *m_out) {
+  if (!h) return QP_ERR_ARG;
+  if (h->dead) return dead_handle(h, fn);
+  bool null = !keys || !o.found || !o.pos;
+  for (int sl = 0; sl < 2; sl++) null = null || !o.key[sl] || !o.seq[sl] || !o.sib[sl] || !o.bits[sl] || !o.depth[sl];
+  if (k && null) return null_buffer(h, fn);
+  if (int rc = canonical_keys(h, fn, "nullifier", keys, k)) return rc;
+  if (int rc = commit_set(h, fn, commit, root_out, m_out)) return rc;
+  if (!k) return QP_OK;
+  try {
+    return device_step(h, h->sc.proofs(h->ctx, h->err, keys, k, o));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(h, fn);
+  }
 }
 
 }  // namespace qph

@@ -8,7 +8,9 @@
 // The log commitment (commit_log, receipts, entries_at, roots_at and the
 // receipt check: ledger_log.h) is the ledger's LogCommit (log_commit.h), brought
 // up to date on demand; a cast does not touch it, and the tree is allocated by
-// the first commit only.  The refusals worded alike for the ledger and the
+// the first commit only.  The nullifier-set commitment (commit_set, set_proofs:
+// nullifier_set.h) is the ledger's SetCommit (set_commit.h) over the credited
+// entries, rebuilt on demand only.  The refusals worded alike for the ledger and the
 // ballot box are handle_common.h's; what is stated here is the ledger's own.
 // qp_ledger_restore reopens a ledger from a published log through the audit's
 // passes (ledger_audit.h; on the device qla::audit_screen_insert_resolve,
@@ -33,6 +35,7 @@
 #include "ledger_rounds.h"
 #include "ledger_table.h"
 #include "log_commit.h"
+#include "set_commit.h"
 #include "verifier.h"
 
 static_assert(sizeof(qp_transfer_result) == sizeof(ql::Result) && sizeof(ql::Result) == 24 &&
@@ -78,6 +81,7 @@ struct qp_ledger : ql::Words {
   TimingEvents<3> ev;                               // upload start, upload end, resolve end of the last cast
   float ms[2] = {0, 0};
   LogCommit<ql::HostLog> lc;               // the log commitment, both paths
+  SetCommit sc;                            // the nullifier-set commitment, both paths
   DevBuf d_gacc, d_gnum, d_gamt, d_gflag;  // per entries_at batch, beside d_q (the seqs) and d_qsum (the nullifiers)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
@@ -356,6 +360,25 @@ int commit(qp_ledger *l) {
   uint32_t word = 0;
   if (int rc = l->lc.commit(l->ctx, l->err, fn, l->BROKEN, l->count, l->capacity, leaves, &ctr->err, &word)) return rc;
   return error_word(l, fn, word);
+}
+
+// the set commitment over the credited entries of the log as it stands, on either path.  A ledger's
+// log never credits one nullifier twice: a duplicate member is the defensive error.
+int commit_members(qp_ledger *l, const char *fn) {
+  uint64_t dup = ql::NOT_FOUND;
+  if (!l->ctx) {
+    l->sc.commit_host(l->host.nullifier.data(), l->host.flags.data(), l->host.count(), ql::FLAG_CREDITED, &dup);
+  } else {
+    const qpk::LedgerDev d = l->t.dev();
+    if (int rc = l->sc.commit_device(l->ctx, l->err, d.nullifier, d.flags, l->count, ql::FLAG_CREDITED, &dup)) {
+      l->err = std::string(fn) + ": " + l->err;
+      return rc;
+    }
+  }
+  if (dup == ql::NOT_FOUND) return QP_OK;
+  l->dead = true;
+  return refuse(l, l->BROKEN, std::string(fn) + ": entry " + std::to_string(dup) +
+                                  " is credited and an earlier credited entry has its nullifier (an internal invariant broke)");
 }
 
 // The device half of a restore, over the fresh ledger's own log and tables (sized for its capacity):
@@ -801,6 +824,19 @@ int qp_ledger_receipt_check(const uint64_t root[4], uint64_t n, uint64_t seq, co
                             const uint64_t *siblings, uint32_t path_bits, uint32_t depth) {
   if (!root || !nullifier || !amount || !account || !siblings) return QP_RECEIPT_NULL;
   return ql::receipt_check(root, n, seq, nullifier, number, amount, account, flags, siblings, path_bits, depth);
+}
+
+int qp_ledger_commit_set(qp_ledger *l, uint64_t root_out[4], uint64_t *m_out) {
+  return qph::commit_set(l, "qp_ledger_commit_set", commit_members, root_out, m_out);
+}
+
+int qp_ledger_set_proofs(qp_ledger *l, const uint64_t *keys, uint32_t k, uint8_t *found, uint64_t *pos, uint64_t *lo_key,
+                         uint64_t *lo_seq, uint64_t *lo_siblings, uint32_t *lo_bits, uint32_t *lo_depth,
+                         uint64_t *hi_key, uint64_t *hi_seq, uint64_t *hi_siblings, uint32_t *hi_bits,
+                         uint32_t *hi_depth, uint64_t root_out[4], uint64_t *m_out) {
+  const SetCommit::Out o{found, pos, {lo_key, hi_key}, {lo_seq, hi_seq}, {lo_siblings, hi_siblings}, {lo_bits, hi_bits},
+                         {lo_depth, hi_depth}};
+  return qph::set_proofs(l, "qp_ledger_set_proofs", commit_members, keys, k, o, root_out, m_out);
 }
 
 int qp_ledger_cast_times(const qp_ledger *l, double ms[2]) {

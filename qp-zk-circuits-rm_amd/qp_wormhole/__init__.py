@@ -21,6 +21,8 @@ from .ballot import (AUDIT_STATUS_TEXT, BALLOT_STATUS_TEXT, AuditReport, BallotB
                      BallotResult, audit_log)
 from .ledger import (LEDGER_AUDIT_STATUS_TEXT, TRANSFER_STATUS_TEXT, LedgerAuditReport, TransferReceipt,  # noqa: F401,E402
                      TransferResult, WormholeLedger, audit_ledger_log, ledger_log_payouts)
+from .nullifier_set import (NullifierLeaf, NullifierProof, check_nullifier_proof, nullifier_set_root,  # noqa: F401,E402
+                            nullifier_set_tile, nullifier_set_times)
 from .screen import INPUT_STATUS_TEXT, InputStatus, screen_inputs  # noqa: F401,E402
 
 __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorageProof", "PublicCircuitInputs",
@@ -31,4 +33,6 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "WormholeVerifier", "merkle_verify", "VoterRegistry", "BallotBox", "BallotResult", "BallotReceipt",
            "BALLOT_STATUS_TEXT", "AuditReport", "AUDIT_STATUS_TEXT", "audit_log",
            "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT", "TransferReceipt", "LedgerAuditReport",
-           "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log", "ledger_log_payouts", "INPUT_STATUS_TEXT", "InputStatus", "screen_inputs"]
+           "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log", "ledger_log_payouts", "INPUT_STATUS_TEXT", "InputStatus", "screen_inputs",
+           "NullifierLeaf", "NullifierProof", "check_nullifier_proof", "nullifier_set_root", "nullifier_set_tile",
+           "nullifier_set_times"]

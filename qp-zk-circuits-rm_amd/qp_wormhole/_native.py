@@ -231,6 +231,19 @@ def lib():
         "qp_ledger_log_payouts_between": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_uint64, ctypes.c_uint64,
                                                          ctypes.c_uint64, ctypes.c_uint64, VP, VP, VP,
                                                          ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_commit_set": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_commit_set": (ctypes.c_int, [VP, VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ballot_box_set_proofs": (ctypes.c_int, [VP, VP, ctypes.c_uint32] + [VP] * 12 +
+                                     [VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_set_proofs": (ctypes.c_int, [VP, VP, ctypes.c_uint32] + [VP] * 12 +
+                                 [VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_nullifier_set_root": (ctypes.c_int, [VP, VP, VP, ctypes.c_uint64, VP, ctypes.POINTER(ctypes.c_uint64), VP,
+                                                 ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_nullifier_set_last_error": (ctypes.c_char_p, []),
+        "qp_nullifier_set_check": (ctypes.c_int, [VP, ctypes.c_uint64, VP, ctypes.c_uint32, ctypes.c_uint64] +
+                                   [VP, ctypes.c_uint64, VP, ctypes.c_uint32, ctypes.c_uint32] * 2),
+        "qp_nullifier_set_tile": (ctypes.c_uint32, []),
+        "qp_nullifier_set_times": (ctypes.c_uint32, [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

@@ -22,6 +22,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._native import Context, QpError, lib
+from .nullifier_set import NullifierSetMixin
 from .registry import PATH_SLOTS  # sibling slots of a receipt's path: the log tree is the registry's kind of tree
 
 P = 0xFFFFFFFF00000001
@@ -115,7 +116,9 @@ def audit_log(ctx_or_none, entries, root=None, tally=None, commitments=()):
                        int(o["yes"]), int(o["no"]), int(o["counted"]))
 
 
-class BallotBox:
+class BallotBox(NullifierSetMixin):
+    _SET_ABI = "qp_ballot_box"  # commit_nullifiers, nullifier_proofs, nullifier_proof_for, check_nullifier_proof
+
     def __init__(self, ctx_or_device, proposal_id, roots, verifier=None, capacity=None):
         """proposal_id: 4 canonical felts.  roots: the accepted Merkle roots, 1 to 64
         digests (a registry's `root` of every epoch ballots may refer to).  verifier:

@@ -40,6 +40,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._native import Context, QpError, lib
+from .nullifier_set import NullifierSetMixin
 
 P = 0xFFFFFFFF00000001
 NPI = 16
@@ -262,7 +263,9 @@ def ledger_log_payouts(ctx_or_none, entries, m0=0, m1=None, raw=False):
     return _round_rows(call, m0, m1, raw)
 
 
-class WormholeLedger:
+class WormholeLedger(NullifierSetMixin):
+    _SET_ABI = "qp_ledger"  # commit_nullifiers, nullifier_proofs, nullifier_proof_for, check_nullifier_proof
+
     def __init__(self, ctx_or_device, roots, padding=None, verifier=None, capacity=None):
         """roots: the accepted storage roots, 1 to 4096 digests of 4 canonical felts.
         padding: the 16 public inputs of the aggregator's padding proof
