@@ -349,6 +349,7 @@ enum {
     QP_FOP_NT_MUL_POW2,       /* nt::mul_pow2<param>(a): param a multiple of 6 below 192   */
     QP_FOP_ACC3,              /* gfn::Acc3, groups of param (1..256) elements: mac(a[k],
                                * b[k]) for each, add_shifted(a[0], param % 64), value()   */
+    QP_FOP_PF_REDUCE_ROW_WIDE, /* pf::reduce_row_wide(al = a, ah = b): b < 2^64 - 2^32     */
     QP_FOP_COUNT
 };
 int qp_debug_field_op(qp_ctx *ctx, uint32_t op, uint32_t param, const uint64_t *a, const uint64_t *b, uint64_t n,
@@ -379,7 +380,10 @@ enum {
     QP_PFORM_COOP_MDS,         /* pc::wave_mds_row with pc::mds_coef, one state per wave    */
     QP_PFORM_ROW_MDS,          /* pc::row_mds with pc::mds_coef, one state per 16-lane row  */
     QP_PFORM_DENSE_GROUP,      /* pf::dense_group<param, pfd::GLEN[param]>, param a group start: 0, 3, .., 15, 18, 20 */
-    QP_PFORM_COUNT
+    QP_PFORM_COUNT,            /* the forms above; it stays the first id they reject        */
+    QP_PFORM_DENSE_GROUP4 = QP_PFORM_COUNT + 1, /* pf::dense_group<param, pfd4::GLEN[param], pf::TabG4>, param a group
+                                * start of the hashing path's plan: 0, 4, 8, 12, 16, 19      */
+    QP_PFORM_END
 };
 int qp_debug_poseidon_op(qp_ctx *ctx, uint32_t form, uint32_t param, const uint64_t *states, uint64_t nstates,
                          uint64_t *out);

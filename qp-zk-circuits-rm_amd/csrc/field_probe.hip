@@ -94,6 +94,7 @@ __global__ void __launch_bounds__(256) k_field_op(const uint64_t *__restrict__ a
       else if constexpr (OP == QP_FOP_GL_MUL) r = gl::mul(x, y);
       else if constexpr (OP == QP_FOP_PF_SBOX) r = pf::sbox(x);
       else if constexpr (OP == QP_FOP_PF_SBOX_C) r = pf::sbox_c(x);
+      else if constexpr (OP == QP_FOP_PF_REDUCE_ROW_WIDE) r = pf::reduce_row_wide(x, y);
       else r = pow2_e<0>(param, x);
       out[g] = r;
     }

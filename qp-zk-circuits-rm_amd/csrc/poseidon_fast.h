@@ -18,7 +18,8 @@
 //     executed except the first round's;
 //   * each row reduces in 4 instructions: value = al + 2^32 ah with
 //     al, ah < 2^60 (reduce_row) -> t = al + eps*hi32(ah) (one mad),
-//     t.hi += lo32(ah) with carry c, t += c*eps.
+//     t.hi += lo32(ah) with carry c, t += c*eps; the fourth step of a dense
+//     group (al, ah up to 2^63.72) in 5 (reduce_row_wide).
 //   * sbox x^7 = x^3 * x^4 on gfn::mul.
 // One form of each piece: the code-shape variants that were measured and lost
 // (compiler mads, C reductions, rolled rounds, multi-row asm blocks) are rows
@@ -28,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include "field_nc.h"
 #include "poseidon.h"
+#include "poseidon_dense4_consts.h"
 #include "poseidon_dense_consts.h"
 #include "poseidon_partial_consts.h"
 
@@ -72,6 +74,30 @@ __device__ __forceinline__ uint64_t reduce_row(uint64_t al, uint64_t ah) {
   const uint64_t tt = ((uint64_t)t1 << 32) | t0;
   uint64_t r;
   asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(r), "=s"(c1) : "v"(e), "v"(tt));
+  return r;
+}
+
+// value = al + 2^32 ah for any al < 2^64 and ah < 2^64 - 2^32  ->  [0, 2^64),
+// same residue: the rows of a dense group's fourth step (al, ah up to 2^63.72,
+// tests/test_poseidon_dense4.py computes the maxima from the tables).
+// With ah = 2^32 hh + hl: value = lo32(al) + 2^32 (hi32(al) + hl) + 2^64 hh.
+// The 33-bit sum hi32(al) + hl = s + 2^32 c2 hands its carry to the multiplier,
+// h = hh + c2 <= 2^32 - 1 (hh <= 2^32 - 2), so value = base + 2^64 h with
+// base = lo32(al) + 2^32 s < 2^64, and 2^64 = eps mod p: t = base + eps h with
+// the mad's carry-out c1.  c2 and c1 can coincide (al = ah = 2^63.7 with
+// hi32(al) + hl >= 2^32); c2 costs no correction of its own, it rides in h.
+// Only c1 is corrected, by + eps: on c1 the kept word is base + eps h - 2^64
+// <= (2^64 - 1) + (2^64 - 2^33 + 1) - 2^64 = 2^64 - 2^33, so adding eps stays
+// below 2^64 - 2^32 and cannot wrap.
+__device__ __forceinline__ uint64_t reduce_row_wide(uint64_t al, uint64_t ah) {
+  uint32_t s1, h, e;
+  uint64_t c2, c1, t, r;
+  asm("v_add_co_u32_e64 %0, %1, %2, %3" : "=v"(s1), "=s"(c2) : "v"(hi32(al)), "v"(lo32(ah)));
+  asm(QP_CWAIT "v_addc_co_u32_e64 %0, %1, %2, 0, %1" : "=v"(h), "+s"(c2) : "v"(hi32(ah)));
+  const uint64_t base = ((uint64_t)s1 << 32) | lo32(al);
+  asm("v_mad_u64_u32 %0, %1, %2, -1, %3" : "=v"(t), "=s"(c1) : "v"(h), "v"(base));
+  asm(QP_CWAIT "v_cndmask_b32_e64 %0, 0, -1, %1" : "=v"(e) : "s"(c1));
+  asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(r), "=s"(c1) : "v"(e), "v"(t));
   return r;
 }
 
@@ -450,14 +476,46 @@ __device__ __forceinline__ void partial_group(uint64_t s[12], const HK &hook = H
   s[0] = s0;
 }
 
-// ---- dense groups of G <= 3 partial rounds (tools/gen_poseidon_dense.py): a
+// ---- dense groups of G <= 4 partial rounds (tools/gen_poseidon_dense.py): a
 // partial round is v <- M (Z v + e_0 v_0^7) + c with Z zeroing lane 0, so G of
 // them are rows of (MZ)^m over the group-start lanes 1..11 plus columns
-// (MZ)^k M e_0 for the group's S-box outputs x_l, all exact small integers
-// (< 2^22, row sums < 2^23.85).  Every term is one mad per 32-bit half, as in
-// the dense MDS rows, where the sparse form pays six for a full-width
-// constant; al, ah stay below 2^56 (tests/test_poseidon_dense.py) and reduce
-// with reduce_row.  The hashing permutation runs the partial rounds this way.
+// (MZ)^k M e_0 for the group's S-box outputs x_l, all exact small integers.
+// Every term is one mad per 32-bit half, as in the dense MDS rows, where the
+// sparse form pays six for a full-width constant.  For m <= 3 the entries are
+// below 2^22 and the row sums below 2^23.85: al, ah stay below 2^56
+// (tests/test_poseidon_dense.py) and reduce with reduce_row.  For m = 4 the
+// entries reach 2^28.3 and the row sums 2^31.72: al, ah reach 2^63.72
+// (tests/test_poseidon_dense4.py) and reduce with reduce_row_wide.  The
+// hashing permutation runs the partial rounds in the groups of pfd4 (4,4,4,4,
+// 3,3: 2 524 mads, 88 reduced rows); the pfd tables (3,3,3,3,3,3,2,2: 2 988,
+// 110) stay for the probe.
+
+// the generated tables of a plan as compile-time values
+struct TabG3 {
+  static constexpr int GMAX = 3;
+  static constexpr int glen(int t) { return pfd::GLEN[t]; }
+  static constexpr uint32_t pow(int i) { return pfd::POW[i]; }
+  static constexpr uint32_t col(int i) { return pfd::COL[i]; }
+  static constexpr uint32_t k(int i) { return pfd::K[i]; }
+};
+struct TabG4 {
+  static constexpr int GMAX = 4;
+  static constexpr int glen(int t) { return pfd4::GLEN[t]; }
+  static constexpr uint32_t pow(int i) { return pfd4::POW[i]; }
+  static constexpr uint32_t col(int i) { return pfd4::COL[i]; }
+  static constexpr uint32_t k(int i) { return pfd4::K[i]; }
+};
+
+// Row I of step M sums to rs over the integers, so with the constant's half
+// each accumulator is at most (rs + 1)(2^32 - 1): past reduce_row's 2^60 the
+// row reduces wide (the generator's row_is_wide)
+template <class TB, int M, int I>
+constexpr bool dg_wide() {
+  uint64_t rs = 0;
+  for (int j = 0; j < 11; j++) rs += TB::pow(((M - 1) * 12 + I) * 11 + j);
+  for (int l = 0; l < M; l++) rs += TB::col(l * 12 + I);
+  return (rs + 1) * 0xFFFFFFFFull >= (1ull << 60);
+}
 
 // al += lo * C, ah += hi * C: one constant for the pair of mads (inline up to
 // 64, else an SGPR), the dead carry-outs sunk into VCC as in mac_limbs
@@ -477,58 +535,60 @@ __device__ __forceinline__ void mac_pair(uint64_t &al, uint64_t &ah, uint32_t lo
 // The newest x's column is M's column 0 (inline constants): its pair of mads
 // opens the row with the halves of K as addends (an SGPR addend leaves the
 // constant bus no room for an SGPR factor).
-template <int M, int I, int J = 1>
+template <class TB, int M, int I, int J = 1>
 __device__ __forceinline__ void dg_lane_terms(uint64_t &al, uint64_t &ah, const uint32_t lo[12], const uint32_t hi[12]) {
   if constexpr (J < 12) {
-    mac_pair<pfd::POW[((M - 1) * 12 + I) * 11 + J - 1]>(al, ah, lo[J], hi[J]);
-    dg_lane_terms<M, I, J + 1>(al, ah, lo, hi);
+    mac_pair<TB::pow(((M - 1) * 12 + I) * 11 + J - 1)>(al, ah, lo[J], hi[J]);
+    dg_lane_terms<TB, M, I, J + 1>(al, ah, lo, hi);
   }
 }
-template <int M, int I, int L>
+template <class TB, int M, int I, int L>
 __device__ __forceinline__ void dg_x_terms(uint64_t &al, uint64_t &ah, const uint32_t *xl, const uint32_t *xh) {
   if constexpr (L >= 0) {
-    mac_pair<pfd::COL[(M - 1 - L) * 12 + I]>(al, ah, xl[L], xh[L]);
-    dg_x_terms<M, I, L - 1>(al, ah, xl, xh);
+    mac_pair<TB::col((M - 1 - L) * 12 + I)>(al, ah, xl[L], xh[L]);
+    dg_x_terms<TB, M, I, L - 1>(al, ah, xl, xh);
   }
 }
-template <int T0, int M, int I>
+template <class TB, int T0, int M, int I>
 __device__ __forceinline__ uint64_t dg_row(const uint32_t lo[12], const uint32_t hi[12], const uint32_t *xl,
                                            const uint32_t *xh) {
-  constexpr uint32_t C0 = pfd::COL[I];
+  constexpr uint32_t C0 = TB::col(I);
   static_assert(C0 <= 64, "M's column 0 is inline");
-  constexpr uint64_t kl = pfd::K[((T0 + M - 1) * 12 + I) * 2], kh = pfd::K[((T0 + M - 1) * 12 + I) * 2 + 1];
+  constexpr uint64_t kl = TB::k(((T0 + M - 1) * 12 + I) * 2), kh = TB::k(((T0 + M - 1) * 12 + I) * 2 + 1);
   uint64_t al, ah;
   asm("v_mad_u64_u32 %0, vcc, %2, %4, %5\n\tv_mad_u64_u32 %1, vcc, %3, %4, %6"
       : "=&v"(al), "=&v"(ah) : "v"(xl[M - 1]), "v"(xh[M - 1]), "i"(C0), "s"(kl), "s"(kh) : "vcc");
-  dg_x_terms<M, I, M - 2>(al, ah, xl, xh);
-  dg_lane_terms<M, I>(al, ah, lo, hi);
-  return reduce_row(al, ah);
+  dg_x_terms<TB, M, I, M - 2>(al, ah, xl, xh);
+  dg_lane_terms<TB, M, I>(al, ah, lo, hi);
+  if constexpr (dg_wide<TB, M, I>()) return reduce_row_wide(al, ah);
+  else return reduce_row(al, ah);
 }
 
 // x_0 = v_0^7, then y_M (row 0 of step M) and x_M = y_M^7 for M = 1..G-1
-template <int T0, int G, int M = 1>
+template <class TB, int T0, int G, int M = 1>
 __device__ __forceinline__ void dg_lane0(const uint32_t lo[12], const uint32_t hi[12], uint32_t *xl, uint32_t *xh) {
   if constexpr (M < G) {
-    const uint64_t x = sbox(dg_row<T0, M, 0>(lo, hi, xl, xh));
+    const uint64_t x = sbox(dg_row<TB, T0, M, 0>(lo, hi, xl, xh));
     xl[M] = lo32(x);
     xh[M] = hi32(x);
-    dg_lane0<T0, G, M + 1>(lo, hi, xl, xh);
+    dg_lane0<TB, T0, G, M + 1>(lo, hi, xl, xh);
   }
 }
-template <int T0, int G, int I = 0>
+template <class TB, int T0, int G, int I = 0>
 __device__ __forceinline__ void dg_out(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12], const uint32_t *xl,
                                        const uint32_t *xh) {
   if constexpr (I < 12) {
-    s[I] = dg_row<T0, G, I>(lo, hi, xl, xh);
-    dg_out<T0, G, I + 1>(s, lo, hi, xl, xh);
+    s[I] = dg_row<TB, T0, G, I>(lo, hi, xl, xh);
+    dg_out<TB, T0, G, I + 1>(s, lo, hi, xl, xh);
   }
 }
 
 // partial rounds T0..T0+G-1 on the state entering round 4 + T0 (its constants
-// added); leaves the state entering round 4 + T0 + G
-template <int T0, int G>
+// added); leaves the state entering round 4 + T0 + G.  TB: the tables whose
+// constants K were pushed through this group (T0 a group start of TB's plan)
+template <int T0, int G, class TB = TabG3>
 __device__ __forceinline__ void dense_group(uint64_t s[12]) {
-  static_assert(G >= 1 && G <= 3 && T0 >= 0 && T0 + G <= 22, "the tables hold (MZ)^1..3");
+  static_assert(G >= 1 && G <= 4 && G <= TB::GMAX && T0 >= 0 && T0 + G <= 22, "the tables hold (MZ)^1..GMAX");
   uint32_t lo[12], hi[12], xl[G], xh[G];
 #pragma unroll
   for (int j = 1; j < 12; j++) {
@@ -538,8 +598,8 @@ __device__ __forceinline__ void dense_group(uint64_t s[12]) {
   const uint64_t x0 = sbox(s[0]);
   xl[0] = lo32(x0);
   xh[0] = hi32(x0);
-  dg_lane0<T0, G>(lo, hi, xl, xh);
-  dg_out<T0, G>(s, lo, hi, xl, xh);
+  dg_lane0<TB, T0, G>(lo, hi, xl, xh);
+  dg_out<TB, T0, G>(s, lo, hi, xl, xh);
 }
 
 // rounds R..29.  OUT: bit mask of the output lanes the caller reads (the last
@@ -547,10 +607,10 @@ __device__ __forceinline__ void dense_group(uint64_t s[12]) {
 template <int R, uint32_t OUT = 0xFFFu>
 __device__ __forceinline__ void rounds(uint64_t s[12]) {
   if constexpr (R >= 4 && R < 26) {
-    // the partial rounds, in the groups of pfd::GLEN
-    constexpr int T0 = R - 4, G = pfd::GLEN[T0];
+    // the partial rounds, in the groups of pfd4::GLEN
+    constexpr int T0 = R - 4, G = pfd4::GLEN[T0];
     static_assert(G > 0, "partial rounds are entered at a group start");
-    dense_group<T0, G>(s);
+    dense_group<T0, G, TabG4>(s);
     rounds<R + G, OUT>(s);
   } else if constexpr (R < 30) {
     sbox12(s);

@@ -32,6 +32,7 @@ bool param_ok(uint32_t form, uint32_t param) {
     case QP_PFORM_PARTIAL_DYN: return param >= 1 && param < (uint32_t)ps::ROUNDS;
     case QP_PFORM_PARTIAL_GROUP: return param <= 20 && param % pf::PF_GROUP == 0;
     case QP_PFORM_DENSE_GROUP: return param < 22 && pfd::GLEN[param] != 0;
+    case QP_PFORM_DENSE_GROUP4: return param < 22 && pfd4::GLEN[param] != 0;
     default: return form < QP_PFORM_COUNT && !param;
   }
 }
@@ -45,7 +46,7 @@ __device__ __forceinline__ void split(const uint64_t s[12], uint32_t lo[12], uin
 }
 
 // one state per lane.  P: the compile-time parameter of the form (NEXT of
-// mds_block, T0 of partial_group and dense_group); param: the run-time one (the round whose
+// mds_block, T0 of partial_group and of dense_group over either table); param: the run-time one (the round whose
 // constants the dyn forms and mds_k fold)
 template <uint32_t FORM, int P>
 __global__ void __launch_bounds__(256) k_poseidon_lane(const uint64_t *__restrict__ in, uint64_t nstates,
@@ -85,6 +86,8 @@ __global__ void __launch_bounds__(256) k_poseidon_lane(const uint64_t *__restric
       pf::partial_group<P, (22 - P) < pf::PF_GROUP ? (22 - P) : pf::PF_GROUP>(s);
     } else if constexpr (FORM == QP_PFORM_DENSE_GROUP) {
       pf::dense_group<P, pfd::GLEN[P]>(s);
+    } else if constexpr (FORM == QP_PFORM_DENSE_GROUP4) {
+      pf::dense_group<P, pfd4::GLEN[P], pf::TabG4>(s);
     } else if constexpr (FORM == QP_PFORM_FULL_ROUND_DYN) {
       pf::full_round_dyn(s, ps::RC_DEV + param * 12);
     } else {
@@ -146,6 +149,14 @@ void dense_launch(uint32_t t0, dim3 grid, hipStream_t s, const uint64_t *in, uin
   }
 }
 
+template <int T0 = 0>
+void dense4_launch(uint32_t t0, dim3 grid, hipStream_t s, const uint64_t *in, uint64_t n, uint64_t *out) {
+  if constexpr (T0 < 22) {
+    if (t0 == (uint32_t)T0) lane_launch<QP_PFORM_DENSE_GROUP4, T0>(grid, s, in, n, 0, out);
+    else dense4_launch<T0 + pfd4::GLEN[T0]>(t0, grid, s, in, n, out);
+  }
+}
+
 void launch(uint32_t form, uint32_t param, hipStream_t s, const uint64_t *in, uint64_t n, uint64_t *out) {
   if (wave_form(form) || row_form(form)) {
     const dim3 grid((unsigned)((n + (row_form(form) ? 15 : 3)) / (row_form(form) ? 16 : 4)));
@@ -172,6 +183,7 @@ void launch(uint32_t form, uint32_t param, hipStream_t s, const uint64_t *in, ui
     case QP_PFORM_MDS_INIT_SPARSE: lane_launch<QP_PFORM_MDS_INIT_SPARSE, 0>(grid, s, in, n, param, out); break;
     case QP_PFORM_PARTIAL_GROUP: group_launch(param, grid, s, in, n, out); break;
     case QP_PFORM_DENSE_GROUP: dense_launch(param, grid, s, in, n, out); break;
+    case QP_PFORM_DENSE_GROUP4: dense4_launch(param, grid, s, in, n, out); break;
     case QP_PFORM_FULL_ROUND_DYN: lane_launch<QP_PFORM_FULL_ROUND_DYN, 0>(grid, s, in, n, param, out); break;
     default: lane_launch<QP_PFORM_PARTIAL_DYN, 0>(grid, s, in, n, param, out); break;
   }

@@ -424,7 +424,7 @@ def poseidon_permute(ctx, states):
 (FOP_NT_ADD, FOP_NT_ADD4, FOP_GFN_ADD, FOP_GFN_ADD_C, FOP_PF_ADD_C, FOP_GL_ADD, FOP_NT_SUB, FOP_NT_SUB4, FOP_GL_SUB,
  FOP_NT_REDUCE, FOP_GFN_REDUCE, FOP_GL_REDUCE128, FOP_PF_REDUCE_ROW, FOP_PF_REDUCE_ROW_C, FOP_PF_SUB_SMALL,
  FOP_PF_MUL, FOP_PF_MUL_C, FOP_PF_MULK2, FOP_PF_MULK3, FOP_GL_MUL, FOP_PF_SBOX, FOP_PF_SBOX_C, FOP_NT_MUL_POW2,
- FOP_ACC3, FOP_COUNT) = range(25)
+ FOP_ACC3, FOP_PF_REDUCE_ROW_WIDE, FOP_COUNT) = range(26)
 
 
 def debug_field_op(ctx, op, a, b=None, param=0):
@@ -446,6 +446,8 @@ def debug_field_op(ctx, op, a, b=None, param=0):
 (PFORM_PERMUTE_NC, PFORM_PERMUTE_CAPZ, PFORM_ROUNDS1_L7, PFORM_COOP_PERMUTE, PFORM_ROW_PERMUTE, PFORM_MDS_BLOCK,
  PFORM_MDS_K, PFORM_MDS_MADS, PFORM_CAPZ_ROUND0, PFORM_MDS_INIT_SPARSE, PFORM_PARTIAL_GROUP, PFORM_FULL_ROUND_DYN,
  PFORM_PARTIAL_DYN, PFORM_COOP_MDS, PFORM_ROW_MDS, PFORM_DENSE_GROUP, PFORM_COUNT) = range(17)
+# forms added after those: PFORM_COUNT stays the first id the forms above reject
+PFORM_DENSE_GROUP4 = PFORM_COUNT + 1
 
 
 def debug_poseidon_op(ctx, form, states, param=0):

@@ -26,6 +26,12 @@ Tables (namespace pfd):
     K[t][i]        32-bit halves of K_m[i] for partial round t = T0 + m - 1 of its group
 
     python tools/gen_poseidon_dense.py   # writes the header, self-checks
+
+The hashing permutation runs groups of up to four (plan 4,4,4,4,3,3, tables
+m = 1..4 and k = 0..3 in namespace pfd4, 2 700 mads); the pfd tables stay for
+the probe's G <= 3 instances.
+
+    python tools/gen_poseidon_dense.py --plan4   # writes poseidon_dense4_consts.h
 """
 import importlib.util
 import os
@@ -189,7 +195,108 @@ def header_text(plan=PLAN):
     return "\n".join(L) + "\n"
 
 
+# ---- groups of up to four (--plan4 -> poseidon_dense4_consts.h, namespace pfd4) ----
+# (MZ)^4 has entries below 2^30 and row sums below 2^32, so a step-4 row over
+# 32-bit halves reaches 2^63.8: past reduce_row's 2^60, inside reduce_row_wide's
+# al < 2^64, ah < 2^64 - 2^32.  Steps 1..3 are the rows of the plan above.
+HDR4 = os.path.join(ROOT, "qp-zk-circuits-rm_amd", "csrc", "poseidon_dense4_consts.h")
+PLAN4 = (4, 4, 4, 4, 3, 3)  # 2 700 mads, 48 wide rows; 4,4,4,4,4,2 has 2 702 and 60
+REDUCE_ROW_BOUND = 1 << 60
+REDUCE_WIDE_BOUND = (1 << 64) - (1 << 32)
+
+
+def row_is_wide(rs):
+    """A row of integer sum rs hands reduce at most (rs + 1) (2^32 - 1) per
+    accumulator (the constant's half included); the device code picks the
+    reduction by the same rule (pf::dg_wide)."""
+    return (rs + 1) * H32 >= REDUCE_ROW_BOUND
+
+
+def accumulator_maxima4(plan=PLAN4):
+    """Per reduction, the largest al / ah with every half at 2^32 - 1, the
+    largest row sum and entry, and the rows (t0, m, i) that reduce wide."""
+    pw, col = tables(max(plan))
+    K = all_constants(plan)
+    w = {"entry": 0, "row_sum": 0, "acc_row": 0, "acc_wide": 0, "wide_rows": []}
+    for t0, g in group_starts(plan):
+        for m in range(1, g + 1):
+            for i in (range(W) if m == g else [0]):
+                terms = row_terms(m, i, pw, col)
+                rs, k = sum(terms), K[t0 + m - 1][i]
+                acc = max(rs * H32 + (k & H32), rs * H32 + (k >> 32))
+                w["entry"] = max(w["entry"], max(terms))
+                w["row_sum"] = max(w["row_sum"], rs)
+                if row_is_wide(rs):
+                    w["acc_wide"] = max(w["acc_wide"], acc)
+                    w["wide_rows"].append((t0, m, i))
+                else:
+                    w["acc_row"] = max(w["acc_row"], acc)
+    return w
+
+
+def reduce_counts(plan):
+    """(rows reduced, of them wide)"""
+    pw, col = tables(max(plan))
+    n = nw = 0
+    for _, g in group_starts(plan):
+        for m in range(1, g + 1):
+            for i in (range(W) if m == g else [0]):
+                n += 1
+                nw += row_is_wide(sum(row_terms(m, i, pw, col)))
+    return n, nw
+
+
+def header_text4(plan=PLAN4):
+    gmax = max(plan)
+    pw, col = tables(gmax)
+    K = all_constants(plan)
+    assert gmax == 4 and all(c > 0 for m in range(1, gmax + 1) for i in range(W) for c in pw[m][i][1:])
+    assert all(0 < c <= 64 for c in col[0]), "the seed term of every row takes an inline constant"
+    w = accumulator_maxima4(plan)
+    assert w["entry"] < 1 << 32 and w["row_sum"] < 1 << 32, "(MZ)^4 fits 32 bits"
+    assert w["acc_row"] < REDUCE_ROW_BOUND and w["acc_wide"] < REDUCE_WIDE_BOUND
+    L = []
+    L.append("// poseidon_dense4_consts.h -- GENERATED by tools/gen_poseidon_dense.py --plan4 (see there).")
+    L.append("// Poseidon-Goldilocks partial rounds in groups of up to 4 as exact small-integer rows:")
+    L.append("// POW[m-1][i][j-1] = (MZ)^m[i][j], COL[k][i] = ((MZ)^k M e_0)[i], K[t][i] the pushed round")
+    L.append("// constants (32-bit halves), GLEN[t] the length of the group starting at partial round t.")
+    L.append("#pragma once")
+    L.append("#include <stdint.h>")
+    L.append("namespace pfd4 {")
+    glen = [0] * 22
+    for t0, g in group_starts(plan):
+        glen[t0] = g
+    L.append(f"constexpr int GLEN[22] = {{{', '.join(str(x) for x in glen)}}};")
+
+    def arr(name, flat, per, fmt):
+        L.append(f"constexpr uint32_t {name}[{len(flat)}] = {{")
+        for i in range(0, len(flat), per):
+            L.append("    " + ", ".join(fmt % x for x in flat[i:i + per]) + ",")
+        L.append("};")
+
+    arr("POW", [pw[m][i][j] for m in range(1, gmax + 1) for i in range(W) for j in range(1, W)], 11, "%du")
+    arr("COL", [col[k][i] for k in range(gmax) for i in range(W)], 12, "%du")
+    arr("K", [h for t in range(22) for i in range(W) for h in (K[t][i] & H32, K[t][i] >> 32)], 8, "0x%08xu")
+    L.append("}  // namespace pfd4")
+    return "\n".join(L) + "\n"
+
+
+def main4():
+    rnd = random.Random(12)
+    states = [[0] * W, [P - 1] * W] + [[rnd.randrange(P) for _ in range(W)] for _ in range(20)]
+    for plan in (PLAN4, (4, 4, 4, 4, 4, 2)):
+        for s in states:
+            assert permute_dense_grouped(s, plan) == permute_plain(s), plan
+        print("plan %s: %d mads, %d rows reduced, %d of them wide" % ((plan, mad_count(plan)) + reduce_counts(plan)))
+    assert (mad_count(PLAN4), reduce_counts(PLAN4)) < (mad_count((4, 4, 4, 4, 4, 2)), reduce_counts((4, 4, 4, 4, 4, 2)))
+    open(HDR4, "w").write(header_text4())
+    print("dense partial-round groups %s == plain permutation; %d mads; wrote %s" % (PLAN4, mad_count(PLAN4), HDR4))
+
+
 def main():
+    import sys
+    if "--plan4" in sys.argv[1:]:
+        return main4()
     rnd = random.Random(11)
     states = [[0] * W, [P - 1] * W] + [[rnd.randrange(P) for _ in range(W)] for _ in range(20)]
     for plan in (PLAN, (3,) * 7 + (1,), (2,) * 11, (1,) * 22):
