@@ -827,7 +827,8 @@ int qp_ledger_cast_times(const qp_ledger *l, double ms[2]);
  *   the accumulator tree over leaves [0, n): node = hash_no_pad(left || right),
  *     the last node of an odd level moves up unchanged; laid out for the
  *     ledger's capacity.
- * The settler publishes (root, n, payouts).  A receipt is the entry
+ * The settler publishes (root, n, payouts), or in place of the list the payout
+ * claims commitment of the round (below).  A receipt is the entry
  * (nullifier, number, amount limbs, account, flags) plus at most 31 siblings
  * compacted as qp_registry_paths compacts them, the side bits and the depth,
  * and holds only under the (root, n) it was made under.  The checker takes the
@@ -1049,6 +1050,89 @@ uint32_t qp_nullifier_set_tile(void);
  * sort (with the host's wait for m), duplicates + leaves, levels; ms[4 + p] = merge pass p.  Returns
  * the number written; 0: no build yet, or cap is too small (36 always suffices)                    */
 uint32_t qp_nullifier_set_times(double *ms, uint32_t cap);
+
+/* ---- payout claims: one root per round, a short proof per payee -----------------
+ * A settler that publishes (root, n, payouts) makes every payee trust the list,
+ * and every payer keep it.  The claims commitment replaces the list by a root, as
+ * a Merkle distributor does: each account claims its total with a short proof,
+ * and an account that is owed nothing in the round can be shown that.  For a log
+ * range [m0, m1), 0 <= m0 <= m1 <= admitted:
+ *   rows     = exactly the rows qp_ledger_payouts_between(m0, m1) gives, A of
+ *              them: an account, four limb sums, first_seq (the lowest credited
+ *              seq of the account in the range, counted from 0 in the whole log);
+ *   order    = by account: its four felts, felt 0 first, each a full unsigned
+ *              64-bit word (the nullifier set's order, first_seq as the fifth
+ *              word); accounts are distinct within a range by construction;
+ *   total    of a row: T = sum_i sums[i] << (96 - 32 i), carry-normalised into
+ *              five 32-bit limbs t[0..5), most significant first (at most 2^31
+ *              entries of at most 2^128 each: T < 2^160): one canonical form, so
+ *              a payer reads a number, not a split;
+ *   claim leaf at sorted position j = hash_no_pad([account[0..4], t[0..5],
+ *              first_seq, 3]): 11 felts, two permutations of plonky2's overwrite
+ *              sponge, as the 14-felt log leaf: felts 0..7 into state[0..8],
+ *              permute; felts 8..10 into state[0..3] with state[3..12] kept,
+ *              permute; the digest is state[0..4];
+ *   claims tree over leaves [0, A): node = hash_no_pad(left || right), the odd
+ *              node moves up unchanged;
+ *   commitment = (claims_root, A, total[5]) for the named (m0, m1); total = the
+ *              five-limb sum of all rows (for m0 = 0, m1 = admitted: the grand
+ *              total of qp_ledger_recount).  A = 0: the zero root, a zero total,
+ *              and every absence holds with no path;
+ *   claim for account x: pos = the number of rows with an account below x, and
+ *              found.  Found: the leaf at pos (the `hi` slot) has account x, and
+ *              its total is what x is owed.  Not found: the leaf at pos - 1 (`lo`,
+ *              if pos > 0) is below x and the leaf at pos (`hi`, if pos < A)
+ *              above.  A slot the claim has no use for is all zero.
+ * A claim holds only under the (claims_root, A) of its range.  The total is
+ * published beside the root and binds nothing by itself: an auditor recomputes
+ * it from the log (qp_ledger_log_claims_root).  The ledger keeps the commitment
+ * of one range, keyed by (m0, m1): the log is append-only and final, so the same
+ * range again launches nothing, and another range rebuilds.  Its buffers are its
+ * own: no other call allocates, launches or copies anything for it, and a ledger
+ * that never asks pays nothing.  With a context the range is credited into a
+ * scratch account table (the payout round's launches), the owners are sorted by
+ * account (the nullifier set's tile sort and merge passes), and the leaves, the
+ * grand total, the levels, the search and the gathers run on the device.       */
+/* the claims commitment of log entries [m0, m1): root_out, *count_out, total_out (each may be NULL) =
+ * (claims_root, A, total).  m0 == m1: the empty commitment.  QP_ERR_ARG: m0 > m1, m1 > admitted   */
+int qp_ledger_commit_claims(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t root_out[4], uint64_t *count_out,
+                            uint32_t total_out[5]);
+/* commits the range if it is not the one held, then the claims of accounts[0..k) ([k][4], canonical
+ * felts, else QP_ERR_ARG naming the position before anything is enqueued): found [k], pos [k], and
+ * per slot account [k][4], total [k][5], first_seq [k], siblings [k][32][4], bits [k], depth [k], a
+ * path laid out as qp_ledger_set_proofs lays it out.  root_out, *count_out (either may be NULL) = the
+ * pair the claims hold under.  k == 0: QP_OK, nothing beyond the commit                          */
+int qp_ledger_claims(qp_ledger *l, uint64_t m0, uint64_t m1, const uint64_t *accounts, uint32_t k, uint8_t *found,
+                     uint64_t *pos, uint64_t *lo_account, uint32_t *lo_total, uint64_t *lo_first_seq,
+                     uint64_t *lo_siblings, uint32_t *lo_bits, uint32_t *lo_depth, uint64_t *hi_account,
+                     uint32_t *hi_total, uint64_t *hi_first_seq, uint64_t *hi_siblings, uint32_t *hi_bits,
+                     uint32_t *hi_depth, uint64_t root_out[4], uint64_t *count_out);
+/* the auditor's side, from a published log alone (accounts_log [n][4], amounts [n][4], flags [n], 1
+ * <= n <= 2^31); ctx == NULL: host.  root_out, *count_out, total_out (each may be NULL) as above;
+ * order_out (may be NULL; room for m1 - m0) = the rows' first_seq in sorted order, A of them.  Only
+ * the entries of [m0, m1) are read (with a context: uploaded).  Refusals and their error slot as
+ * qp_ledger_log_payouts_between's                                                              */
+int qp_ledger_log_claims_root(qp_ctx *ctx /* NULL: host */, const uint64_t *accounts_log, const uint32_t *amounts,
+                              const uint8_t *flags, uint64_t n, uint64_t m0, uint64_t m1, uint64_t root_out[4],
+                              uint64_t *count_out, uint32_t total_out[5], uint64_t *order_out);
+/* checks one claim against a published (claims_root, A); host only, needs no ledger and no device.
+ * siblings [32][4] each.  Returns QP_RECEIPT_OK or the first reason found, in qp_nullifier_set_check's
+ * order: QP_RECEIPT_NULL; QP_RECEIPT_NON_CANONICAL (a felt >= p in root, x, an account, a first_seq
+ * or the siblings); QP_RECEIPT_SHAPE (count > 2^31, pos > count, found > 1, found with pos == count,
+ * a path whose depth or side bits are not the ones (j, count) gives, a non-zero sibling slot above
+ * the depth, a slot the claim has no use for that is not all zero); QP_SET_ORDER (not lo.account < x
+ * < hi.account, or found with an account other than x); QP_RECEIPT_ROOT.  Total limbs are in range
+ * by their type                                                                                  */
+int qp_ledger_claim_check(const uint64_t root[4], uint64_t count, const uint64_t x[4], uint32_t found, uint64_t pos,
+                          const uint64_t lo_account[4], const uint32_t lo_total[5], uint64_t lo_first_seq,
+                          const uint64_t *lo_siblings, uint32_t lo_bits, uint32_t lo_depth, const uint64_t hi_account[4],
+                          const uint32_t hi_total[5], uint64_t hi_first_seq, const uint64_t *hi_siblings,
+                          uint32_t hi_bits, uint32_t hi_depth);
+/* the stage times (ms) of the last device build of a claims tree on this thread: ms[0..4) = credit
+ * + compaction (with the scratch's allocation and the host's wait for A), tile sort, leaves + grand
+ * total, levels; ms[4 + p] = merge pass p.  Returns the number written; 0: no build yet, or cap is
+ * too small (36 always suffices)                                                                  */
+uint32_t qp_ledger_claims_times(double *ms, uint32_t cap);
 
 /* ---- routine-level seams ---------------------------------
  * The pieces of plonky2's prove() (qp-plonky2 1.1.1 plonk/prover.rs,

@@ -10,7 +10,9 @@
 // up to date on demand; a cast does not touch it, and the tree is allocated by
 // the first commit only.  The nullifier-set commitment (commit_set, set_proofs:
 // nullifier_set.h) is the ledger's SetCommit (set_commit.h) over the credited
-// entries, rebuilt on demand only.  The refusals worded alike for the ledger and the
+// entries, rebuilt on demand only.  The payout claims commitment (commit_claims,
+// claims: claims.h) is the ledger's ClaimsCommit (claims_commit.h) over the rows
+// of one payout round, keyed by the range and built on demand only.  The refusals worded alike for the ledger and the
 // ballot box are handle_common.h's; what is stated here is the ledger's own.
 // qp_ledger_restore reopens a ledger from a published log through the audit's
 // passes (ledger_audit.h; on the device qla::audit_screen_insert_resolve,
@@ -26,6 +28,7 @@
 #include <utility>
 #include <vector>
 #include "acc_tree.h"
+#include "claims_commit.h"
 #include "ctx.h"
 #include "handle_common.h"
 #include "ledger_audit.h"
@@ -82,6 +85,7 @@ struct qp_ledger : ql::Words {
   float ms[2] = {0, 0};
   LogCommit<ql::HostLog> lc;               // the log commitment, both paths
   SetCommit sc;                            // the nullifier-set commitment, both paths
+  ClaimsCommit cc;                         // the payout claims commitment of one range, both paths
   DevBuf d_gacc, d_gnum, d_gamt, d_gflag;  // per entries_at batch, beside d_q (the seqs) and d_qsum (the nullifiers)
   uint64_t admitted() const { return ctx ? count : host.count(); }
   uint64_t cap() const { return ctx ? capacity : host.capacity; }
@@ -448,6 +452,27 @@ int entries_at_device(qp_ledger *l, const uint64_t *seqs, uint32_t k, uint64_t *
     done += nb;
   }
   return QP_OK;
+}
+
+// what both claims calls refuse first: a dead handle, a range outside the log (payouts_between's words)
+int claims_front(qp_ledger *l, const char *fn, uint64_t m0, uint64_t m1) {
+  if (l->dead) return dead_handle(l, fn);
+  uint64_t count = 0;
+  const std::string why = ql::round_refusal(l->admitted(), m0, m1, 0, nullptr, nullptr, nullptr, &count);
+  return why.empty() ? QP_OK : refuse(l, QP_ERR_ARG, std::string(fn) + ": " + why);
+}
+
+// the claims commitment of log range [m0, m1) (inside the log; the caller checked), on either path
+int commit_claims(qp_ledger *l, const char *fn, uint64_t m0, uint64_t m1) {
+  if (!l->ctx) {
+    const ql::HostLedger &h = l->host;
+    l->cc.commit_host(h.account.data(), h.amount.data(), h.flags.data(), m0, m1);
+    return QP_OK;
+  }
+  const qpk::LedgerDev d = l->t.dev();
+  const int rc = l->cc.commit_device(l->ctx, l->err, d.account + m0 * 4, d.amount + m0 * 4, d.flags + m0, m0, m1);
+  if (rc) l->err = std::string(fn) + ": " + l->err;
+  return rc == QP_ERR_OOM ? rc : device_step(l, rc);  // the buffers are the commitment's own: the ledger stands
 }
 
 }  // namespace
@@ -837,6 +862,51 @@ int qp_ledger_set_proofs(qp_ledger *l, const uint64_t *keys, uint32_t k, uint8_t
   const SetCommit::Out o{found, pos, {lo_key, hi_key}, {lo_seq, hi_seq}, {lo_siblings, hi_siblings}, {lo_bits, hi_bits},
                          {lo_depth, hi_depth}};
   return qph::set_proofs(l, "qp_ledger_set_proofs", commit_members, keys, k, o, root_out, m_out);
+}
+
+int qp_ledger_commit_claims(qp_ledger *l, uint64_t m0, uint64_t m1, uint64_t root_out[4], uint64_t *count_out,
+                            uint32_t total_out[5]) {
+  const char *fn = "qp_ledger_commit_claims";
+  if (!l) return QP_ERR_ARG;
+  if (int rc = claims_front(l, fn, m0, m1)) return rc;
+  try {
+    if (int rc = commit_claims(l, fn, m0, m1)) return rc;
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, fn);
+  }
+  l->cc.triple(root_out, count_out, total_out);
+  return QP_OK;
+}
+
+int qp_ledger_claims(qp_ledger *l, uint64_t m0, uint64_t m1, const uint64_t *accounts, uint32_t k, uint8_t *found,
+                     uint64_t *pos, uint64_t *lo_account, uint32_t *lo_total, uint64_t *lo_first_seq,
+                     uint64_t *lo_siblings, uint32_t *lo_bits, uint32_t *lo_depth, uint64_t *hi_account,
+                     uint32_t *hi_total, uint64_t *hi_first_seq, uint64_t *hi_siblings, uint32_t *hi_bits,
+                     uint32_t *hi_depth, uint64_t root_out[4], uint64_t *count_out) {
+  const char *fn = "qp_ledger_claims";
+  if (!l) return QP_ERR_ARG;
+  if (int rc = claims_front(l, fn, m0, m1)) return rc;
+  const ClaimsCommit::Out o{found,
+                            pos,
+                            {lo_account, hi_account},
+                            {lo_total, hi_total},
+                            {lo_first_seq, hi_first_seq},
+                            {lo_siblings, hi_siblings},
+                            {lo_bits, hi_bits},
+                            {lo_depth, hi_depth}};
+  bool null = !accounts || !found || !pos;
+  for (int sl = 0; sl < 2; sl++)
+    null = null || !o.account[sl] || !o.total[sl] || !o.first_seq[sl] || !o.sib[sl] || !o.bits[sl] || !o.depth[sl];
+  if (k && null) return null_buffer(l, fn);
+  if (int rc = canonical_keys(l, fn, "account", accounts, k)) return rc;
+  try {
+    if (int rc = commit_claims(l, fn, m0, m1)) return rc;
+    l->cc.triple(root_out, count_out, nullptr);
+    if (!k) return QP_OK;
+    return device_step(l, l->cc.proofs(l->ctx, l->err, accounts, k, o));
+  } catch (const std::bad_alloc &) {
+    return bad_alloc(l, fn);
+  }
 }
 
 int qp_ledger_cast_times(const qp_ledger *l, double ms[2]) {

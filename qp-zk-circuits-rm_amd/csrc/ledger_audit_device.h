@@ -75,6 +75,23 @@ int audit_screen_insert_resolve(AccErr e, hipStream_t s, const ql::AuditLog &g, 
 // thread, and c's err when there is a context (ledger.cpp)
 void set_ledgerless_error(qp_ctx *c, const std::string &why);
 
+// The scratch of a payout round and what its credit leaves there: the view's account table (aslot,
+// sum), astay [k], the owners of the range compacted in log order (payee [rows], local indices j =
+// seq - m0) and their number.
+struct RoundCredit {
+  DevBuf astay, aslot, sum, d_err, d_blk, d_payee;
+  qpk::LedgerDev v{};  // the view (ledger_kernels.h): account, amount and flags at entry m0, the scratch tables
+  uint32_t rows = 0;
+  const uint32_t *payee() const { return d_payee.as<uint32_t>(); }
+};
+
+// The credit of a range into r and the owners' compaction (ledger_rounds.cpp): the scratch's
+// allocation and memsets, ledger_round_credit, ledger_payee_count, ledger_scan, ledger_payee_write,
+// and one synchronise that reads r.rows and the defensive error word.  The first half of
+// rounds_device, and of a claims commitment's device build (claims_commit.h): one statement for both.
+int round_credit_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_m0, const uint32_t *amounts_at_m0,
+                        const uint8_t *flags_at_m0, uint64_t k, RoundCredit &r);
+
 // The device path of a payout round (ledger_rounds.cpp), shared by qp_ledger_payouts_between (the
 // pointers lead into the ledger's own log, which is only read) and qp_ledger_log_payouts_between (into
 // the uploaded range): accounts, amounts and flags are device pointers at entry m0, k = m1 - m0 >= 1.

@@ -14,38 +14,37 @@
 
 // Launch order on the one stream, every buffer but the log the call's own: the credit of the range
 // into the scratch account table and its sums; the owners' count per block, the scan, the owners'
-// write (log order = first_seq order, no sort); a synchronise for the row count; one gather of the
-// first min(cap, rows) rows.  A sum or a slot word is read only in launches after the one that writes it.
-int qla::rounds_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_m0, const uint32_t *amounts_at_m0,
-                       const uint8_t *flags_at_m0, uint64_t k, uint64_t m0, uint64_t cap, uint64_t *accounts,
-                       uint64_t *sums, uint64_t *first_seq, uint64_t *count) {
+// write (log order = first_seq order, no sort); a synchronise for the row count.  A sum or a slot word
+// is read only in launches after the one that writes it.
+int qla::round_credit_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_m0, const uint32_t *amounts_at_m0,
+                             const uint8_t *flags_at_m0, uint64_t k, RoundCredit &r) {
   AccErr e{err};
   hipStream_t s = c->stream;
   const uint64_t S = ql::table_slots(k);
   const uint32_t nb = qpk::ledger_blocks(k);
   QP_HIP_TRY(&e, hipSetDevice(c->device));
-  DevBuf astay, aslot, sum, d_err, d_blk, d_payee, o_acc, o_sum, o_seq;
-  QP_HIP_TRY(&e, astay.alloc((size_t)((k + 1) / 2)));
-  QP_HIP_TRY(&e, aslot.alloc((size_t)(S / 2)));
-  QP_HIP_TRY(&e, sum.alloc((size_t)(S * 4)));
-  QP_HIP_TRY(&e, d_err.alloc(1));
-  QP_HIP_TRY(&e, d_blk.alloc(((size_t)nb + 2) / 2));
-  QP_HIP_TRY(&e, d_payee.alloc((size_t)((k + 1) / 2)));
-  const qpk::LedgerDev v{nullptr,
-                         nullptr,
-                         const_cast<uint32_t *>(amounts_at_m0),
-                         const_cast<uint64_t *>(accounts_at_m0),
-                         const_cast<uint8_t *>(flags_at_m0),
-                         astay.as<uint32_t>(),
-                         nullptr,
-                         aslot.as<uint32_t>(),
-                         sum.as<unsigned long long>(),
-                         S - 1};
-  uint32_t *blk = d_blk.as<uint32_t>(), *payee = d_payee.as<uint32_t>(), rows = 0, bad = 0;
-  QP_HIP_TRY(&e, hipMemsetAsync(aslot.p, 0xFF, S * 4, s));
-  QP_HIP_TRY(&e, hipMemsetAsync(sum.p, 0, S * 32, s));
-  QP_HIP_TRY(&e, hipMemsetAsync(d_err.p, 0, 8, s));
-  qpk::ledger_round_credit(v, (uint32_t)k, d_err.as<uint32_t>(), s);
+  QP_HIP_TRY(&e, r.astay.alloc((size_t)((k + 1) / 2)));
+  QP_HIP_TRY(&e, r.aslot.alloc((size_t)(S / 2)));
+  QP_HIP_TRY(&e, r.sum.alloc((size_t)(S * 4)));
+  QP_HIP_TRY(&e, r.d_err.alloc(1));
+  QP_HIP_TRY(&e, r.d_blk.alloc(((size_t)nb + 2) / 2));
+  QP_HIP_TRY(&e, r.d_payee.alloc((size_t)((k + 1) / 2)));
+  r.v = qpk::LedgerDev{nullptr,
+                       nullptr,
+                       const_cast<uint32_t *>(amounts_at_m0),
+                       const_cast<uint64_t *>(accounts_at_m0),
+                       const_cast<uint8_t *>(flags_at_m0),
+                       r.astay.as<uint32_t>(),
+                       nullptr,
+                       r.aslot.as<uint32_t>(),
+                       r.sum.as<unsigned long long>(),
+                       S - 1};
+  const qpk::LedgerDev &v = r.v;
+  uint32_t *blk = r.d_blk.as<uint32_t>(), *payee = r.d_payee.as<uint32_t>(), rows = 0, bad = 0;
+  QP_HIP_TRY(&e, hipMemsetAsync(r.aslot.p, 0xFF, S * 4, s));
+  QP_HIP_TRY(&e, hipMemsetAsync(r.sum.p, 0, S * 32, s));
+  QP_HIP_TRY(&e, hipMemsetAsync(r.d_err.p, 0, 8, s));
+  qpk::ledger_round_credit(v, (uint32_t)k, r.d_err.as<uint32_t>(), s);
   QP_HIP_TRY(&e, hipGetLastError());
   qpk::ledger_payee_count(v, (uint32_t)k, blk, s);
   QP_HIP_TRY(&e, hipGetLastError());
@@ -54,7 +53,7 @@ int qla::rounds_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_
   qpk::ledger_payee_write(v, (uint32_t)k, blk, payee, s);
   QP_HIP_TRY(&e, hipGetLastError());
   QP_HIP_TRY(&e, hipMemcpyAsync(&rows, blk + nb, 4, hipMemcpyDeviceToHost, s));
-  QP_HIP_TRY(&e, hipMemcpyAsync(&bad, d_err.p, 4, hipMemcpyDeviceToHost, s));
+  QP_HIP_TRY(&e, hipMemcpyAsync(&bad, r.d_err.p, 4, hipMemcpyDeviceToHost, s));
   QP_HIP_TRY(&e, hipStreamSynchronize(s));
   if (bad || rows > k) {
     err = std::string(bad ? "the round's account table's probe found no slot"
@@ -62,6 +61,21 @@ int qla::rounds_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_
           " (an internal invariant broke)";
     return QP_ERR_HIP;
   }
+  r.rows = rows;
+  return QP_OK;
+}
+
+// The round's rows after the credit: one gather of the first min(cap, rows) rows.
+int qla::rounds_device(qp_ctx *c, std::string &err, const uint64_t *accounts_at_m0, const uint32_t *amounts_at_m0,
+                       const uint8_t *flags_at_m0, uint64_t k, uint64_t m0, uint64_t cap, uint64_t *accounts,
+                       uint64_t *sums, uint64_t *first_seq, uint64_t *count) {
+  AccErr e{err};
+  hipStream_t s = c->stream;
+  RoundCredit r;
+  DevBuf o_acc, o_sum, o_seq;
+  if (int rc = round_credit_device(c, err, accounts_at_m0, amounts_at_m0, flags_at_m0, k, r)) return rc;
+  const qpk::LedgerDev &v = r.v;
+  const uint32_t *payee = r.payee(), rows = r.rows;
   const uint32_t stored = (uint32_t)std::min<uint64_t>(cap, rows);
   if (stored) {
     QP_HIP_TRY(&e, o_acc.alloc((size_t)stored * 4));

@@ -20,7 +20,9 @@ from .registry import VoterRegistry  # noqa: F401,E402
 from .ballot import (AUDIT_STATUS_TEXT, BALLOT_STATUS_TEXT, AuditReport, BallotBox, BallotReceipt,  # noqa: F401,E402
                      BallotResult, audit_log)
 from .ledger import (LEDGER_AUDIT_STATUS_TEXT, TRANSFER_STATUS_TEXT, LedgerAuditReport, TransferReceipt,  # noqa: F401,E402
-                     TransferResult, WormholeLedger, audit_ledger_log, ledger_log_payouts)
+                     TransferResult, WormholeLedger, audit_ledger_log, ledger_log_claims_root, ledger_log_payouts)
+from .claims import (CLAIM_CHECK_TEXT, ClaimLeaf, ClaimsCommitment, PayoutClaim, check_claim,  # noqa: F401,E402
+                     check_claim_status, claims_times)
 from .nullifier_set import (NullifierLeaf, NullifierProof, check_nullifier_proof, nullifier_set_root,  # noqa: F401,E402
                             nullifier_set_tile, nullifier_set_times)
 from .screen import INPUT_STATUS_TEXT, InputStatus, screen_inputs  # noqa: F401,E402
@@ -35,4 +37,5 @@ __all__ = ["Circuit", "CircuitInputs", "PrivateCircuitInputs", "ProcessedStorage
            "WormholeLedger", "TransferResult", "TRANSFER_STATUS_TEXT", "TransferReceipt", "LedgerAuditReport",
            "LEDGER_AUDIT_STATUS_TEXT", "audit_ledger_log", "ledger_log_payouts", "INPUT_STATUS_TEXT", "InputStatus", "screen_inputs",
            "NullifierLeaf", "NullifierProof", "check_nullifier_proof", "nullifier_set_root", "nullifier_set_tile",
-           "nullifier_set_times"]
+           "nullifier_set_times", "ledger_log_claims_root", "CLAIM_CHECK_TEXT", "ClaimLeaf", "ClaimsCommitment",
+           "PayoutClaim", "check_claim", "check_claim_status", "claims_times"]

@@ -244,6 +244,15 @@ def lib():
                                    [VP, ctypes.c_uint64, VP, ctypes.c_uint32, ctypes.c_uint32] * 2),
         "qp_nullifier_set_tile": (ctypes.c_uint32, []),
         "qp_nullifier_set_times": (ctypes.c_uint32, [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]),
+        "qp_ledger_commit_claims": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP,
+                                                   ctypes.POINTER(ctypes.c_uint64), VP]),
+        "qp_ledger_claims": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_uint64, VP, ctypes.c_uint32] + [VP] * 14 +
+                             [VP, ctypes.POINTER(ctypes.c_uint64)]),
+        "qp_ledger_log_claims_root": (ctypes.c_int, [VP, VP, VP, VP, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                     VP, ctypes.POINTER(ctypes.c_uint64), VP, VP]),
+        "qp_ledger_claim_check": (ctypes.c_int, [VP, ctypes.c_uint64, VP, ctypes.c_uint32, ctypes.c_uint64] +
+                                  [VP, VP, ctypes.c_uint64, VP, ctypes.c_uint32, ctypes.c_uint32] * 2),
+        "qp_ledger_claims_times": (ctypes.c_uint32, [ctypes.POINTER(ctypes.c_double), ctypes.c_uint32]),
         "qp_prover_set_timing": (ctypes.c_int, [VP, ctypes.c_int]),
         "qp_prover_debug_force_pow": (ctypes.c_int, [VP, ctypes.c_uint64, ctypes.c_int]),
         "qp_prover_debug_drop_table": (ctypes.c_int, [VP, ctypes.c_char_p]),

@@ -33,6 +33,13 @@ A settler pays per round, per commitment (root_k, n_k): `payouts_between(n_{k-1}
 n_k)` is what round k pays, `ledger_log_payouts` the same from the published log
 alone.  `WormholeLedger.restore` reopens a ledger from its published log, so a
 settler whose process died counts on with the nullifier set it had.
+
+In place of the payout list a settler can publish one root per round:
+`commit_claims(m0, m1)` commits the round's per-account totals, sorted by
+account, to a Merkle root; `claim_for` gives an account what it is owed with a
+short proof, or a proof that it is owed nothing; `check_claim` checks one
+without a ledger, and `ledger_log_claims_root` recomputes the commitment from
+the published log alone (claims.py).
 """
 import ctypes
 from collections import namedtuple
@@ -40,6 +47,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._native import Context, QpError, lib
+from .claims import TOTAL_LIMBS, ClaimLeaf, ClaimsCommitment, PayoutClaim, check_claim, limbs_total
 from .nullifier_set import NullifierSetMixin
 
 P = 0xFFFFFFFF00000001
@@ -261,6 +269,28 @@ def ledger_log_payouts(ctx_or_none, entries, m0=0, m1=None, raw=False):
         if rc:
             raise QpError(rc, lib().qp_ledger_last_error(None).decode())
     return _round_rows(call, m0, m1, raw)
+
+
+def ledger_log_claims_root(ctx_or_none, entries, m0=0, m1=None):
+    """(root, count, total, order): the payout claims commitment of round [m0, m1) of a
+    published transfer log (`entries`: what `WormholeLedger.entries()` returned;
+    m1=None: to the end), as `WormholeLedger.commit_claims` gives it, and the rows'
+    first_seq in sorted order.  An auditor compares (root, count, total) with what
+    the settler published for the round.  The flags are trusted: `audit_ledger_log`
+    is what checks them.  With a Context the range alone is uploaded and committed
+    on the device, with None on the host; needs no ledger."""
+    _, _, amt, acc, fl = _ledger_log_arrays(entries)
+    n = len(fl)
+    m0, m1 = int(m0), n if m1 is None else int(m1)
+    room = max(m1 - m0, 0) if m1 <= MAX_CAPACITY else 0  # a range the call refuses: no buffer
+    root, count, total = np.zeros(4, np.uint64), ctypes.c_uint64(), np.zeros(TOTAL_LIMBS, np.uint32)
+    order = np.zeros(max(room, 1), np.uint64)
+    rc = lib().qp_ledger_log_claims_root(None if ctx_or_none is None else ctx_or_none.h, acc.ctypes.data, amt.ctypes.data,
+                                         fl.ctypes.data, n, m0, m1, root.ctypes.data, ctypes.byref(count),
+                                         total.ctypes.data, order.ctypes.data)
+    if rc:
+        raise QpError(rc, lib().qp_ledger_last_error(None).decode())
+    return [int(x) for x in root], count.value, limbs_total(total), [int(x) for x in order[:count.value]]
 
 
 class WormholeLedger(NullifierSetMixin):
@@ -519,6 +549,60 @@ class WormholeLedger(NullifierSetMixin):
         def call(cap, a, s, f, count):
             self._check(lib().qp_ledger_payouts_between(self.h, m0, m1, cap, a, s, f, count))
         return _round_rows(call, m0, m1, raw)
+
+    # ---- payout claims: one root per round, a short proof per payee (claims.py has the definitions)
+    def _claims_range(self, m0, m1):
+        return int(m0), self.admitted if m1 is None else int(m1)
+
+    def commit_claims(self, m0=0, m1=None):
+        """ClaimsCommitment(root, count, total, m0, m1) of the round of log entries
+        [m0, m1) (m1=None: to the end): the root over the rows of
+        `payouts_between(m0, m1)` sorted by account, their number, and the exact sum
+        of their totals.  A settler publishes it in place of the payout list.  The
+        ledger keeps one range's tree: the same range again does no work."""
+        m0, m1 = self._claims_range(m0, m1)
+        root, count, total = np.zeros(4, np.uint64), ctypes.c_uint64(), np.zeros(TOTAL_LIMBS, np.uint32)
+        self._check(lib().qp_ledger_commit_claims(self.h, m0, m1, root.ctypes.data, ctypes.byref(count),
+                                                  total.ctypes.data))
+        return ClaimsCommitment([int(x) for x in root], count.value, limbs_total(total), m0, m1)
+
+    def claims(self, accounts, m0=0, m1=None):
+        """One PayoutClaim per account (32 bytes or 4 canonical felts), all under the
+        commitment of round [m0, m1): what the account is owed with its path, or the
+        two adjacent leaves that show it is owed nothing."""
+        m0, m1 = self._claims_range(m0, m1)
+        q = _keys(accounts, "account")
+        k = len(q)
+        found, pos = np.zeros(k, np.uint8), np.zeros(k, np.uint64)
+        acc = [np.zeros((k, 4), np.uint64) for _ in range(2)]
+        tot = [np.zeros((k, TOTAL_LIMBS), np.uint32) for _ in range(2)]
+        seq = [np.zeros(k, np.uint64) for _ in range(2)]
+        sib = [np.zeros((k, PATH_SLOTS, 4), np.uint64) for _ in range(2)]
+        bits = [np.zeros(k, np.uint32) for _ in range(2)]
+        depth = [np.zeros(k, np.uint32) for _ in range(2)]
+        root, count = np.zeros(4, np.uint64), ctypes.c_uint64()
+        args = [self.h, m0, m1, q.ctypes.data, k, found.ctypes.data, pos.ctypes.data]
+        for s in range(2):
+            args += [acc[s].ctypes.data, tot[s].ctypes.data, seq[s].ctypes.data, sib[s].ctypes.data, bits[s].ctypes.data,
+                     depth[s].ctypes.data]
+        self._check(lib().qp_ledger_claims(*args, root.ctypes.data, ctypes.byref(count)))
+        root, count = [int(x) for x in root], count.value
+
+        def leaf(s, i):
+            return ClaimLeaf([int(x) for x in acc[s][i]], limbs_total(tot[s][i]), int(seq[s][i]),
+                             sib[s][i, :depth[s][i]].tolist(), int(bits[s][i]), int(depth[s][i]))
+
+        out = []
+        for i in range(k):
+            f, p = bool(found[i]), int(pos[i])
+            out.append(PayoutClaim([int(x) for x in q[i]], f, p, leaf(0, i) if not f and p > 0 else None,
+                                   leaf(1, i) if p < count else None, root, count, m0, m1))
+        return out
+
+    def claim_for(self, account, m0=0, m1=None):
+        return self.claims([account], m0, m1)[0]
+
+    check_claim = staticmethod(check_claim)
 
     def totals_for(self, accounts):
         """Per account (32 bytes or 4 felts) its exact total, or None if it was never credited."""
